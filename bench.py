@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- meshes/sec of the GATOR forward (GAT encoder + MDR head -> 6890 vertices) on N MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N = 1 runs in this process.  N > 1: one rank per GPU over RCCL.  When the script is started directly (no RANK in the
 environment) it starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process -- before
@@ -12,11 +12,21 @@ A "step" = one GATOR.forward over a batch of B synthetic poses per GPU (default:
 configs[1]; weak scaling: every rank owns its own B samples), inputs resident in HBM, followed -- for N>1 -- by the RCCL
 all-gather of the predicted vertices [N*B, 6890, 3] over xGMI.  Rank 0 prints ONE JSON line.
 
-Timing: W warm-up steps, then R blocks (default 11) of EXACTLY K steps, each block bracketed by barrier + synchronize on
-both sides and reduced with MAX over ranks; the line reports the MEDIAN block (`ms_per_step` x `steps` = that block).
+Timing: W warm-up steps, then ONE block of EXACTLY K timed steps, bracketed by barrier + synchronize on both sides and reduced
+with MAX over ranks (`ms_per_step` x `steps` = that block).  `--blocks R` / `--min-timed-s S` time R blocks of K steps (more until
+S seconds are timed) and report the MEDIAN block instead.
 
-roofline  : the dominant kernel of the forward (largest share of device time), timed live with HIP events recorded by the
-            library on the launch stream (gator_profile_*); algorithmic (fp32) FLOPs per stage from SURVEY Appendix D.
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs) and print the line.  Everything
+else below (roofline, variants, config3, parity, cpu_baseline, clocks, comm) is measured with --full only, after the timed steps;
+roofline, variants and config3 time blocks of --steps steps but of ~0.25 s at most.
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned, as DIR/<name>.npy (float32 / float64, at most
+            64 MB in all): `verts` and `pose3d` (gather mode; a fixed seeded sample of rows when the batch is larger) or
+            `error_sums` (eval mode).  Inputs and weights are seeded, so two builds compare output for output.
+
+roofline  : the dominant kernel of the forward (largest share of device time), timed with HIP events recorded by the library
+            on the launch stream (gator_profile_*) in a pass of its own after the timed steps; algorithmic (fp32) FLOPs per
+            stage from SURVEY Appendix D.
             `peak` is the ceiling of the arithmetic that kernel EXECUTES: every product runs on the 16-bit MFMA (2.5 PFLOP/s dense)
             from split fp32 operands (x3_common.h) -- token-wise linears on four partial products (weights exact on three fp16
             planes, activations rounded to two), attention cores and the vertex regressor on three (both operands on two planes) --
@@ -103,10 +113,14 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--blocks', type=int, default=11, help='timed blocks of --steps steps each (a minimum: see --min-timed-s); the median block is reported')
-    ap.add_argument('--min-timed-s', type=float, default=3.0,
+    ap.add_argument('--blocks', type=int, default=1, help='timed blocks of --steps steps each (a minimum: see --min-timed-s); the median block is reported')
+    ap.add_argument('--min-timed-s', type=float, default=0.0,
                     help='keep adding timed blocks of --steps steps until the timed region holds at least this many seconds of forwards '
                          '(N = 1; with ranks the block count must agree, so it is fixed from the first blocks by rank 0 and broadcast); 0 = exactly --blocks')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure roofline, variants, config3, parity, cpu_baseline, clocks and (N > 1) comm')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned to DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
     ap.add_argument('--config', type=int, default=0, choices=[0, 2, 3, 4, 5],
                     help='BASELINE.json preset (1-based as in VERDICT.md): 2 = B=256 J=17 fp32, 3 = B=2048 J=19 bf16, 4 = 1024 per GPU J=17 + '
                          'all-gather (8 GPUs = B 8192), 5 = evaluation mode J=19 (all-reduce only); --batch/--joints/--precision/--mode override')
@@ -118,9 +132,9 @@ def parse():
     ap.add_argument('--mode', default=None, choices=['gather', 'eval'],
                     help='N>1: all-gather the vertices (config 4) or the all-reduce-only evaluation mode (config 5)')
     ap.add_argument('--subbatch-variant', action='store_true', help='also time the sub-batch-streams=2 mode (extra key)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-variants', action='store_true', help='skip the A/B variants measured beside the headline (N = 1 only)')
-    ap.add_argument('--no-config3', action='store_true', help='skip the `config3` sub-record (BASELINE configs[2] beside the default headline, N = 1 only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip `parity` and `cpu_baseline`')
+    ap.add_argument('--no-variants', action='store_true', help='--full: skip the A/B variants measured beside the headline (N = 1 only)')
+    ap.add_argument('--no-config3', action='store_true', help='--full: skip the `config3` sub-record (BASELINE configs[2] beside the default headline, N = 1 only)')
     a = ap.parse_args()
     preset = BASELINE_CONFIGS.get(a.config, dict(batch=256, joints=17, precision='f32', mode='gather'))
     for k in ('batch', 'joints', 'precision', 'mode'):
@@ -387,6 +401,31 @@ def parity_check(model, base, alpha, J, x, verts, n=32, bar_mm=1e-3):
             'bar_mm': bar_mm}
 
 
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: bytes of array data at most (under 64 MB in all, .npy headers included)
+
+
+def dump_outputs(path, out, mode):
+    """--dump-outputs: the arrays the timed step returned, as float32 / float64 .npy files.  Gather mode: `verts` [rows, 6890, 3] and
+    `pose3d` [rows, J, 3] -- every row, or when they exceed DUMP_BYTES the same fixed sample of rows (seed 0, ascending) of both.
+    Eval mode: `error_sums` (sum MPJPE, sum PA-MPJPE, samples)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    if mode == 'eval':
+        arrays = {'error_sums': out.detach().cpu().numpy().astype(np.float64)}
+    else:
+        verts, pose3d = out[0].detach(), out[1].detach()
+        n = verts.shape[0]
+        row_bytes = (verts[0].numel() + pose3d[0].numel()) * 4
+        if n * row_bytes > DUMP_BYTES:
+            rows = np.sort(np.random.RandomState(0).choice(n, DUMP_BYTES // row_bytes, replace=False))
+            idx = torch.from_numpy(rows).to(verts.device)
+            verts, pose3d = verts.index_select(0, idx), pose3d.index_select(0, idx)
+        arrays = {'verts': verts.cpu().numpy().astype(np.float32), 'pose3d': pose3d.cpu().numpy().astype(np.float32)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), arr)
+
+
 def main():
     a = parse()
     in_group = 'RANK' in os.environ and 'WORLD_SIZE' in os.environ
@@ -446,7 +485,6 @@ def main():
     for _ in range(a.warmup):
         out = runner.step(x)
     sync()
-    model.profile(4)          # HIP-event brackets on every 4th timed step (the brackets themselves cost ~3 % of a step)
     dts = []
     for _ in range(max(1, a.blocks)):
         dt, out = block(lambda: runner.step(x), a.steps)
@@ -458,13 +496,22 @@ def main():
         for _ in range(more):
             dt, out = block(lambda: runner.step(x), a.steps)
             dts.append(dt)
-    prof = model.profile_read()
-    model.profile(0)
     dt = float(np.median(dts))
+    # --full's measurements beside the headline time blocks of --steps steps, but of ~0.25 s at most: ten variants and config3 run
+    # five blocks each, and a long headline must not stretch a --full run past minutes
+    xs = max(1, min(a.steps, int(0.25 * a.steps / dt)))
     if a.mode == 'gather':
         assert out[0].shape == (B * world, 6890, 3)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, a.mode)
+    prof = None
+    if a.full:                # stage times for `roofline`: HIP-event brackets on every 4th step (~3 % of a step), in a pass of their own
+        model.profile(4)
+        block(lambda: runner.step(x), max(xs, 40))
+        prof = model.profile_read()
+        model.profile(0)
     comm = None
-    if world > 1 or force_dist:   # outside the timed region: what the collective costs alone, and how much of it the overlap hides
+    if a.full and (world > 1 or force_dist):   # outside the timed region: what the collective costs alone, and how much of it the overlap hides
         dt_c, _ = block(lambda: model(x), a.steps)
         dt_g, _ = block(lambda: runner.comm_only(), a.steps)
         c_ms, g_ms, t_ms = dt_c / a.steps * 1e3, dt_g / a.steps * 1e3, dt / a.steps * 1e3
@@ -514,8 +561,8 @@ def main():
                         'pmc_digest': digest,
                         'avg_launch_ms': round(avg_s * 1e3, 4), 'pipe': pipe,
                         'stages_ms': {k: round(v[0] / v[1], 4) for k, v in prof.items()},
-                        'stages_note': 'HIP-event brackets on every 4th timed step; a bracketed step runs ~2 % slower, so the stages sum to slightly more than ms_per_step'}
-        if roof is None:   # no per-kernel events available (bring-up path): price the whole forward
+                        'stages_note': 'HIP-event brackets on every 4th step of a pass after the timed steps; a bracketed step runs ~2 % slower, so the stages sum to slightly more than ms_per_step'}
+        if a.full and roof is None:   # no per-kernel events available (bring-up path): price the whole forward
             roof = {'bound': 'mfma', 'kernel': 'whole forward', 'achieved': round(per_gpu_tf, 2), 'peak': PEAK_F32_TFLOPS,
                     'unit': 'TFLOP/s', 'frac': round(per_gpu_tf / PEAK_F32_TFLOPS, 4), 'traffic': None}
         jset = {17: 'Human3.6M 17-joint', 19: 'COCO 19-joint'}.get(J, '%d-joint' % J)
@@ -547,12 +594,13 @@ def main():
                 'whole_forward': {'flop_per_mesh': FLOPS_PER_MESH.get(J), 'achieved_tflops_per_gpu': round(per_gpu_tf, 2),
                                   'frac_of_fp32_peak_157.3': round(per_gpu_tf / PEAK_F32_TFLOPS, 4),
                                   'frac_of_split_precision_peak_416.7': round(per_gpu_tf / PEAK_X3_TFLOPS, 4),
-                                  'compulsory_bytes_per_mesh': BYTES_PER_MESH.get(J)},
-                'roofline': roof}
-        line['clocks'] = gpu_clocks(local)
+                                  'compulsory_bytes_per_mesh': BYTES_PER_MESH.get(J)}}
+        if a.full:
+            line['roofline'] = roof
+            line['clocks'] = gpu_clocks(local)
         if comm is not None:
             line['comm'] = comm
-        if world == 1 and not a.no_variants and a.impl == 'fused' and a.mode == 'gather':
+        if a.full and world == 1 and not a.no_variants and a.impl == 'fused' and a.mode == 'gather':
             # The same workload, same process, same box, with the library's A/B switches (read when a context is created).  The
             # headline's 431x431 attention core and its vertex regressor ROUND their operands to two fp16 planes (22 bits; output
             # parity demonstrated in tests/test_gpu_x3.py); `exact_split` is the build without any rounded operand, `fp32_mfma` every product on the
@@ -586,8 +634,8 @@ def main():
                     mv.precision = vprec
                     for _ in range(a.warmup):
                         mv(x)
-                    dv = sorted(block(lambda: mv(x), a.steps)[0] for _ in range(5))[2]
-                    variants[vname] = {'value': round(B * a.steps / dv, 1), 'ms_per_step': round(dv / a.steps * 1e3, 4)}
+                    dv = sorted(block(lambda: mv(x), xs)[0] for _ in range(5))[2]
+                    variants[vname] = {'value': round(B * xs / dv, 1), 'ms_per_step': round(dv / xs * 1e3, 4)}
                     del mv
                 finally:
                     for k, v in old.items():
@@ -608,8 +656,8 @@ def main():
                     model(x)
                 for _ in range(a.warmup):
                     graph.replay()
-                dv = sorted(block(lambda: graph.replay(), a.steps)[0] for _ in range(5))[2]
-                variants['headline replayed from a hipGraph (torch.cuda.CUDAGraph)'] = {'value': round(B * a.steps / dv, 1), 'ms_per_step': round(dv / a.steps * 1e3, 4)}
+                dv = sorted(block(lambda: graph.replay(), xs)[0] for _ in range(5))[2]
+                variants['headline replayed from a hipGraph (torch.cuda.CUDAGraph)'] = {'value': round(B * xs / dv, 1), 'ms_per_step': round(dv / xs * 1e3, 4)}
                 del graph
             except Exception as e:       # a box whose runtime refuses the capture does not invalidate the line
                 variants['headline replayed from a hipGraph (torch.cuda.CUDAGraph)'] = {'error': str(e)[:200]}
@@ -622,9 +670,9 @@ def main():
                 og = (torch.empty(B, 6890, 3, device=dev), torch.empty(B, J, 3, device=dev))
                 for _ in range(max(a.warmup, 3)):
                     mg(x, out=og)
-                dv = sorted(block(lambda: mg(x, out=og), a.steps)[0] for _ in range(5))[2]
+                dv = sorted(block(lambda: mg(x, out=og), xs)[0] for _ in range(5))[2]
                 variants['headline with the library replaying the forward from a hipGraph (gator_set_graph_replay)'] = {
-                    'value': round(B * a.steps / dv, 1), 'ms_per_step': round(dv / a.steps * 1e3, 4), 'graph_launches': mg.graph_launches()}
+                    'value': round(B * xs / dv, 1), 'ms_per_step': round(dv / xs * 1e3, 4), 'graph_launches': mg.graph_launches()}
                 del mg
             except Exception as e:
                 variants['headline with the library replaying the forward from a hipGraph (gator_set_graph_replay)'] = {'error': str(e)[:200]}
@@ -632,7 +680,7 @@ def main():
             f32v = variants.get('fp32 build at this shape (gator_forward_f32)')
             if f32v and 'value' in f32v:      # config 3's own bar (round-4 review): >= 1.6 x the fp32 build on the same box
                 line['vs_fp32_build_same_box'] = round(value / f32v['value'], 3)
-        if world == 1 and a.config == 0 and not a.no_config3 and a.impl == 'fused' and a.mode == 'gather' and (B, J, a.precision) == (256, 17, 'f32'):
+        if a.full and world == 1 and a.config == 0 and not a.no_config3 and a.impl == 'fused' and a.mode == 'gather' and (B, J, a.precision) == (256, 17, 'f32'):
             # BASELINE configs[2] (B = 2048 COCO 19-joint, 16-bit operand mode) beside the default headline, so that the driver's own run carries it
             # (round-5 review): same process, same box, the variants' protocol (median of 5 blocks of --steps steps), the fp32 build at the same
             # shape next to it, parity of 8 samples of the timed batch against the fp64 oracle.  `python bench.py --config 3` is the full line.
@@ -641,13 +689,13 @@ def main():
                 B3, J3 = c3['batch'], c3['joints']
                 m3, base3, alpha3 = build_model(J3, a.impl, dev)
                 x3 = torch.from_numpy(synthetic.synthetic_pose2d(B3, J3, seed=1003)).to(dev)
-                rec = {'workload': c3['name'], 'dtype': 'f16', 'protocol': 'median of 5 blocks of %d steps after %d warm-up steps' % (a.steps, a.warmup)}
+                rec = {'workload': c3['name'], 'dtype': 'f16', 'protocol': 'median of 5 blocks of %d steps after %d warm-up steps' % (xs, a.warmup)}
                 for prec, key in (('bf16', None), ('f32', 'fp32_build_same_shape')):
                     m3.precision = prec
                     for _ in range(a.warmup):
                         o3 = m3(x3)
-                    dv = sorted(block(lambda: m3(x3), a.steps)[0] for _ in range(5))[2]
-                    r = {'value': round(B3 * a.steps / dv, 1), 'unit': 'meshes/sec', 'ms_per_step': round(dv / a.steps * 1e3, 4)}
+                    dv = sorted(block(lambda: m3(x3), xs)[0] for _ in range(5))[2]
+                    r = {'value': round(B3 * xs / dv, 1), 'unit': 'meshes/sec', 'ms_per_step': round(dv / xs * 1e3, 4)}
                     if key is None:
                         rec.update(r)
                         if not a.no_cpu_baseline:
@@ -668,9 +716,9 @@ def main():
             m2.subbatch_streams = 2
             for _ in range(a.warmup):
                 m2(x)
-            d2 = sorted(block(lambda: m2(x), a.steps)[0] for _ in range(5))[2]
-            line['subbatch_streams_2'] = {'value': round(B * a.steps / d2, 1), 'ms_per_step': round(d2 / a.steps * 1e3, 4)}
-        if world == 1 and not a.no_cpu_baseline:
+            d2 = sorted(block(lambda: m2(x), xs)[0] for _ in range(5))[2]
+            line['subbatch_streams_2'] = {'value': round(B * xs / d2, 1), 'ms_per_step': round(d2 / xs * 1e3, 4)}
+        if a.full and world == 1 and not a.no_cpu_baseline:
             if a.mode == 'gather':
                 line['parity'] = parity_check(model, base, alpha, J, x, out[0], bar_mm=1e-3 if a.precision == 'f32' else 1.0)
             line['cpu_baseline'] = cpu_baseline(model, base, alpha, J)

@@ -183,7 +183,7 @@ def test_two_rank_rccl_gather_is_bitwise_single_process():
 def test_bench_launches_its_own_ranks():
     _need_two()
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--blocks', '2',
-                        '--batch', '64'], capture_output=True, text=True, timeout=900)
+                        '--batch', '64', '--full'], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
     assert line['n_gpus'] == 2 and line['config']['parallelism'] == 'dp2'

@@ -7,7 +7,7 @@ for rep in 1 2; do
   for lib in "$@"; do
     tag=$(basename "$lib" .so)
     if [ "$lib" = "default" ]; then unset GATOR_AMD_LIB; else export GATOR_AMD_LIB=$PWD/$lib; fi
-    python bench.py --no-cpu-baseline --no-variants --steps 20 --warmup 5 --blocks 7 ${AB_ARGS:-} > "$OUT/$tag.$rep.json" 2> "$OUT/$tag.$rep.err"
+    python bench.py --full --no-cpu-baseline --no-variants --steps 20 --warmup 5 --blocks 7 --min-timed-s 3 ${AB_ARGS:-} > "$OUT/$tag.$rep.json" 2> "$OUT/$tag.$rep.err"
     python - "$OUT/$tag.$rep.json" "$tag" "$rep" <<'PY'
 import json, sys
 try:

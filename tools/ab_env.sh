@@ -6,7 +6,7 @@ mkdir -p "$OUT"
 for rep in 1 2; do
   for spec in "$@"; do
     tag=${spec%%:*}; envs=${spec#*:}
-    env $envs python bench.py --no-cpu-baseline --no-variants --steps 20 --warmup 5 --blocks 7 --min-timed-s 1 ${AB_ARGS:-} > "$OUT/$tag.$rep.json" 2> "$OUT/$tag.$rep.err"
+    env $envs python bench.py --full --no-cpu-baseline --no-variants --steps 20 --warmup 5 --blocks 7 --min-timed-s 1 ${AB_ARGS:-} > "$OUT/$tag.$rep.json" 2> "$OUT/$tag.$rep.err"
     python - "$OUT/$tag.$rep.json" "$tag" "$rep" <<'PY'
 import json, sys
 try:
