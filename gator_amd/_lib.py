@@ -64,6 +64,8 @@ SIGNATURES = {
     'gator_preprocess_chain_f32': (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     'gator_joint_errors_f32': (_I, [_P, _P, _I, _I, _P, _I, _I, ctypes.c_float, _P, _P]),
     'gator_rigid_align_f32': (_I, [_P, _P, _I, _I, _P, _P]),
+    'gator_crop_joints_f32': (_I, [_P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
+    'gator_fit_camera_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),
     'gator_comm_unique_id': (_I, [_P]),
     'gator_comm_create': (_I, [_P, _I, _I, ctypes.POINTER(_P)]),
     'gator_comm_destroy': (_I, [_P]),

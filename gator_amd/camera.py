@@ -1,0 +1,93 @@
+"""The demo's camera step on the device (demo/run.py:21-39,123-164): from raw 2D joints and the model's 3D joints to the weak-perspective
+camera that lays the mesh over the image.
+
+  raw joints [B,J,2|3] --crop_joints-->  target in crop pixels [B,J(+2),2], bbox1 [B,4], valid [B]        demo/run.py:124-127
+  forward_joints' joints [B,n,3] + target --fit_camera-->  cam [B,3] (s, tx, ty), loss [B][, orig_cam [B,4]]   demo/run.py:138-157,21-39
+
+fit_camera runs the reference's 1500 Adam steps of models.project_net.OptimzeCamLayer for every sample of the batch in one launch;
+fit_mesh_to_image is the demo's whole flow, batched."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+DEMO_SCHEDULE = ((0, 0.1), (500, 0.05), (1000, 0.001))     # demo/run.py:135,154-157: lr 0.1, 0.05 after step 500, 0.001 after step 1000
+DEMO_CROP = 500                                             # demo/run.py:177 virtual_crop_size
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def crop_joints(joints, crop_size=DEMO_CROP, box_scale=1.25, box_aspect=1.0, add_pelvis_neck=False):
+    """joints [B,J,2|3] f32 on a HIP device (pixels) -> (xy [B,J(+2),2] in crop pixels, bbox [B,4] = bbox1 (x, y, w, h),
+    valid [B] int32: 0 where process_bbox rejects the box; xy and bbox are 0 there).  crop_size is an int or (width, height)."""
+    if not joints.is_cuda:
+        raise RuntimeError('crop_joints: joints must live on a HIP device (there is no CPU path)')
+    if joints.dim() != 3 or joints.shape[2] < 2:
+        raise ValueError('crop_joints: expected [B,J,2|3], got %s' % (tuple(joints.shape),))
+    cw, ch = (crop_size, crop_size) if np.isscalar(crop_size) else crop_size
+    x = joints.contiguous().float()
+    B, J, C = x.shape
+    dev = x.device
+    xy = torch.empty((B, J + (2 if add_pelvis_neck else 0), 2), device=dev, dtype=torch.float32)
+    bbox = torch.empty((B, 4), device=dev, dtype=torch.float32)
+    valid = torch.empty((B,), device=dev, dtype=torch.int32)
+    _lib.check(_lib.load().gator_crop_joints_f32(x.data_ptr(), B, J, C, int(bool(add_pelvis_neck)), float(box_aspect), float(box_scale),
+                                                 int(cw), int(ch), xy.data_ptr(), bbox.data_ptr(), valid.data_ptr(), _stream(dev)),
+               'gator_crop_joints_f32')
+    return xy, bbox, valid
+
+
+def fit_camera(joints3d, target, init=None, steps=1500, schedule=DEMO_SCHEDULE, crop_size=DEMO_CROP, n_fit=17, bbox=None, image_size=None):
+    """Fit the weak-perspective camera of every sample: joints3d [B,n,3] (metres), target [B,m,2] (crop pixels), both on one HIP
+    device; the first n_fit joints of each are used.  init [B,3] (default: torch.rand on the device, as OptimzeCamLayer draws it).
+    schedule: up to 8 (milestone, lr) pairs -- the first lr from step 0, every later lr from step milestone + 1.
+    -> (cam [B,3], loss [B]) or, with bbox [B,4] and image_size = (width, height), (cam, loss, orig_cam [B,4] = (sx, sy, tx, ty))."""
+    if not joints3d.is_cuda or not target.is_cuda:
+        raise RuntimeError('fit_camera: inputs must live on a HIP device (there is no CPU path)')
+    if joints3d.dim() != 3 or joints3d.shape[2] != 3 or target.dim() != 3 or target.shape[2] != 2 or target.shape[0] != joints3d.shape[0]:
+        raise ValueError('fit_camera: expected joints3d [B,n,3] and target [B,m,2], got %s and %s' % (tuple(joints3d.shape), tuple(target.shape)))
+    if (bbox is None) != (image_size is None):
+        raise ValueError('fit_camera: bbox and image_size go together')
+    dev = joints3d.device
+    p = joints3d.contiguous().float()
+    t = target.to(dev).contiguous().float()
+    B = p.shape[0]
+    c0 = torch.rand((B, 3), device=dev) if init is None else torch.as_tensor(init, dtype=torch.float32, device=dev).reshape(B, 3).contiguous()
+    sched = list(schedule)
+    ms = (ctypes.c_int32 * max(len(sched), 1))(*[int(m) for m, _ in sched])
+    lrs = (ctypes.c_double * max(len(sched), 1))(*[float(v) for _, v in sched])
+    cam = torch.empty((B, 3), device=dev, dtype=torch.float32)
+    loss = torch.empty((B,), device=dev, dtype=torch.float32)
+    bb = oc = None
+    w = h = 0.0
+    if bbox is not None:
+        bb = torch.as_tensor(bbox, dtype=torch.float32, device=dev).reshape(B, 4).contiguous()
+        oc = torch.empty((B, 4), device=dev, dtype=torch.float32)
+        w, h = float(image_size[0]), float(image_size[1])
+    _lib.check(_lib.load().gator_fit_camera_f32(p.data_ptr(), B, p.shape[1], t.data_ptr(), t.shape[1], int(n_fit), c0.data_ptr(), int(crop_size),
+                                                int(steps), ms, lrs, len(sched), bb.data_ptr() if bb is not None else None, w, h, cam.data_ptr(),
+                                                loss.data_ptr(), oc.data_ptr() if oc is not None else None, _stream(dev)),
+               'gator_fit_camera_f32')
+    return (cam, loss) if oc is None else (cam, loss, oc)
+
+
+def fit_mesh_to_image(model, raw_joints, joint_set, image_size, init=None, steps=1500, schedule=DEMO_SCHEDULE, crop_size=DEMO_CROP):
+    """The demo's flow (demo/run.py:193-211 with optimize_cam_param, :123-164) for a batch of detections.
+    model: a gator_amd GATOR with its joint regressor registered (set_joint_regressor: the COCO one for 'coco', the H36M one for 'human36');
+    raw_joints [B,17,2|3] pixels on the model's device; image_size = (width, height) of the images.
+    -> dict of mesh [B,6890,3], pose3d, joints (regressed, metres), cam [B,3], orig_cam [B,4], bbox [B,4], loss [B], valid [B]."""
+    from . import preprocess
+    if joint_set not in ('coco', 'human36'):
+        raise ValueError("fit_mesh_to_image: joint_set is 'coco' or 'human36', got %r" % (joint_set,))
+    coco = joint_set == 'coco'
+    x = raw_joints.contiguous().float()
+    pose2d = preprocess.normalise_pose2d(x, add_pelvis_neck=coco)
+    joints, pose3d, mesh = model.forward_joints(pose2d, with_verts=True)
+    target, bbox, valid = crop_joints(x, crop_size, add_pelvis_neck=coco)
+    cam, loss, orig_cam = fit_camera(joints, target, init=init, steps=steps, schedule=schedule, crop_size=crop_size,
+                                     n_fit=joints.shape[1], bbox=bbox, image_size=image_size)
+    return {'mesh': mesh, 'pose3d': pose3d, 'joints': joints, 'cam': cam, 'orig_cam': orig_cam, 'bbox': bbox, 'loss': loss, 'valid': valid}

@@ -228,6 +228,34 @@ int gator_preprocess_chain_f32(const float* joints, int32_t batch, int32_t num_j
  * the kernel under PA-MPJPE (data/PW3D/dataset.py:337-375). */
 int gator_rigid_align_f32(const float* a, const float* b, int32_t batch, int32_t n_points, float* aligned, void* stream);
 
+/* The demo's crop-space target (demo/run.py:124-127), batched, rot = 0 and no flip: get_bbox (lib/coord_utils.py:21-39),
+ * process_bbox(bbox, box_aspect, box_scale) (:42-66), j2d_processing(joints, (crop_w, crop_h), bbox1, 0, 0, None) (lib/aug_utils.py:51-64).
+ *   joints [batch, num_joint_in, comps] raw 2D joints in pixels; add_pelvis_neck as in gator_preprocess_pose2d_f32 (demo/run.py:103-121).
+ *   joints_crop [batch, num_joint_out, 2] in crop pixels (not standardised); bbox [batch, 4] = bbox1 as (x, y, w, h);
+ *   valid [batch] = 0 where process_bbox returns None, and joints_crop / bbox of that sample are 0.
+ * The demo uses box_aspect 1.0, box_scale 1.25, crop 500 x 500. */
+int gator_crop_joints_f32(const float* joints, int32_t batch, int32_t num_joint_in, int32_t comps, int32_t add_pelvis_neck,
+                          float box_aspect, float box_scale, int32_t crop_w, int32_t crop_h, float* joints_crop, float* bbox,
+                          int32_t* valid, void* stream);
+
+/* The demo's camera fit (demo/run.py:123-164 with lib/models/project_net.py:6-17), one sample per lane, in one launch:
+ * `steps` torch.optim.Adam steps (betas 0.9 / 0.999, eps 1e-8) of cam = (s, tx, ty) on nn.L1Loss between
+ * (joints3d_xy + t) * s * r + r  (r = crop_size / 2)  and target, over the first n_fit joints of both.
+ *   joints3d [batch, n_joint_in, 3] (metres, gator_forward_joints_f32's joints); target [batch, n_target_in, 2] (crop pixels,
+ *   gator_crop_joints_f32's joints_crop); init [batch, 3]; all device pointers.
+ *   Schedule (host arrays, 1..8 pairs): lrs[0] from the first step, then lrs[i] from 0-based step milestones[i] + 1 on, i.e. after the
+ *   optimizer step at j == milestones[i] (the demo: {0, 500, 1000} / {0.1, 0.05, 0.001}; milestones[0] is ignored).  The per-step
+ *   Adam factors are formed on the host in double, as torch does, and kept on the device for the process's life per schedule.
+ *   cam [batch, 3]; loss [batch] or NULL: the mean L1 error in crop pixels at the final cam.
+ *   bbox [batch, 4] (gator_crop_joints_f32's bbox) with orig_cam [batch, 4], or both NULL: orig_cam = (sx, sy, tx, ty) of
+ *   convert_crop_cam_to_orig_img (demo/run.py:21-39) for an image img_w pixels wide and img_h high.  The demo's call site passes
+ *   orig_img.shape[:2] (height, width) as (width, height) (demo/run.py:202,211,42-51); pass the true width and height here.
+ * steps = 0 returns init.  A non-finite input gives NaN outputs for its own sample only (no device status). */
+int gator_fit_camera_f32(const float* joints3d, int32_t batch, int32_t n_joint_in, const float* target, int32_t n_target_in,
+                         int32_t n_fit, const float* init, int32_t crop_size, int32_t steps, const int32_t* milestones,
+                         const double* lrs, int32_t n_schedule, const float* bbox, float img_w, float img_h, float* cam,
+                         float* loss, float* orig_cam, void* stream);
+
 /* Multi-GPU: samples are independent, the batch is sharded contiguously over one process per GPU, and the path's one
  * collective is the all-gather of the predicted vertices [B/N,6890,3] (+ pose3d [B/N,J,3]) over xGMI.  gator_amd/parallel.py issues
  * it through torch.distributed ("nccl" = RCCL); these entry points do the same on RCCL directly for hosts without torch:

@@ -4,6 +4,7 @@ mounted read-only at /root/reference) on CPU with import shims.  Dev-container o
 never travels to the GPU box; only the small data fixtures written here do.
 
 Usage:  python tools/gen_golden.py            (re-creates tests/golden/*.npz)
+        python tools/gen_golden.py camfit     (one section only: base, scale, train, rigid, preprocess, camfit)
 
 Shims: timm DropPath/Mlp stubs, easydict stub, a pre-seeded core.config.cfg (the real
 one mkdirs under the read-only tree at import), funcs_utils stub (imports cv2/matplotlib), a 3-point
@@ -426,6 +427,116 @@ def rigid_align_golden():
     print('rigid_align: 24 sets, PA error %.4f mm' % pa)
 
 
+def _import_demo_run():
+    """demo/run.py as a module, with stand-ins for what it imports but the camera step does not reach (renderer, vis, smpl, the
+    checkpoint and .obj helpers); lib/ is on the path already (install_shims)."""
+    import importlib.util
+    for name, attrs in (('__init_path', {}), ('renderer', {'Renderer': object}), ('vis', {'vis_2d_keypoints': None}),
+                        ('smpl', {'SMPL': object})):
+        m = types.ModuleType(name)
+        m.__dict__.update(attrs)
+        sys.modules[name] = m
+    sys.modules['funcs_utils'].save_obj = None
+    spec = importlib.util.spec_from_file_location('demo_run', os.path.join(REF, 'demo', 'run.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def camfit_golden():
+    """The demo's camera step run as it is (demo/run.py:123-164, lib/models/project_net.py, convert_crop_cam_to_orig_img :21-39):
+    the crop target through the real get_bbox / process_bbox(aspect 1.0, scale 1.25) / j2d_processing at 500 x 500, then one
+    OptimzeCamLayer per sample with cam_param overwritten by the recorded init, torch.optim.Adam and nn.L1Loss with the demo's
+    schedule on the CPU, in fp32 and fp64.  Sample 0 is demo/coco_joint_input.npy; 1-23 random COCO detections (pelvis and neck
+    appended, the fit on the first 17), 24-47 random H36M-17 ones.  joints3d projects near its target (s in [0.7, 1.2], |t| <= 0.1,
+    3 cm noise) except for four samples whose joints are shuffled (ill-conditioned fits) and two whose detections collapse to one
+    point (valid = 0, target 0).  Raw joints are float32 values (what the device reads)."""
+    scratch = tempfile.mkdtemp(prefix='gator_golden_')
+    install_shims(scratch, True)
+    for m in [k for k in sys.modules if k in ('coord_utils', 'aug_utils')]:
+        del sys.modules[m]
+    import aug_utils
+    import coord_utils
+    demo = _import_demo_run()
+    import models  # noqa: F401  (reference lib/models)
+    import models.project_net as ref_pn
+    N, crop, img_w, img_h = 48, 500, 1920, 1080
+    shuffled, collapsed = (5, 17, 30, 41), (20, 44)
+    rs = np.random.RandomState(2027)
+    raw = np.zeros((N, 17, 2), np.float32)
+    raw[0] = np.load(os.path.join(REF, 'demo', 'coco_joint_input.npy'))[:, :2]
+    for i in range(1, N):
+        c = rs.rand(2) * np.array([1200, 500]) + np.array([350, 280])
+        ext = np.array([rs.rand() * 250 + 60, rs.rand() * 450 + 120])
+        raw[i] = c + (rs.rand(17, 2) - 0.5) * ext
+        if i in collapsed:
+            raw[i] = raw[i, :1]
+    is_coco = (np.arange(N) < 24).astype(np.int32)
+    xy = np.zeros((N, 19, 2), np.float32)
+    bbox = np.zeros((N, 4), np.float32)
+    valid = np.ones(N, np.int32)
+    for i in range(N):
+        j = raw[i].astype(np.float64)
+        if is_coco[i]:
+            j = np.concatenate([j, (j[11:12] + j[12:13]) * 0.5, (j[5:6] + j[6:7]) * 0.5])    # demo/run.py:103-121 (pelvis, neck)
+        b1 = coord_utils.process_bbox(coord_utils.get_bbox(j).copy(), aspect_ratio=1.0, scale=1.25)
+        if b1 is None:
+            valid[i] = 0
+            continue
+        out, _ = aug_utils.j2d_processing(j.copy(), (crop, crop), b1, 0, 0, None)
+        xy[i, :len(j)] = out[:, :2]
+        bbox[i] = b1
+    target = xy[:, :17]
+    s_true = 0.7 + rs.rand(N) * 0.5
+    t_true = (rs.rand(N, 2) - 0.5) * 0.2
+    p = (target - crop / 2) / (s_true[:, None, None] * (crop / 2)) - t_true[:, None, :] + rs.randn(N, 17, 2) * 0.03
+    for i in shuffled:
+        p[i] = p[i, rs.permutation(17)]
+    joints3d = np.concatenate([p, rs.randn(N, 17, 1) * 0.1], 2).astype(np.float32)
+    torch.manual_seed(7)
+    init = torch.rand(N, 3).numpy()
+    snaps = (1, 10, 1500)
+    cams = {}
+    losses = {}
+    for dt, tag in ((torch.float32, 'f32'), (torch.float64, 'f64')):
+        cams[tag] = np.zeros((len(snaps), N, 3), np.float64)
+        losses[tag] = np.zeros(N, np.float64)
+        for i in range(N):
+            layer = ref_pn.get_model(crop_size=crop).to(dt)
+            with torch.no_grad():
+                layer.cam_param.copy_(torch.from_numpy(init[i:i + 1]).to(dt))
+            pred_3d_joint = torch.from_numpy(joints3d[i:i + 1]).to(dt)
+            target_joint = torch.from_numpy(xy[i:i + 1]).to(dt)
+            criterion = nn.L1Loss()
+            optimizer = torch.optim.Adam(layer.parameters(), lr=0.1)
+            layer.train()
+            for j in range(0, 1500):                    # demo/run.py:150-157
+                pred_2d_joint = layer(pred_3d_joint.detach())
+                loss = criterion(pred_2d_joint, target_joint[:, :17, :])
+                optimizer.zero_grad()
+                loss.backward()
+                optimizer.step()
+                if j == 500:
+                    for param_group in optimizer.param_groups:
+                        param_group['lr'] = 0.05
+                if j == 1000:
+                    for param_group in optimizer.param_groups:
+                        param_group['lr'] = 0.001
+                if j + 1 in snaps:
+                    cams[tag][snaps.index(j + 1), i] = layer.cam_param[0].detach().double().numpy()
+            with torch.no_grad():
+                losses[tag][i] = float(criterion(layer(pred_3d_joint), target_joint[:, :17, :]))
+    cam32 = cams['f32'][-1].astype(np.float32)
+    orig_cam = demo.convert_crop_cam_to_orig_img(cam=cam32, bbox=bbox, img_width=img_w, img_height=img_h).astype(np.float32)
+    np.savez_compressed(os.path.join(OUT, 'cam_fit.npz'), raw=raw, is_coco=is_coco, crop_size=np.int32(crop), xy=xy, bbox=bbox,
+                        valid=valid, joints3d=joints3d, init=init, snap_steps=np.array(snaps, np.int32), cam_f32=cams['f32'],
+                        cam_f64=cams['f64'], loss_f32=losses['f32'], loss_f64=losses['f64'], image_size=np.array([img_w, img_h], np.int32),
+                        orig_cam=orig_cam, shuffled=np.array(shuffled, np.int32))
+    d = np.abs(cams['f32'][-1] - cams['f64'][-1]).max(1)
+    print('camfit: %d samples (%d invalid), 1500-step |f32 - f64| max %.2e, median loss %.3f px'
+          % (N, int((valid == 0).sum()), d.max(), float(np.median(losses['f64']))))
+
+
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -446,3 +557,5 @@ if __name__ == '__main__':
         rigid_align_golden()
     if not only or 'preprocess' in only:
         preprocess_chain_golden()
+    if not only or 'camfit' in only:
+        camfit_golden()
