@@ -74,6 +74,92 @@ void fill_tile(float* dst, F tab) {
             for (int j = 0; j < 4; ++j) dst[(g * 64 + lane) * 4 + j] = tab(lane & 31, 8 * g + 4 * (lane >> 5) + j);
 }
 
+// Every environment switch of the fused path (fused_state.h: FusedOptions), read once per ctx, with the rules that depend only on
+// the switches and on gator_config.arithmetic.  Exact arithmetic (GATOR_ARITH_EXACT_SPLIT: no two-plane operand anywhere) wins over
+// the environment.
+int read_fused_options(const gator_ctx* c, FusedOptions* o) {
+    auto flag = [](const char* name, bool dflt) { const char* e = getenv(name); return e ? atoi(e) != 0 : dflt; };      // =0 means off
+    auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    auto set = [](const char* name) { return getenv(name) != nullptr; };
+    const bool exact = c->arithmetic == GATOR_ARITH_EXACT_SPLIT;
+    o->gat_x3 = flag("GATOR_GAT_X3", true);
+    o->gat8 = o->gat_x3 && flag("GATOR_GAT8", true);
+    o->gat8_h4 = !exact && flag("GATOR_GAT8_H4", true);
+    o->gat8_lobyte = o->gat8 && o->gat8_h4 && flag("GATOR_GAT8_LOBYTE", true);
+    o->gat_tiled_h4 = !exact && flag("GATOR_GAT_TILED_H4", true);
+    o->gat_tiled = num("GATOR_GAT_TILED", -1);
+    if (const int m = num("GATOR_GAT_TILED_MIN_BATCH", 0); m > 0) o->gat_tiled_min_batch = m;
+    o->mdr_x3 = exact ? 1 : num("GATOR_MDR_X3", 2);
+    o->up_x3 = exact ? 1 : num("GATOR_UPSAMPLE_X3", 2);
+    if (c->parts & GATOR_PART_MDR) {      // (a ctx without the MDR weights has no use for them)
+        if (o->up_x3 < 0 || o->up_x3 > 2) return fail(GATOR_EINVAL, "GATOR_UPSAMPLE_X3 must be 0, 1 or 2");
+        if (o->mdr_x3 < 0 || o->mdr_x3 > 2) return fail(GATOR_EINVAL, "GATOR_MDR_X3 must be 0, 1 or 2");
+    }
+    o->gat8_tail = o->gat8 && o->gat8_h4 && o->mdr_x3 == 2 && flag("GATOR_GAT8_TAIL", true);
+    o->mdr_persist = set("GATOR_MDR_PERSIST") ? flag("GATOR_MDR_PERSIST", false) : -1;
+    o->mdr_persist_chunk = num("GATOR_MDR_PERSIST_CHUNK", 0);
+    o->mdr_persist_grid = num("GATOR_MDR_PERSIST_GRID", 0);
+    o->mdr_head_partials = flag("GATOR_MDR_HEAD_PARTIALS", true);
+    // Config 3's default: the MDR layers on one fp16 activation plane (mdr_fused.hip XA = 3), the vertex regressor on its two fp16
+    // planes (a single bf16 / fp16 plane there costs 4 / 0.5 mm: profiles/r05_emulate_16bit.txt).  GATOR_C3_MDR=0 /
+    // GATOR_C3_UPSAMPLE_BF16=1 restore round 4's form (bf16 regressor only).
+    o->c3_mdr = o->mdr_x3 == 2 && flag("GATOR_C3_MDR", true);
+    o->c3_encoder = o->gat8 && o->gat8_h4 && o->gat_tiled_h4 && flag("GATOR_C3_ENCODER", true);
+    o->c3_up_w1 = flag("GATOR_C3_UPSAMPLE_W1", true);
+    o->c3_up_bf16 = o->up_x3 != 2 || flag("GATOR_C3_UPSAMPLE_BF16", false);
+    o->c3_guard = flag("GATOR_C3_GUARD", true);
+    o->graph = flag("GATOR_GRAPH", false);
+    o->subbatch_streams = num("GATOR_SUBBATCH_STREAMS", 0);
+#ifdef GATOR_DIAG
+    o->gat8_dbg = num("GATOR_GAT8_DBG", 0);
+    o->gat_stamps = set("GATOR_GAT_STAMPS");
+    o->mdr_cut = num("GATOR_MDR_CUT", 0);
+    o->mdr_stamps = set("GATOR_MDR_STAMPS");
+    o->mdr_solo = set("GATOR_MDR_SOLO");
+    o->mdr_ends = set("GATOR_MDR_ENDS");
+#endif
+    return GATOR_OK;
+}
+
+// Guard of config 3's 16-bit mode (round 6): its 431 x 431 attention carries q and k on ONE fp16 plane each, which moves a
+// score by up to 2^-11 |q| |k|.  |q| |k| is bounded from the weights alone: the custom LayerNorm in front of the in-projections gives
+// every token unit unbiased standard deviation, |x| <= max|a_2| sqrt(63) + |b_2| (vanilla_transformer_encoder.py:31-34), and per head
+// |q . k| <= sigma_max(Wq_h^T Wk_h) |x|^2 / sqrt(d_k) (biases aside).  Returns the largest bound over layers and heads, in the exp2
+// domain; gator_c3_state() reports it.
+float c3_logit_bound(const Weights& w) {
+    float worst = 0.f;
+    for (int li = 0; li < 3; ++li) {
+        const MdrLayerW& r = w.lay[li];
+        const std::vector<float> wq = d2h(r.sa_w[0], 64 * 64), wk = d2h(r.sa_w[1], 64 * 64), a2 = d2h(r.a2, 64), b2 = d2h(r.b2, 64);
+        double amax = 0, bn = 0;
+        for (int i = 0; i < 64; ++i) { amax = std::max(amax, (double)std::fabs(a2[i])); bn += (double)b2[i] * b2[i]; }
+        const double xn = amax * std::sqrt(63.0) + std::sqrt(bn);
+        for (int hd = 0; hd < 2; ++hd) {
+            // M = Wq_h^T Wk_h (64 x 64); sigma_max by power iteration on M^T M
+            std::vector<double> M(64 * 64, 0.0), v(64, 1.0), t(64), u(64);
+            for (int i = 0; i < 64; ++i)
+                for (int j = 0; j < 64; ++j) {
+                    double acc = 0;
+                    for (int c2 = 0; c2 < 32; ++c2) acc += (double)wq[(32 * hd + c2) * 64 + i] * (double)wk[(32 * hd + c2) * 64 + j];
+                    M[i * 64 + j] = acc;
+                }
+            double sig = 0;
+            for (int it = 0; it < 64; ++it) {
+                for (int i = 0; i < 64; ++i) { double acc = 0; for (int j = 0; j < 64; ++j) acc += M[i * 64 + j] * v[j]; t[i] = acc; }
+                for (int j = 0; j < 64; ++j) { double acc = 0; for (int i = 0; i < 64; ++i) acc += M[i * 64 + j] * t[i]; u[j] = acc; }
+                double n = 0;
+                for (int j = 0; j < 64; ++j) n += u[j] * u[j];
+                n = std::sqrt(n);
+                if (!(n > 0)) break;
+                sig = std::sqrt(n);                      // |M^T M v| -> sigma_max^2 for a unit v
+                for (int j = 0; j < 64; ++j) v[j] = u[j] / n;
+            }
+            worst = std::max(worst, (float)(sig * xn * xn / std::sqrt(32.0) * 1.4426950408889634));
+        }
+    }
+    return worst;
+}
+
 int fused_create_gat(gator_ctx* c, FusedState* f, void* stream) {
     const Weights& w = c->w;
     const int J = c->J;
@@ -130,39 +216,22 @@ int fused_create_gat(gator_ctx* c, FusedState* f, void* stream) {
         });
         q.f1b = upload(t2);
     }
-    {   // split-precision image of every block's weight grids (the tables mc/md/aoffT/f1b in between are converted too, unused)
-        const char* e = getenv("GATOR_GAT_X3");
-        f->gat_x3 = !(e && atoi(e) == 0);
-        const char* te = getenv("GATOR_GAT_TAIL");
-        f->gat_split_tail = !(te && atoi(te) == 0);
-        const char* t8 = getenv("GATOR_GAT8_TAIL");
-        f->gat8_tail = !(t8 && atoi(t8) == 0);
-        if (f->gat_x3) {
-            const int64_t ntiles = (p - f->gblk[0].qkv) / kTile;
-            GATOR_HIP_CHECK(hipMalloc(&f->gxbuf, (size_t)ntiles * kTileX3 * sizeof(float)));
-            int rc = fused_repack_x3(f->gblk[0].qkv, f->gxbuf, ntiles, stream);
+    if (f->opt.gat_x3) {   // split-precision image of every block's weight grids (the tables mc/md/aoffT/f1b in between are converted too, unused)
+        const int64_t ntiles = (p - f->gblk[0].qkv) / kTile;
+        GATOR_HIP_CHECK(hipMalloc(&f->gxbuf, (size_t)ntiles * kTileX3 * sizeof(float)));
+        int rc = fused_repack_x3(f->gblk[0].qkv, f->gxbuf, ntiles, stream);
+        if (rc) return rc;
+        if (f->opt.gat_tiled_h4) {
+            float left = 0.f;
+            GATOR_HIP_CHECK(hipMalloc(&f->gxbuf_h3, (size_t)ntiles * kTileX3 * sizeof(float)));
+            // the scale comes from the nine weight grids of each block (264 tiles), not from the mc / mdT / aoffT / f1b tables behind them
+            rc = fused_repack_h3(f->gblk[0].qkv, f->gxbuf_h3, ntiles, &f->gat_tiled_wshift, &left, stream, (int64_t)blk_tiles, 264);
+            if (rc == GATOR_OK && left > 1e-7f) rc = fail(GATOR_EUNSUPPORTED, "GAT weights span more than fp16 x 3 planes hold exactly: use GATOR_GAT_TILED_H4=0");
             if (rc) return rc;
-            const bool exact = c->arithmetic == GATOR_ARITH_EXACT_SPLIT;       // gator_config.arithmetic: no two-plane operand anywhere
-            const char* th = getenv("GATOR_GAT_TILED_H4");
-            f->gat_tiled_h4 = !exact && !(th && atoi(th) == 0);
-            if (f->gat_tiled_h4) {
-                float left = 0.f;
-                GATOR_HIP_CHECK(hipMalloc(&f->gxbuf_h3, (size_t)ntiles * kTileX3 * sizeof(float)));
-                // the scale comes from the nine weight grids of each block (264 tiles), not from the mc / mdT / aoffT / f1b tables behind them
-                rc = fused_repack_h3(f->gblk[0].qkv, f->gxbuf_h3, ntiles, &f->gat_tiled_wshift, &left, stream, (int64_t)blk_tiles, 264);
-                if (rc == GATOR_OK && left > 1e-7f) rc = fail(GATOR_EUNSUPPORTED, "GAT weights span more than fp16 x 3 planes hold exactly: use GATOR_GAT_TILED_H4=0");
-                if (rc) return rc;
-            }
-            const char* g8 = getenv("GATOR_GAT8");
-            f->gat8 = !(g8 && atoi(g8) == 0);
-            const char* g8h = getenv("GATOR_GAT8_H4");
-            f->gat8_h4 = !exact && !(g8h && atoi(g8h) == 0);
-            if (f->gat8) {
-                rc = gat8_build_stream(f, stream);
-                if (rc) return rc;
-            }
-        } else {
-            f->gat8 = false;
+        }
+        if (f->opt.gat8) {
+            rc = gat8_build_stream(f, stream);
+            if (rc) return rc;
         }
     }
     std::vector<float> bt(8 * kTile), mt(kTile);
@@ -205,13 +274,8 @@ int fused_create_gat(gator_ctx* c, FusedState* f, void* stream) {
         if (rc == GATOR_OK) rc = gat_tiled_prepare_device();
         if (rc == GATOR_OK) rc = gat8_prepare_device();
         if (rc) return rc;
-        const char* tl = getenv("GATOR_GAT_TILED");
-        f->gat_tiled = tl ? atoi(tl) : -1;
-        f->gat_tiled_env = f->gat_tiled;
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) f->n_cu = prop.multiProcessorCount;
-        const char* tm = getenv("GATOR_GAT_TILED_MIN_BATCH");
-        if (tm && atoi(tm) > 0) f->gat_tiled_min_batch = atoi(tm);
     }
     GATOR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     GATOR_HIP_CHECK(hipGetLastError());
@@ -224,83 +288,25 @@ int fused_create(gator_ctx* c, void* stream) {
     if (c->impl == GATOR_IMPL_BASIC) return GATOR_OK;
     FusedState* f = new FusedState();
     c->fused = f;
+    int rc = read_fused_options(c, &f->opt);
+    if (rc) return rc;
+    f->gat_tiled = f->opt.gat_tiled;
+    f->graph_replay = f->opt.graph;
     const Weights& w = c->w;
     if (c->parts & GATOR_PART_GAT) {
-        int rc = fused_create_gat(c, f, stream);
+        rc = fused_create_gat(c, f, stream);
         if (rc) return rc;
     }
     if (!(c->parts & GATOR_PART_MDR)) return GATOR_OK;
-    // vertex regressor: split-precision bf16 planes by default; GATOR_UPSAMPLE_X3=0 keeps the fp32-input MFMA kernel (A/B runs)
-    const char* x3env = getenv("GATOR_UPSAMPLE_X3");
-    const bool exact = c->arithmetic == GATOR_ARITH_EXACT_SPLIT;
-    const int up_mode = exact ? 1 : x3env ? atoi(x3env) : 2;
-    if (up_mode < 0 || up_mode > 2) return fail(GATOR_EINVAL, "GATOR_UPSAMPLE_X3 must be 0, 1 or 2");
-    f->x3 = up_mode != 0;
-    f->up_x2 = up_mode == 2;
-    const char* mx3 = getenv("GATOR_MDR_X3");
-    f->mdr_x3 = exact ? 1 : mx3 ? atoi(mx3) : 2;
-    if (f->mdr_x3 < 0 || f->mdr_x3 > 2) return fail(GATOR_EINVAL, "GATOR_MDR_X3 must be 0, 1 or 2");
-    // BASELINE config 3 (gator_forward_bf16): which stages run on ONE 16-bit operand plane.  Default: the MDR layers (one fp16 activation
-    // plane, mdr_fused.hip XA = 3), the vertex regressor stays on its two fp16 planes (a single bf16 / fp16 plane there costs 4 / 0.5 mm:
-    // profiles/r05_emulate_16bit.txt).  GATOR_C3_MDR=0 / GATOR_C3_UPSAMPLE_BF16=1 restore round 4's form (bf16 regressor only).
-    if (const char* e = getenv("GATOR_C3_MDR")) f->c3_mdr = atoi(e) != 0;
-    if (const char* e = getenv("GATOR_C3_UPSAMPLE_BF16")) f->c3_up_bf16 = atoi(e) != 0;
-    if (const char* e = getenv("GATOR_C3_ENCODER")) f->c3_encoder = atoi(e) != 0;
-    if (const char* e = getenv("GATOR_C3_UPSAMPLE_W1")) f->c3_up_w1 = atoi(e) != 0;
-    if (f->mdr_x3 != 2) f->c3_mdr = false;
-    if (f->c3_mdr) {
-        // Guard of the 16-bit mode (round 6): its 431 x 431 attention carries q and k on ONE fp16 plane each, which moves a score by up to
-        // 2^-11 |q| |k|.  |q| |k| is bounded from the weights alone: the custom LayerNorm in front of the in-projections gives every token unit unbiased
-        // standard deviation, |x| <= max|a_2| sqrt(63) + |b_2| (vanilla_transformer_encoder.py:31-34), and per head |q . k| <= sigma_max(Wq_h^T Wk_h) |x|^2
-        // / sqrt(d_k) (biases aside).  Above 2^10 in the exp2 domain - a worst-case shift of half a unit, 41 % of a probability - the MDR layers of
-        // gator_forward_bf16 keep the fp32 configuration's two planes for this ctx (measured: bound 470 -> 0.63 mm max, 3 340 -> 7.6 mm;
-        // tests/test_gpu_bf16.py).  GATOR_C3_GUARD=0 switches the guard off; gator_c3_state() reports bound and decision.
-        float worst = 0.f;
-        for (int li = 0; li < 3; ++li) {
-            const MdrLayerW& r = w.lay[li];
-            const std::vector<float> wq = d2h(r.sa_w[0], 64 * 64), wk = d2h(r.sa_w[1], 64 * 64), a2 = d2h(r.a2, 64), b2 = d2h(r.b2, 64);
-            double amax = 0, bn = 0;
-            for (int i = 0; i < 64; ++i) { amax = std::max(amax, (double)std::fabs(a2[i])); bn += (double)b2[i] * b2[i]; }
-            const double xn = amax * std::sqrt(63.0) + std::sqrt(bn);
-            for (int hd = 0; hd < 2; ++hd) {
-                // M = Wq_h^T Wk_h (64 x 64); sigma_max by power iteration on M^T M
-                std::vector<double> M(64 * 64, 0.0), v(64, 1.0), t(64), u(64);
-                for (int i = 0; i < 64; ++i)
-                    for (int j = 0; j < 64; ++j) {
-                        double acc = 0;
-                        for (int c2 = 0; c2 < 32; ++c2) acc += (double)wq[(32 * hd + c2) * 64 + i] * (double)wk[(32 * hd + c2) * 64 + j];
-                        M[i * 64 + j] = acc;
-                    }
-                double sig = 0;
-                for (int it = 0; it < 64; ++it) {
-                    for (int i = 0; i < 64; ++i) { double acc = 0; for (int j = 0; j < 64; ++j) acc += M[i * 64 + j] * v[j]; t[i] = acc; }
-                    for (int j = 0; j < 64; ++j) { double acc = 0; for (int i = 0; i < 64; ++i) acc += M[i * 64 + j] * t[i]; u[j] = acc; }
-                    double n = 0;
-                    for (int j = 0; j < 64; ++j) n += u[j] * u[j];
-                    n = std::sqrt(n);
-                    if (!(n > 0)) break;
-                    sig = std::sqrt(n);                      // |M^T M v| -> sigma_max^2 for a unit v
-                    for (int j = 0; j < 64; ++j) v[j] = u[j] / n;
-                }
-                worst = std::max(worst, (float)(sig * xn * xn / std::sqrt(32.0) * 1.4426950408889634));
-            }
-        }
-        f->c3_logit_bound = worst;
-        const char* ge = getenv("GATOR_C3_GUARD");
+    if (f->opt.c3_mdr) {
+        // Above 2^10 in the exp2 domain - a worst-case shift of half a unit, 41 % of a probability - the MDR layers of gator_forward_bf16
+        // keep the fp32 configuration's two planes for this ctx (measured: bound 470 -> 0.63 mm max, 3 340 -> 7.6 mm; tests/test_gpu_bf16.py).
         // (the encoder leaves the mode with them: under such weights the MDR layers amplify the 11-bit rounding of its activations too -
         // measured at bound 3 449: 5.1 mm max in the mode, 1.9 with the MDR layers on two planes, and the figure of the test with both out)
-        if (!(ge && atoi(ge) == 0) && !(worst <= 1024.0f)) { f->c3_mdr = false; f->c3_encoder = false; f->c3_guarded = true; }
+        f->c3_logit_bound = c3_logit_bound(w);
+        if (f->opt.c3_guard && !(f->c3_logit_bound <= 1024.0f)) f->opt.c3_mdr = f->opt.c3_encoder = false;
     }
-    if (!(f->x3 && f->up_x2)) f->c3_up_bf16 = true;
-    if (const char* e = getenv("GATOR_GRAPH")) f->graph_replay = atoi(e) != 0;      // hipGraph replay of repeated forwards (gator_set_graph_replay)
-    const char* mper = getenv("GATOR_MDR_PERSIST");
-    f->mdr_persist = mper ? (atoi(mper) != 0 ? 1 : 0) : -1;
-    const char* mpg = getenv("GATOR_MDR_PERSIST_GRID");
-    f->mdr_persist_grid = mpg ? atoi(mpg) : 0;
-    const char* mpc = getenv("GATOR_MDR_PERSIST_CHUNK");
-    f->mdr_persist_chunk = mpc ? atoi(mpc) : 0;
-    if (const char* e = getenv("GATOR_MDR_HEAD_PARTIALS")) f->mdr_head_partials = atoi(e) != 0;
-    const size_t n_up = f->x3 ? 0 : (size_t)3 * kOB * kCB * kTile, n_layer = (size_t)64 * kTile;
+    const size_t n_up = f->opt.up_x3 == 0 ? (size_t)3 * kOB * kCB * kTile : 0, n_layer = (size_t)64 * kTile;
     const size_t total = n_up + 3 * n_layer + 24 * kTile + 64 + (size_t)kVT * 2 * kTile + 3 * 64 + 1024;
     GATOR_HIP_CHECK(hipMalloc(&f->wbuf, total * sizeof(float)));
     f->wbuf_floats = total;
@@ -308,12 +314,12 @@ int fused_create(gator_ctx* c, void* stream) {
     auto take = [&](size_t k) { float* r = p; p += k; return r; };
     // upsample_conv.weight [6890][431][3] -> one packed [216][14] tile grid per tap
     float* up = take(n_up);
-    if (f->x3 && f->up_x2) {
+    if (f->opt.up_x3 == 2) {
         GATOR_HIP_CHECK(hipMalloc(&f->up_w2, upsample_x2_weight_elems() * 2));
         int rc = pack_upsample_x2(w.up_w, f->up_w2, &f->up_w2_unscale, stream);
         if (rc == GATOR_OK) rc = upsample_x2_prepare_device();
         if (rc) return rc;
-    } else if (f->x3) {
+    } else if (f->opt.up_x3 == 1) {
         GATOR_HIP_CHECK(hipMalloc(&f->up_w3, upsample_x3_weight_elems() * 2));
         int rc = pack_upsample_x3(w.up_w, f->up_w3, stream);
         if (rc) return rc;
@@ -361,10 +367,10 @@ int fused_create(gator_ctx* c, void* stream) {
         GATOR_HIP_CHECK(hipFree(tmp));
         if (rc) return rc;
         f->head_w = dst;
-        if (f->mdr_x3) {     // split-precision image of the three layers' tile grids and the head tiles (contiguous in wbuf)
+        if (f->opt.mdr_x3) {     // split-precision image of the three layers' tile grids and the head tiles (contiguous in wbuf)
             const int64_t ntiles = (dst + 2 * kTile - f->lay[0].wq) / kTile;
             GATOR_HIP_CHECK(hipMalloc(&f->wxbuf, (size_t)ntiles * kTileX3 * sizeof(float)));
-            if (f->mdr_x3 == 2) {     // three fp16 planes under one power-of-two scale (x3_common.h: the 4-product linears)
+            if (f->opt.mdr_x3 == 2) {     // three fp16 planes under one power-of-two scale (x3_common.h: the 4-product linears)
                 float left = 0.f;
                 rc = fused_repack_h3(f->lay[0].wq, f->wxbuf, ntiles, &f->mdr_wshift, &left, stream);
                 if (rc == GATOR_OK && left > 1e-7f) rc = fail(GATOR_EUNSUPPORTED, "MDR weights span more than fp16 x 3 planes hold exactly (residual %.2e of the largest weight): use GATOR_MDR_X3=1", left);
@@ -386,11 +392,11 @@ int fused_create(gator_ctx* c, void* stream) {
         rc = fused_pack_linear(w.jfeat_w + 5, 133, 1, 64, 128, d128, stream);
         if (rc) return rc;
         f->jfeat128_p = d128;
-        if (f->mdr_x3 == 2) {      // the same eight tiles as three fp16 planes under their own power-of-two scale (k_gat8's fused tail, gat_roles.hip)
+        if (f->opt.mdr_x3 == 2) {      // the same eight tiles as three fp16 planes under their own power-of-two scale (k_gat8's fused tail, gat_roles.hip)
             float left = 0.f;
             GATOR_HIP_CHECK(hipMalloc(&f->jf128_h3, (size_t)8 * kTileX3 * sizeof(float)));
             rc = fused_repack_h3(d128, f->jf128_h3, 8, &f->jf128_wshift, &left, stream);
-            if (rc == GATOR_OK && left > 1e-7f) { (void)hipFree(f->jf128_h3); f->jf128_h3 = nullptr; }      // (the two tail launches stay)
+            if (rc == GATOR_OK && left > 1e-7f) { (void)hipFree(f->jf128_h3); f->jf128_h3 = nullptr; f->opt.gat8_tail = false; }      // (the two tail launches stay)
             if (rc) return rc;
         }
         const std::vector<float> jw = d2h(w.jfeat_w, 64 * 133);
@@ -466,8 +472,8 @@ void fused_destroy(gator_ctx* c) {
 }
 
 int launch_upsample_any(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints, bool w1) {
-    if (!f->x3) return launch_upsample(f, c, B, verts, stream);
-    return f->up_x2 ? launch_upsample_x2(f, c, B, verts, stream, with_joints, w1) : launch_upsample_x3(f, c, B, verts, stream, with_joints);
+    if (f->opt.up_x3 == 0) return launch_upsample(f, c, B, verts, stream);
+    return f->opt.up_x3 == 2 ? launch_upsample_x2(f, c, B, verts, stream, with_joints, w1) : launch_upsample_x3(f, c, B, verts, stream, with_joints);
 }
 
 int fused_gat_forward(gator_ctx* c, const float* pose2d, int B, float* x_out, float* feat, void* stream) {
@@ -479,8 +485,8 @@ static int fused_upsample_in(gator_ctx* c, const float* vert431, int B, float* v
     int rc = fused_ensure_ws(c, B);
     if (rc) return rc;
     FusedState* f = c->fused;
-    rc = !f->x3 ? launch_pack_vc(vert431, B, f->vcp, stream)
-         : f->up_x2 ? launch_pack_vc_x2(vert431, B, f->vcp3, stream) : launch_pack_vc_x3(vert431, B, f->cap, f->vcp3, stream);
+    rc = f->opt.up_x3 == 0 ? launch_pack_vc(vert431, B, f->vcp, stream)
+         : f->opt.up_x3 == 2 ? launch_pack_vc_x2(vert431, B, f->vcp3, stream) : launch_pack_vc_x3(vert431, B, f->cap, f->vcp3, stream);
     if (rc) return rc;
     StageTimer tm(c, "upsample", stream);
     return launch_upsample_any(f, c, B, verts, stream);
@@ -526,9 +532,9 @@ static int fused_mdr_forward_impl(gator_ctx* c, const float* pc, int B, float* v
     int rc = fused_ensure_ws(c, B);
     if (rc) return rc;
     FusedState* f = c->fused;
-    rc = launch_mdr(c, f, pc, B, stream, nullptr, nullptr, bf16 && f->c3_mdr);        // also writes the packed vertex-GEMM operand f->vcp / f->vcp3
+    rc = launch_mdr(c, f, pc, B, stream, nullptr, nullptr, bf16 && f->opt.c3_mdr);        // also writes the packed vertex-GEMM operand f->vcp / f->vcp3
     if (rc) return rc;
-    if (bf16 && f->c3_up_bf16) return fused_upsample_bf16_in(c, f->vc, B, verts, stream);
+    if (bf16 && f->opt.c3_up_bf16) return fused_upsample_bf16_in(c, f->vc, B, verts, stream);
     StageTimer tm(c, "upsample", stream);
     return launch_upsample_any(f, c, B, verts, stream);
 }
@@ -557,7 +563,7 @@ static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* 
     if (rc) return rc;
     FusedState::GraphSlot* slot = nullptr;
     for (auto& g : f->graphs)
-        if (g.B == B && g.in == pose2d && g.verts == verts && g.pose3d == pose3d && g.bf16 == bf16 && g.tiled == f->gat_tiled && g.persist == f->mdr_persist && g.ws == f->ws) { slot = &g; break; }
+        if (g.B == B && g.in == pose2d && g.verts == verts && g.pose3d == pose3d && g.bf16 == bf16 && g.tiled == f->gat_tiled && g.persist == f->opt.mdr_persist && g.ws == f->ws) { slot = &g; break; }
     if (!slot) {                                         // first sight: remember the key, run directly
         if ((int)f->graphs.size() >= FusedState::kGraphSlots) {
             // evict a key that was never captured if there is one (no replay can be in flight: no device-wide wait), else the least recently used
@@ -568,7 +574,7 @@ static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* 
             f->graphs.erase(lru);
         }
         FusedState::GraphSlot g;
-        g.B = B; g.in = pose2d; g.verts = verts; g.pose3d = pose3d; g.bf16 = bf16; g.tiled = f->gat_tiled; g.persist = f->mdr_persist; g.ws = f->ws;
+        g.B = B; g.in = pose2d; g.verts = verts; g.pose3d = pose3d; g.bf16 = bf16; g.tiled = f->gat_tiled; g.persist = f->opt.mdr_persist; g.ws = f->ws;
         g.used = ++f->graph_clock;
         f->graphs.push_back(g);
         return fused_forward_one(c, pose2d, B, verts, pose3d, stream, bf16);
@@ -612,8 +618,7 @@ static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* 
 // filling the idle SIMDs in the tail of the other half's kernels.  Enabled by gator_config.flags / GATOR_SUBBATCH_STREAMS=2.
 int fused_forward(gator_ctx* c, const float* pose2d, int B, float* verts, float* pose3d, void* stream, bool bf16) {
     FusedState* f = c->fused;
-    static const int env_split = getenv("GATOR_SUBBATCH_STREAMS") ? atoi(getenv("GATOR_SUBBATCH_STREAMS")) : 0;
-    const int want = c->subbatch_streams > 0 ? c->subbatch_streams : env_split;
+    const int want = c->subbatch_streams > 0 ? c->subbatch_streams : f->opt.subbatch_streams;
     if (want < 2 || B < 128) {
         WsScope ws(f, 0);
         if (f->graph_replay && !c->profiling && !c->block_taps) {
@@ -653,10 +658,10 @@ int fused_forward(gator_ctx* c, const float* pose2d, int B, float* verts, float*
 int fused_tiled_samples(const gator_ctx* c, int B, bool unpinned) {
     const FusedState* f = c->fused;
     int n_tiled = 0;
-    const int policy = f ? (unpinned ? f->gat_tiled_env : f->gat_tiled) : 0;
-    if (f && f->gat_x3 && policy != 0) {
+    const int policy = f ? (unpinned ? f->opt.gat_tiled : f->gat_tiled) : 0;
+    if (f && f->opt.gat_x3 && policy != 0) {
         if (policy == 1) n_tiled = B;
-        else if (B >= f->gat_tiled_min_batch) {
+        else if (B >= f->opt.gat_tiled_min_batch) {
             const int round = f->n_cu * gat_tiled_samples_per_wg(c->J);
             n_tiled = (B / round) * round;
             // the remainder: k_gat8 takes ~0.18 ms per n_cu samples (four partial products), a partial round of the tiled kernel ~0.85 ms
@@ -677,33 +682,32 @@ static int fused_forward_one(gator_ctx* c, const float* pose2d, int B, float* ve
     // Within one kernel results are bit-identical whatever the batch; between the two they agree to fp32 rounding noise
     // (tests/test_gpu_tiled.py), so above the threshold a sample's last bits depend on the batch size and its position in it.
     // GATOR_GAT_TILED=0 keeps every batch on k_gat (bitwise batch invariance at any size), =1 forces the tiled kernel.
+    // The tail (lifter + MDR joint tokens): k_gat8 runs it for its own samples as its epilogue where the ctx has that form (round 6);
+    // the samples of the sample-tiled kernel, or all of them without it, get the two batched launches of gat_tail.hip.
     const int n_tiled = fused_tiled_samples(c, B);
-    const bool tiled = n_tiled > 0;
-    const bool enc16 = bf16 && f->c3_encoder && f->gat_x3 && f->gat8 && f->gat8_h4 && f->gat_tiled_h4 && f->g8stream != nullptr;
-    const bool fused_tail = n_tiled < B && f->gat8_tail && f->gat_split_tail && f->gat_x3 && gat8_tail_supported(c, f, enc16);
-    float* tail_jkv = nullptr;
+    const bool enc16 = bf16 && f->opt.c3_encoder;      // config 3: both encoders' one-plane forms
+    const bool fused_tail = n_tiled < B && gat8_tail_supported(f, enc16);
     {   // x_out [B,3J] IS pose3d [B,J,3]: the tail writes the caller's buffer and produces the MDR joint K/V
         StageTimer tm(c, "gat", stream);
         if (n_tiled > 0) rc = launch_gat_tiled(c, f, pose2d, n_tiled, f->feat, stream, B, enc16);
         if (rc == GATOR_OK && n_tiled < B) {
             const size_t o = (size_t)n_tiled * c->J;
-            // k_gat8 with the lifter + joint tokens of its samples as its epilogue (round 6); the sample-tiled part keeps the two launches
-            if (fused_tail) tail_jkv = f->jkv + (size_t)n_tiled * 12 * kTile;
+            float* tail_jkv = fused_tail ? f->jkv + (size_t)n_tiled * 12 * kTile : nullptr;
             rc = launch_gat(c, f, pose2d + o * 2, B - n_tiled, pose3d + o * 3, f->feat + o * kC, stream, true, B, n_tiled, enc16, tail_jkv);
         }
     }
     if (rc) return rc;
-    const int n_tail = fused_tail ? n_tiled : ((f->gat_split_tail || tiled) ? B : 0);
+    const int n_tail = fused_tail ? n_tiled : B;
     if (n_tail > 0) {   // lifter + MDR joint tokens as two batched launches (gat_tail.hip)
         StageTimer tm(c, "gat_tail", stream);
         rc = launch_gat_tail(c, f, pose2d, f->feat, n_tail, pose3d, stream, true, !fused_tail);
         if (rc) return rc;
     }
     c->set_tap(TAP_FEAT, f->feat, (int64_t)B * c->J * kC);
-    rc = launch_mdr(c, f, nullptr, B, stream, pose3d, pose2d, bf16 && f->c3_mdr);      // pose_combine is never materialised on this path
+    rc = launch_mdr(c, f, nullptr, B, stream, pose3d, pose2d, bf16 && f->opt.c3_mdr);      // pose_combine is never materialised on this path
     if (rc) return rc;
     if (joints) {      // vertex GEMM with the joint-regression epilogue (verts may be null: nothing of 82 kB/mesh is stored)
-        if (!f->x3 || bf16) return fail(GATOR_EUNSUPPORTED, "gator_forward_joints_f32 needs the split-precision vertex regressor");
+        if (f->opt.up_x3 == 0 || bf16) return fail(GATOR_EUNSUPPORTED, "gator_forward_joints_f32 needs the split-precision vertex regressor");
         if (B > f->jr_cap) {
             if (f->jr_P) { GATOR_HIP_CHECK(hipDeviceSynchronize()); GATOR_HIP_CHECK(hipFree(f->jr_P)); f->jr_P = nullptr; }
             GATOR_HIP_CHECK(hipMalloc(&f->jr_P, (size_t)B * f->jr_nnz * 3 * sizeof(float)));
@@ -714,9 +718,9 @@ static int fused_forward_one(gator_ctx* c, const float* pose2d, int B, float* ve
         StageTimer tm(c, "jreg_reduce", stream);
         return launch_jreg_reduce(f, B, joints, stream);
     }
-    if (bf16 && f->c3_up_bf16) return fused_upsample_bf16_in(c, f->vc, B, verts, stream);
+    if (bf16 && f->opt.c3_up_bf16) return fused_upsample_bf16_in(c, f->vc, B, verts, stream);
     StageTimer tm(c, "upsample", stream);
-    return launch_upsample_any(f, c, B, verts, stream, false, bf16 && f->c3_up_w1);
+    return launch_upsample_any(f, c, B, verts, stream, false, bf16 && f->opt.c3_up_w1);
 }
 
 // Register a sparse [nj, 6890] joint regressor (COO, host or device pointers are both read through hipMemcpy) for the fused epilogue
@@ -764,19 +768,19 @@ int fused_set_joint_regressor(gator_ctx* c, const int32_t* row, const int32_t* c
 }
 
 void fused_disable_persist(gator_ctx* c) {
-    if (c->fused) c->fused->mdr_persist = 0;
+    if (c->fused) c->fused->opt.mdr_persist = 0;
 }
 
 int fused_c3_state(const gator_ctx* c, float* bound) {
     const FusedState* f = c->fused;
     if (!f) return fail(GATOR_EUNSUPPORTED, "gator_c3_state: fused ctx only");
     if (bound) *bound = f->c3_logit_bound;
-    return f->c3_mdr ? 1 : 0;
+    return f->opt.c3_mdr ? 1 : 0;
 }
 
 int fused_set_encoder(gator_ctx* c, int mode) {
-    if (mode == 1 && !c->fused->gat_x3) return fail(GATOR_EUNSUPPORTED, "gator_set_encoder: the sample-tiled encoder needs the split-precision path (GATOR_GAT_X3)");
-    c->fused->gat_tiled = mode == GATOR_ENCODER_AUTO ? c->fused->gat_tiled_env : mode;      // AUTO = the ctx's own policy, incl. a GATOR_GAT_TILED pin of the environment
+    if (mode == 1 && !c->fused->opt.gat_x3) return fail(GATOR_EUNSUPPORTED, "gator_set_encoder: the sample-tiled encoder needs the split-precision path (GATOR_GAT_X3)");
+    c->fused->gat_tiled = mode == GATOR_ENCODER_AUTO ? c->fused->opt.gat_tiled : mode;      // AUTO = the ctx's own policy, incl. a GATOR_GAT_TILED pin of the environment
     return GATOR_OK;
 }
 

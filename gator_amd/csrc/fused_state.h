@@ -46,7 +46,52 @@ struct FusedWs {
     int vcp16_cap = 0;
 };
 
+// The fused path's environment switches: read once per ctx, at gator_create (fused_api.hip: read_fused_options), which also applies
+// the rules that combine them and gator_config.arithmetic.  What only the weights or the device can tell (the config-3 guard, the
+// byte-lo round trip, the residual checks of the fp16 x 3 weight images) narrows them later by clearing a flag.  Launchers read
+// FusedState::opt and nothing else.
+struct FusedOptions {
+    // encoder
+    bool gat_x3 = true;                 // GATOR_GAT_X3 (default 1): GAT linears on split-precision bf16 MFMA; =0: fp32-input MFMA (k_gat only)
+    bool gat8 = true;                   // GATOR_GAT8 (default 1): the one-sample-per-workgroup encoder is the two-role kernel k_gat8; =0: k_gat.  Needs gat_x3
+    bool gat8_h4 = true;                // GATOR_GAT8_H4 (default 1): k_gat8's token-wise products on four partial products (x3_common.h); =0: the exact six.  Off under exact arithmetic
+    bool gat8_lobyte = true;            // GATOR_GAT8_LOBYTE (default 1): k_gat8 streams the byte-lo image of its weights (H3B, gat_roles.hip); =0: the three fp16 planes.
+                                        // Needs gat8 and gat8_h4; cleared unless every lo value survives the byte round trip (always, for finite weights)
+    bool gat8_tail = true;              // GATOR_GAT8_TAIL (default 1): k_gat8 runs its samples' lifter and MDR joint tokens as its epilogue (round 6); =0: the two
+                                        // launches of gat_tail.hip.  Needs gat8, gat8_h4 and mdr_x3 = 2; cleared if jf128_h3 cannot hold the joint-feature weights;
+                                        // outside config 3 it also needs gat8_lobyte (gat8_tail_supported)
+    bool gat_tiled_h4 = true;           // GATOR_GAT_TILED_H4 (default 1): the sample-tiled encoder's token-wise products on four partial products; =0: the exact six.  Off under exact arithmetic
+    int gat_tiled = -1;                 // GATOR_GAT_TILED: -1 (default) by batch size (fused_tiled_samples), 0 never the sample-tiled encoder, 1 always; what GATOR_ENCODER_AUTO restores
+    int gat_tiled_min_batch = 1024;     // GATOR_GAT_TILED_MIN_BATCH (default 1024; values <= 0 ignored): smallest batch the by-batch-size policy gives the sample-tiled encoder
+    // MDR layers and vertex regressor
+    int mdr_x3 = 2;                     // GATOR_MDR_X3: 0 fp32-input MFMA; 1 exact bf16 x 3 split everywhere; 2 (default) that + the 431x431 attention on two fp16 planes.  1 under exact arithmetic
+    int up_x3 = 2;                      // GATOR_UPSAMPLE_X3: 0 the fp32-input MFMA vertex regressor; 1 the exact three bf16 planes; 2 (default) two scaled fp16 planes.  1 under exact arithmetic
+    int mdr_persist = -1;               // GATOR_MDR_PERSIST: the four MDR stages as persistent launches (k_mdr_persist): -1 (default) by batch size (launch_mdr), 0 never, 1 always.
+                                        // A persistent launch that did not complete sets it to 0 (fused_disable_persist)
+    int mdr_persist_chunk = 0;          // GATOR_MDR_PERSIST_CHUNK: most samples per persistent launch (0, default: floor(B / 256) launches, ceil(B / 384) in config 3)
+    int mdr_persist_grid = 0;           // GATOR_MDR_PERSIST_GRID: workgroups of the persistent launch (0, default: two per CU; tests: a grid that leaves XCDs without one)
+    bool mdr_head_partials = true;      // GATOR_MDR_HEAD_PARTIALS (default 1): the tiles' head-conv partial sums + k_mdr_head_finish; =0: the whole head in k_mdr_head (A/B)
+    // gator_forward_bf16 (BASELINE config 3): which stages run on ONE 16-bit operand plane
+    bool c3_mdr = true;                 // GATOR_C3_MDR (default 1): the MDR layers on one fp16 activation plane; =0: the fp32 configuration's form.  Needs mdr_x3 = 2; cleared by the guard
+    bool c3_encoder = true;             // GATOR_C3_ENCODER (default 1): the encoder's token-wise products on one fp16 activation plane as well; =0: the fp32 configuration's.
+                                        // Needs gat8 and both encoders' four-product forms; cleared by the guard
+    bool c3_up_w1 = true;               // GATOR_C3_UPSAMPLE_W1 (default 1): the vertex regressor's weights on ONE fp16 plane, coarse vertices on two; =0: weights on two
+    bool c3_up_bf16 = false;            // GATOR_C3_UPSAMPLE_BF16 (default 0): the vertex regressor on one bf16 plane instead of its two fp16 planes.  Set unless up_x3 = 2
+    bool c3_guard = true;               // GATOR_C3_GUARD (default 1): clear c3_mdr and c3_encoder if the weights bound the attention logits above 2^10 (fused_create); =0: never
+    // forward
+    bool graph = false;                 // GATOR_GRAPH (default 0): =1 starts the ctx with hipGraph replay of repeated forwards on (gator_set_graph_replay)
+    int subbatch_streams = 0;           // GATOR_SUBBATCH_STREAMS: 2 runs batches >= 128 as two half-batches on two streams, if gator_config.subbatch_streams is 0 (fused_forward)
+    // diagnostic library only (-DGATOR_DIAG; not read otherwise)
+    int gat8_dbg = 0;                   // GATOR_GAT8_DBG: k_gat8's debug mode (1: the helper waves reduced to their barriers)
+    bool gat_stamps = false;            // GATOR_GAT_STAMPS (set): k_gat / k_gat8 record and print in-kernel cycle stamps
+    int mdr_cut = 0;                    // GATOR_MDR_CUT: bit 0 makes every MDR weight load read its tile 0, bit 1 every K / V load (L2 -> CU traffic probe)
+    bool mdr_stamps = false;            // GATOR_MDR_STAMPS (set): k_mdr_layer<1> records and prints stamps (four launches only)
+    bool mdr_solo = false;              // GATOR_MDR_SOLO (set): the MDR layer launches hold one workgroup per CU (one wave per SIMD)
+    bool mdr_ends = false;              // GATOR_MDR_ENDS (set): the last persistent launch prints when its workgroups started and ended
+};
+
 struct FusedState : FusedWs {
+    FusedOptions opt;                   // the switches this ctx was created with, narrowed by the weights and the device
     float* wbuf = nullptr;              // all packed weights
     float* gbuf = nullptr;              // packed GAT weights + tables
     GatBlockPk gblk[kDepth];
@@ -55,40 +100,19 @@ struct FusedState : FusedWs {
     // upsample: Wp[tap][ob][cb][4][64][4]
     const float* up_w = nullptr;
     void* up_w3 = nullptr;              // bf16 [plane 3][tap][ob][28][64][8]  hi/mid/lo split of upsample_conv.weight
-    int gat_tiled = -1;                 // encoder policy in force: 0 never tiled, 1 always, -1: by batch size (fused_tiled_samples); gator_set_encoder changes it
-    int gat_tiled_env = -1;             // ... as gator_create found it (GATOR_GAT_TILED, default -1): what GATOR_ENCODER_AUTO means for this ctx
-    int gat_tiled_min_batch = 1024;
+    int gat_tiled = -1;                 // encoder policy in force (opt.gat_tiled until gator_set_encoder changes it)
     int n_cu = 256;                     // compute units of the ctx's device
-    bool gat_split_tail = true;         // full forward: lifter + joint tokens as batched launches (GATOR_GAT_TAIL=0: inside k_gat)
-    bool gat_x3 = true;                 // GAT linears on split-precision bf16 MFMA (GATOR_GAT_X3=0: fp32-input MFMA)
     float* gxbuf = nullptr;             // X3 tiles of the GAT block weights, tile-for-tile image of gbuf from gblk[0].qkv on
     float* gxbuf_h3 = nullptr;          // the same grids as three fp16 planes of 2^gat_tiled_wshift * w (k_gat_tiled's four-product form)
-    bool gat_tiled_h4 = true;           // GATOR_GAT_TILED_H4=0: the sample-tiled encoder on the exact six products
     int gat_tiled_wshift = 0;
     float* g8stream = nullptr;          // the same tiles as four per-wave streams in consumption order (gat_roles.hip)
-    bool gat8 = true;                   // one-sample-per-workgroup encoder: the two-role kernel k_gat8 (GATOR_GAT8=0: k_gat)
-    bool gat8_tail = true;              // k_gat8 runs the lifter and the MDR joint tokens as its epilogue (round 6; GATOR_GAT8_TAIL=0: the two launches of gat_tail.hip)
-    bool gat8_h4 = true;                // ... with its token-wise products on four partial products (x3_common.h; GATOR_GAT8_H4=0: the exact six)
     float* g8stream_b = nullptr;        // ... and its byte-lo image (H3B tiles, 5 KiB: gat_roles.hip), what k_gat8<true, LR, false, true> streams
-    bool gat8_lobyte = false;           // set when every weight's lo plane survives the byte round trip (always, for finite weights; GATOR_GAT8_LOBYTE=0: off)
     int gat8_wshift = 0;                // its weight stream holds three fp16 planes of 2^gat8_wshift * w
     float* wxbuf = nullptr;             // X3 tiles of the MDR layer + head weights, tile-for-tile image of wbuf from lay[0].wq on
-    int mdr_persist = -1;               // the four MDR stages as ONE persistent launch (k_mdr_persist): -1 by batch size (launch_mdr), GATOR_MDR_PERSIST=0 never, =1 always
-    int mdr_persist_chunk = 0;          // GATOR_MDR_PERSIST_CHUNK: most samples per persistent launch (0: 384)
-    bool mdr_head_partials = true;      // GATOR_MDR_HEAD_PARTIALS=0 (read at create): the whole head in k_mdr_head instead of the tiles' conv partial sums + k_mdr_head_finish (A/B)
-    int mdr_persist_grid = 0;           // GATOR_MDR_PERSIST_GRID: workgroups of the persistent launch (0: two per CU)
     float* jf128_h3 = nullptr;          // get_joint_feature columns 5..132 as H3 tiles [2][4] of 2^jf128_wshift * w (k_gat8's fused tail)
     int jf128_wshift = 0;
-    int mdr_wshift = 0;                 // GATOR_MDR_X3=2: wxbuf holds three fp16 planes of 2^mdr_wshift * w
-    int mdr_x3 = 2;                     // GATOR_MDR_X3: 0 fp32-input MFMA; 1 exact bf16 x 3 split everywhere; 2 (default) that + the 431x431 attention on two fp16 planes
+    int mdr_wshift = 0;                 // mdr_x3 = 2: wxbuf holds three fp16 planes of 2^mdr_wshift * w
     float c3_logit_bound = 0.f;         // bound on |q . k| / sqrt(d_k) of the MDR self-attention in the exp2 domain, from the weights (fused_create)
-    bool c3_guarded = false;            // ... exceeded 2^10: c3_mdr switched off for this ctx (GATOR_C3_GUARD=0: never)
-    bool c3_mdr = true;                 // gator_forward_bf16 (BASELINE config 3): the MDR layers on one fp16 activation plane (GATOR_C3_MDR=0: fp32 form)
-    bool c3_encoder = true;             // ... the encoder's token-wise products on one fp16 activation plane as well (GATOR_C3_ENCODER=0: the fp32 configuration's)
-    bool c3_up_w1 = true;               // ... the vertex regressor's weights on ONE fp16 plane, coarse vertices on two (GATOR_C3_UPSAMPLE_W1=0: weights on two)
-    bool c3_up_bf16 = false;            // ... and the vertex regressor on one bf16 plane (GATOR_C3_UPSAMPLE_BF16=1; default: its two fp16 planes)
-    bool x3 = true;                     // split-precision vertex regressor (GATOR_UPSAMPLE_X3=0: fp32-input MFMA kernel)
-    bool up_x2 = true;                  // ... on two fp16 planes (default; GATOR_UPSAMPLE_X3=1: the exact three bf16 planes)
     void* up_w2 = nullptr;              // fp16 [ob/2][28][2][tap 3][plane 2][64][8]  scaled hi/lo split of upsample_conv.weight
     float up_w2_unscale = 1.f;          // 2^-(weight shift + activation shift), applied to the finished sums
     void* up_w16 = nullptr;             // bf16 [tap][ob][28][64][8] (packed on the first bf16 call, which waits for the pack)
@@ -140,14 +164,16 @@ int launch_upsample(const FusedState* f, const gator_ctx* c, int B, float* verts
 // gat_fused.hip
 int gat_prepare_device();
 int gat_ensure_blk_tap(gator_ctx* c, FusedState* f, int B);
-int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x_out, float* feat, void* stream, bool joint_epilogue = false,
+// split_tail (the full forward): the lifter and the MDR joint tokens are left to gat_tail.hip's batched launches, or to k_gat8's
+// epilogue for its samples (tail_jkv); false (gator_gat_forward_f32): k_gat runs the lifter itself
+int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x_out, float* feat, void* stream, bool split_tail = false,
                int B_total = 0, int tap_row0 = 0, bool half16 = false, float* tail_jkv = nullptr);      // half16: the one-plane form of the two-role kernel (config 3); other forms ignore it
 // gat_roles.hip
 int gat8_prepare_device();
 int gat8_build_stream(FusedState* f, void* stream);
 int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* feat, void* stream, int B_total = 0, int tap_row0 = 0, bool half16 = false,
                 float* tail_x_out = nullptr, float* tail_jkv = nullptr, int ctr_B = 0);
-bool gat8_tail_supported(const gator_ctx* c, const FusedState* f, bool half16);
+bool gat8_tail_supported(const FusedState* f, bool half16);
 // gat_tiled.hip
 int gat_tiled_prepare_device();
 int gat_tiled_samples_per_wg(int J);

@@ -679,8 +679,9 @@ int gat_ensure_blk_tap(gator_ctx* c, FusedState* f, int B) {
     return GATOR_OK;
 }
 
-int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x_out, float* feat, void* stream, bool joint_epilogue,
+int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x_out, float* feat, void* stream, bool split_tail,
                int B_total, int tap_row0, bool half16, float* tail_jkv) {
+    const bool x3 = f->opt.gat_x3;
     GatArgs a;
     const Weights& w = c->w;
     a.B = B; a.J = c->J; a.pose2d = pose2d;
@@ -692,7 +693,7 @@ int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x
         const GatBlockPk& p = f->gblk[i];
         GatBlockP& q = a.blk[i];
         // X3 tile grids mirror the fp32 ones tile for tile (fused_create_gat): same tile index, 1.5x the tile size
-        auto sel = [&](const float* t) { return f->gat_x3 ? f->gxbuf + (size_t)(t - f->gblk[0].qkv) / kTile * kTileX3 : t; };
+        auto sel = [&](const float* t) { return x3 ? f->gxbuf + (size_t)(t - f->gblk[0].qkv) / kTile * kTileX3 : t; };
         q.qkv = sel(p.qkv); q.proj = sel(p.proj); q.w0 = sel(p.w0); q.w1 = sel(p.w1); q.lin0 = sel(p.lin0); q.lin1 = sel(p.lin1);
         q.back = sel(p.back); q.fc1 = sel(p.fc1); q.fc2 = sel(p.fc2);
         q.back32 = p.back;
@@ -702,17 +703,12 @@ int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x
     }
     a.x_out = x_out; a.feat = feat;
     a.pf_share = a.pf_n = a.pf_block = 0;
-    static const bool l2warm = [] { const char* e = getenv("GATOR_GAT_L2WARM"); return !(e && atoi(e) == 0); }();     // default on; =0 for A/B
-    if (f->gat_x3 && l2warm) {
+    if (x3) {      // each workgroup warms the L2 with its share of the next block's weight tiles
         a.pf_block = (int)((a.blk[1].qkv - a.blk[0].qkv) * sizeof(float));
         a.pf_n = std::min(32, (B + 7) / 8);
         a.pf_share = ((a.pf_block + a.pf_n - 1) / a.pf_n + 4095) / 4096 * 4096;
     }
-    a.jkv = nullptr;
-    if (joint_epilogue) {
-        a.jkv = f->jkv; a.jf5 = f->jfeat5; a.jf_p = f->jfeat128_p; a.jf_b = w.jfeat_b; a.posj_T = f->posj_T;
-        for (int i = 0; i < 3; ++i) { a.j_n1w[i] = w.lay[i].n1w; a.j_n1b[i] = w.lay[i].n1b; a.j_wk_p[i] = f->lay[i].wk; a.j_wv_p[i] = f->lay[i].wv; }
-    }
+    a.jkv = nullptr;      // (k_gat<*, true> runs the lifter only: the full forward's joint tokens come from k_gat8's epilogue or gat_tail.hip)
     a.blk_tap = nullptr;
     a.tapB = B;
     if (c->block_taps) {
@@ -724,17 +720,13 @@ int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x
     }
 #ifdef GATOR_DIAG
     a.stamps = nullptr;
-    static const bool want_stamps = getenv("GATOR_GAT_STAMPS") != nullptr;
     unsigned long long* d_st = nullptr;
-    if (want_stamps) {
+    if (f->opt.gat_stamps) {
         GATOR_HIP_CHECK(hipMalloc(&d_st, 20 * sizeof(unsigned long long)));
         a.stamps = d_st;
     }
 #endif
-    // (a launch that covers only part of a batch -- the remainder behind the sample-tiled kernel -- always leaves the tail to the
-    // batched launches, which then run once over the whole batch)
-    const bool split_tail = joint_epilogue && (f->gat_split_tail || (B_total > 0 && B_total != B));
-    if (split_tail && f->gat_x3 && f->gat8 && f->g8stream) {                             // the two-role form (gat_roles.hip)
+    if (split_tail && f->opt.gat8) {                                                      // the two-role form (gat_roles.hip)
 #ifdef GATOR_DIAG
         if (d_st) GATOR_HIP_CHECK(hipFree(d_st));                                         // (it prints its own stamps)
 #endif
@@ -742,10 +734,10 @@ int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x
         return launch_gat8(c, f, pose2d, B, feat, stream, B_total, tap_row0, half16, tail_jkv ? x_out : nullptr, tail_jkv, tail_jkv ? (B_total > 0 ? B_total : B) : 0);
     }
     if (split_tail) {
-        if (f->gat_x3) k_gat<true, false><<<B, 256, kGatLdsX3, (hipStream_t)stream>>>(a);
+        if (x3) k_gat<true, false><<<B, 256, kGatLdsX3, (hipStream_t)stream>>>(a);
         else k_gat<false, false><<<B, 256, kGatLds, (hipStream_t)stream>>>(a);
     } else {
-        if (f->gat_x3) k_gat<true, true><<<B, 256, kGatLdsX3, (hipStream_t)stream>>>(a);
+        if (x3) k_gat<true, true><<<B, 256, kGatLdsX3, (hipStream_t)stream>>>(a);
         else k_gat<false, true><<<B, 256, kGatLds, (hipStream_t)stream>>>(a);
     }
     GATOR_HIP_CHECK(hipGetLastError());

@@ -1473,7 +1473,7 @@ int gat8_prepare_device() {
 // The per-wave weight streams: the X3 tile grids of fused_create_gat (gxbuf, tile-for-tile image of gbuf from gblk[0].qkv on)
 // re-ordered into the order product wave w consumes them, block after block.
 int gat8_build_stream(FusedState* f, void* stream) {
-    if (!f->gat_x3 || !f->gxbuf) return GATOR_OK;
+    if (!f->opt.gat_x3 || !f->gxbuf) return GATOR_OK;
     std::vector<int> idx((size_t)4 * kWaveTiles + kNT, 0);
     auto tile_of = [&](const float* grid) { return (int)((grid - f->gblk[0].qkv) / kTile); };
     for (int w = 0; w < 4; ++w) {
@@ -1504,7 +1504,7 @@ int gat8_build_stream(FusedState* f, void* stream) {
     int* d_idx = (int*)t_idx.p;
     GATOR_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
     GATOR_HIP_CHECK(hipMalloc(&f->g8stream, (size_t)kStreamFloats * sizeof(float)));
-    if (f->gat8_h4) {      // the four-product form streams three fp16 planes of 2^shift * w: the fp32 tiles are put in stream order
+    if (f->opt.gat8_h4) {      // the four-product form streams three fp16 planes of 2^shift * w: the fp32 tiles are put in stream order
         float left = 0.f;  // first, so that the shift comes from exactly the weights the kernel multiplies (not the tables in between)
         GATOR_HIP_CHECK(hipMalloc(&t_h3.p, idx.size() * kTile * sizeof(float)));
         float* h3 = (float*)t_h3.p;
@@ -1512,8 +1512,7 @@ int gat8_build_stream(FusedState* f, void* stream) {
         int rc = fused_repack_h3(h3, f->g8stream, (int64_t)idx.size(), &f->gat8_wshift, &left, stream);
         if (rc == GATOR_OK && left > 1e-7f) rc = fail(GATOR_EUNSUPPORTED, "GAT weights span more than fp16 x 3 planes hold exactly: use GATOR_GAT8_H4=0");
         if (rc) return rc;
-        static const bool lobyte = [] { const char* e = getenv("GATOR_GAT8_LOBYTE"); return !(e && atoi(e) == 0); }();     // default on; =0 for A/B
-        if (lobyte) {      // the byte-lo image of the same stream (H3B): used only if every lo value survives the round trip
+        if (f->opt.gat8_lobyte) {      // the byte-lo image of the same stream (H3B): used only if every lo value survives the round trip
             DevFree t_bad;
             GATOR_HIP_CHECK(hipMalloc(&t_bad.p, sizeof(unsigned)));
             GATOR_HIP_CHECK(hipMemsetAsync(t_bad.p, 0, sizeof(unsigned), (hipStream_t)stream));
@@ -1523,8 +1522,7 @@ int gat8_build_stream(FusedState* f, void* stream) {
             unsigned nbad = 0;
             GATOR_HIP_CHECK(hipMemcpyAsync(&nbad, t_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
             GATOR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-            f->gat8_lobyte = nbad == 0;
-            if (!f->gat8_lobyte) { (void)hipFree(f->g8stream_b); f->g8stream_b = nullptr; }
+            if (nbad) { f->opt.gat8_lobyte = false; (void)hipFree(f->g8stream_b); f->g8stream_b = nullptr; }
         }
     } else {
         k_gather_tiles<kTileX3><<<(unsigned)idx.size(), 128, 0, (hipStream_t)stream>>>(f->gxbuf, d_idx, f->g8stream);
@@ -1537,15 +1535,15 @@ int gat8_build_stream(FusedState* f, void* stream) {
 // feat only (the lifter and the MDR joint tokens are the batched launches of gat_tail.hip)
 // tail_x_out != nullptr: the lifter (-> tail_x_out [B][3J]) and, with tail_jkv, the MDR joint tokens / K / V tiles run as the kernel's epilogue
 // (gat8_tail_supported); ctr_B > 0: the kernel also zeroes the persistent MDR launch's counters of a forward of ctr_B samples
-bool gat8_tail_supported(const gator_ctx* c, const FusedState* f, bool half16) {
-    if (!half16 && !f->gat8_lobyte) return false;        // (the three-plane stream's kernel has no registers left for the epilogue: GATOR_GAT8_LOBYTE=0 keeps the two launches)
-    return f->gat8 && f->gat8_h4 && f->g8stream != nullptr && f->mdr_x3 == 2 && f->wxbuf != nullptr && f->jf128_h3 != nullptr && (c->J == 17 || c->J == 19);
+bool gat8_tail_supported(const FusedState* f, bool half16) {
+    // (the three-plane stream's kernel has no registers left for the epilogue: outside config 3, GATOR_GAT8_LOBYTE=0 keeps the two launches)
+    return f->opt.gat8_tail && (half16 || f->opt.gat8_lobyte);
 }
 
 int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* feat, void* stream, int B_total, int tap_row0, bool half16,
                 float* tail_x_out, float* tail_jkv, int ctr_B) {
-    if (tail_x_out && !gat8_tail_supported(c, f, half16)) return fail(GATOR_EUNSUPPORTED, "k_gat8: the fused tail needs the four-product forms and 17 or 19 joints");
-    if (half16 && !f->gat8_h4) return fail(GATOR_EUNSUPPORTED, "the 16-bit encoder needs the four-product weight stream (GATOR_GAT8_H4=1, the default)");
+    if (tail_x_out && !gat8_tail_supported(f, half16)) return fail(GATOR_EUNSUPPORTED, "k_gat8: the fused tail needs the four-product forms and 17 or 19 joints");
+    if (half16 && !f->opt.gat8_h4) return fail(GATOR_EUNSUPPORTED, "the 16-bit encoder needs the four-product weight stream (GATOR_GAT8_H4=1, the default)");
     Gat8Args a;
     const Weights& w = c->w;
     a.B = B; a.J = c->J; a.pose2d = pose2d;
@@ -1563,7 +1561,7 @@ int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* 
     if (tail) {
         Gat8Tail& tl = a.tl;
         tl.lifter_w = w.lifter_w; tl.lifter_b = w.lifter_b; tl.x_out = tail_x_out; tl.jkv = tail_jkv;
-        if (ctr_B > 0 && f->mdr_persist != 0) { tl.mdr_ctr = f->mdr_ctr; tl.ctr_B = ctr_B; f->mdr_ctr_clean = true; }
+        if (ctr_B > 0 && f->opt.mdr_persist != 0) { tl.mdr_ctr = f->mdr_ctr; tl.ctr_B = ctr_B; f->mdr_ctr_clean = true; }
         tl.jf_p = f->jfeat128_p;
         for (int i = 0; i < 3; ++i) { tl.j_wk_p[i] = f->lay[i].wk; tl.j_wv_p[i] = f->lay[i].wv; }
         tl.jf5 = f->jfeat5; tl.jf_h3 = f->jf128_h3; tl.jf_b = w.jfeat_b; tl.posj_T = f->posj_T;
@@ -1581,17 +1579,17 @@ int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* 
         a.blk_tap = f->blk_tap + (size_t)tap_row0 * c->J * kC;
         a.tapB = Bt;
     }
-    static const bool l2warm = [] { const char* e = getenv("GATOR_GAT_L2WARM"); return !(e && atoi(e) == 0); }();     // default on; =0 for A/B
+    // L2 warm-up: each workgroup touches its share of the next block's weight stream
     a.pf_n = std::min(32, (B + 7) / 8);                  // workgroups b and b + 8 share an XCD (round-robin dispatch; speed only)
-    const bool lob = f->gat8_h4 && f->gat8_lobyte && !half16;                         // the byte-lo stream (the one-plane form reads hi and mid of the H3 stream)
+    const bool lob = f->opt.gat8_lobyte && !half16;                                   // the byte-lo stream (the one-plane form reads hi and mid of the H3 stream)
     if (lob) a.wstream = f->g8stream_b;
-    a.pf_loads = l2warm ? (kBlkTiles * (lob ? kTileH3B : kTileX3) * 4 / a.pf_n + 8191) / 8192 : 0;       // 8 KiB (64 lines) per instruction
+    a.pf_loads = (kBlkTiles * (lob ? kTileH3B : kTileX3) * 4 / a.pf_n + 8191) / 8192;       // 8 KiB (64 lines) per instruction
     if (a.pf_loads > 6) a.pf_loads = 0;      // fewer than ~8 workgroups per XCD (B < 64): a share is so large that touching it costs more than it hides
-    a.tl.warm_n = (tail && l2warm && a.pf_n >= 8) ? a.pf_n : 0;      // (fewer than 8 workgroups per XCD: a share is too large to be worth touching)
+    a.tl.warm_n = (tail && a.pf_n >= 8) ? a.pf_n : 0;      // (fewer than 8 workgroups per XCD: a share is too large to be worth touching)
 #ifdef GATOR_DIAG
     a.stamps = nullptr;
-    a.dbg = getenv("GATOR_GAT8_DBG") ? atoi(getenv("GATOR_GAT8_DBG")) : 0;
-    static const bool want_stamps = getenv("GATOR_GAT_STAMPS") != nullptr;
+    a.dbg = f->opt.gat8_dbg;
+    const bool want_stamps = f->opt.gat_stamps;
     constexpr int kSt = 2 * kDepth * 23 * 2 + kDepth * 8;
     if (want_stamps) {
         GATOR_HIP_CHECK(hipMalloc(&a.stamps, kSt * sizeof(unsigned long long)));
@@ -1612,7 +1610,7 @@ int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* 
     else if (tail && lob && c->J == 17) k_gat8<true, 10, false, true, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
     else if (tail && lob) k_gat8<true, 12, false, true, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
     else if (tail) return fail(GATOR_EUNSUPPORTED, "k_gat8: no fused tail on the three-plane weight stream");
-    else if (!f->gat8_h4) k_gat8<false, 16><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
+    else if (!f->opt.gat8_h4) k_gat8<false, 16><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
     else if (half16 && c->J <= 18) k_gat8<true, 10, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
     else if (half16 && c->J <= 20) k_gat8<true, 12, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
     else if (lob && c->J <= 18) k_gat8<true, 10, false, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);

@@ -598,8 +598,8 @@ int gat_tiled_prepare_device() {
 
 // pose2d [B,J,2] -> feat [B,J,128]; requires the split-precision weight images (FusedState::gxbuf)
 int launch_gat_tiled(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* feat, void* stream, int B_total, bool half16) {
-    if (half16 && !f->gat_tiled_h4) return fail(GATOR_EUNSUPPORTED, "the 16-bit encoder needs the four-product weight image (GATOR_GAT_TILED_H4=1, the default)");
-    if (!f->gat_x3) return fail(GATOR_EUNSUPPORTED, "the sample-tiled GAT kernel needs the split-precision weights (GATOR_GAT_X3=1)");
+    if (half16 && !f->opt.gat_tiled_h4) return fail(GATOR_EUNSUPPORTED, "the 16-bit encoder needs the four-product weight image (GATOR_GAT_TILED_H4=1, the default)");
+    if (!f->opt.gat_x3) return fail(GATOR_EUNSUPPORTED, "the sample-tiled GAT kernel needs the split-precision weights (GATOR_GAT_X3=1)");
     const Weights& w = c->w;
     TiledArgs a;
     a.B = B; a.Btap = B_total > 0 ? B_total : B; a.S = gat_tiled_samples_per_wg(c->J); a.pose2d = pose2d;
@@ -609,7 +609,7 @@ int launch_gat_tiled(gator_ctx* c, FusedState* f, const float* pose2d, int B, fl
     for (int i = 0; i < kDepth; ++i) {
         const GatBlockPk& p = f->gblk[i];
         TiledBlk& q = a.blk[i];
-        const float* image = f->gat_tiled_h4 ? f->gxbuf_h3 : f->gxbuf;
+        const float* image = f->opt.gat_tiled_h4 ? f->gxbuf_h3 : f->gxbuf;
         auto sel = [&](const float* t) { return image + (size_t)(t - f->gblk[0].qkv) / kTile * kTileX3; };
         q.qkv = sel(p.qkv); q.proj = sel(p.proj); q.w0 = sel(p.w0); q.w1 = sel(p.w1); q.lin0 = sel(p.lin0); q.lin1 = sel(p.lin1);
         q.back = sel(p.back); q.fc1 = sel(p.fc1); q.fc2 = sel(p.fc2);
@@ -626,12 +626,12 @@ int launch_gat_tiled(gator_ctx* c, FusedState* f, const float* pose2d, int B, fl
     }
     const int nwg = (B + a.S - 1) / a.S;
     const size_t ldsb = kTiledLdsFloats * sizeof(float);
-    a.lin_s = f->gat_tiled_h4 ? std::ldexp(16.0f, f->gat_tiled_wshift) : 1.0f;
+    a.lin_s = f->opt.gat_tiled_h4 ? std::ldexp(16.0f, f->gat_tiled_wshift) : 1.0f;
     a.lin_inv = 1.0f / a.lin_s;
     if (half16) {
         if (c->J == 17) k_gat_tiled<17, true, true><<<nwg, 256, ldsb, (hipStream_t)stream>>>(a);
         else k_gat_tiled<19, true, true><<<nwg, 256, ldsb, (hipStream_t)stream>>>(a);
-    } else if (f->gat_tiled_h4) {
+    } else if (f->opt.gat_tiled_h4) {
         if (c->J == 17) k_gat_tiled<17, true><<<nwg, 256, ldsb, (hipStream_t)stream>>>(a);
         else k_gat_tiled<19, true><<<nwg, 256, ldsb, (hipStream_t)stream>>>(a);
     } else {

@@ -1819,7 +1819,7 @@ LayerW make_layer(const FusedState* f, const gator_ctx* c, int li) {
     const MdrLayerW& r = c->w.lay[li];
     LayerW w;
     // X3 images mirror the fp32 tile grids tile for tile (fused_create)
-    auto sel = [&](const float* t) { return f->mdr_x3 ? f->wxbuf + (size_t)(t - f->lay[0].wq) / kTile * kTileX3 : t; };
+    auto sel = [&](const float* t) { return f->opt.mdr_x3 ? f->wxbuf + (size_t)(t - f->lay[0].wq) / kTile * kTileX3 : t; };
     w.wq = sel(p.wq); w.proj = sel(p.proj); w.fc1 = sel(p.fc1); w.fc2 = sel(p.fc2);
     w.sa0 = sel(p.sa[0]); w.sa1 = sel(p.sa[1]); w.sa2 = sel(p.sa[2]); w.sa3 = sel(p.sa[3]);
     w.n1w = r.n1w; w.n1b = r.n1b; w.proj_b = r.proj_b; w.n2w = r.n2w; w.n2b = r.n2b; w.fc1_b = r.fc1_b; w.fc2_b = r.fc2_b;
@@ -1833,41 +1833,40 @@ LayerW make_layer(const FusedState* f, const gator_ctx* c, int li) {
 int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream, const float* x_out, const float* pose2d, bool half16) {
     (void)pose2d;
     // half16 (BASELINE config 3): the layers on ONE fp16 activation plane (XA = 3); needs the default weight / joint-tile forms (GATOR_MDR_X3=2)
-    if (half16 && f->mdr_x3 != 2) return fail(GATOR_EUNSUPPORTED, "16-bit MDR layers need GATOR_MDR_X3=2 (the default)");
-    const int xa = half16 ? 3 : f->mdr_x3;
+    if (half16 && f->opt.mdr_x3 != 2) return fail(GATOR_EUNSUPPORTED, "16-bit MDR layers need GATOR_MDR_X3=2 (the default)");
+    const int xa = half16 ? 3 : f->opt.mdr_x3;
     hipStream_t st = (hipStream_t)stream;
     const Weights& w = c->w;
     JointArgs ja;
     ja.pc = pc; ja.jw_p = f->jfeat_p; ja.jb = w.jfeat_b; ja.posj_T = f->posj_T; ja.jkv = f->jkv; ja.J = c->J;
     for (int i = 0; i < 3; ++i) { ja.n1w[i] = w.lay[i].n1w; ja.n1b[i] = w.lay[i].n1b; ja.wk_p[i] = f->lay[i].wk; ja.wv_p[i] = f->lay[i].wv; }
     ja.mdr_ctr = nullptr;
-    ja.x2 = f->mdr_x3 == 2;
+    ja.x2 = f->opt.mdr_x3 == 2;
     if (pc) {
-        if (f->mdr_persist != 0) { ja.mdr_ctr = f->mdr_ctr; f->mdr_ctr_clean = true; }
+        if (f->opt.mdr_persist != 0) { ja.mdr_ctr = f->mdr_ctr; f->mdr_ctr_clean = true; }
         StageTimer tm(c, "mdr_joint", stream);
         k_mdr_joint<<<B, 128, 0, st>>>(ja);
     }    // else: done by k_gat's epilogue / k_gat_joint
     const size_t per = (size_t)f->cap * kVT * 2 * kTile;      // one [B][14][2] tile set
-    const size_t perq = (size_t)f->cap * kVT * 2 * (f->mdr_x3 == 1 ? kTileX3 : kTile);      // q/k/v tile sets: X3 tiles are 1.5x, fp32 and X2 tiles 4 KiB (X1 tiles 2 KiB: half of a set is used)
+    const size_t perq = (size_t)f->cap * kVT * 2 * (f->opt.mdr_x3 == 1 ? kTileX3 : kTile);      // q/k/v tile sets: X3 tiles are 1.5x, fp32 and X2 tiles 4 KiB (X1 tiles 2 KiB: half of a set is used)
     float* set[3][4] = {{f->vf, f->q, f->k, f->v}, {f->vf + per, f->q + perq, f->k + perq, f->v + perq},
                         {f->vf + 2 * per, f->q + 2 * perq, f->k + 2 * perq, f->v + 2 * perq}};
     MdrArgs a{};
     a.B = B; a.J = c->J; a.jkv = f->jkv; a.pc = pc; a.xout = pc ? nullptr : x_out; a.vj = w.vj; a.tok_base = f->tok_base; a.tok_w3 = f->tok_w3;
-    a.head_w = f->mdr_x3 ? f->wxbuf + (size_t)(f->head_w - f->lay[0].wq) / kTile * kTileX3 : f->head_w; a.head_b = f->head_b; a.hf = f->hf; a.lbf = c->block_taps ? f->lbf : nullptr;      // the "mdr_lbf2" tap costs 110 KB of stores per sample: recorded with the block taps only
-    a.hpart = f->mdr_head_partials ? reinterpret_cast<double*>(f->hpart) : nullptr;      // default on; GATOR_MDR_HEAD_PARTIALS=0 at create: the whole head in k_mdr_head (A/B)
+    a.head_w = f->opt.mdr_x3 ? f->wxbuf + (size_t)(f->head_w - f->lay[0].wq) / kTile * kTileX3 : f->head_w; a.head_b = f->head_b; a.hf = f->hf; a.lbf = c->block_taps ? f->lbf : nullptr;      // the "mdr_lbf2" tap costs 110 KB of stores per sample: recorded with the block taps only
+    a.hpart = f->opt.mdr_head_partials ? reinterpret_cast<double*>(f->hpart) : nullptr;      // default on; GATOR_MDR_HEAD_PARTIALS=0 at create: the whole head in k_mdr_head (A/B)
     a.bconv_w = w.bconv_w; a.hbn_w = w.bn_w; a.hbn_b = w.bn_b; a.hbn_mean = w.bn_mean; a.hbn_var = w.bn_var; a.halpha = c->alpha;
-    a.lin_s = f->mdr_x3 == 2 ? std::ldexp(kActScale, f->mdr_wshift) : 1.0f;      // 4-product linears: 16 x activations, 2^wshift x weights
+    a.lin_s = f->opt.mdr_x3 == 2 ? std::ldexp(kActScale, f->mdr_wshift) : 1.0f;      // 4-product linears: 16 x activations, 2^wshift x weights
     a.lin_inv = 1.0f / a.lin_s;
     const int nwg = (B * kVT + 3) / 4;
 #ifdef GATOR_DIAG
     {
-        static const int cut = getenv("GATOR_MDR_CUT") ? atoi(getenv("GATOR_MDR_CUT")) : 0;
-        static const int wm = (cut & 1) ? 0 : -1, kvm = (cut & 2) ? 0 : -1;
-        GATOR_HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mdr_wmask), &wm, sizeof(int), 0, hipMemcpyHostToDevice, st));
-        GATOR_HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mdr_kvmask), &kvm, sizeof(int), 0, hipMemcpyHostToDevice, st));
+        static const int keep = -1, cut = 0;      // (sources of the asynchronous copies: they outlive the call)
+        GATOR_HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mdr_wmask), (f->opt.mdr_cut & 1) ? &cut : &keep, sizeof(int), 0, hipMemcpyHostToDevice, st));
+        GATOR_HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mdr_kvmask), (f->opt.mdr_cut & 2) ? &cut : &keep, sizeof(int), 0, hipMemcpyHostToDevice, st));
     }
-    static const bool want_stamps = getenv("GATOR_MDR_STAMPS") != nullptr;
-    static const size_t solo = getenv("GATOR_MDR_SOLO") ? 60 * 1024 : 0;      // 1 workgroup per CU (1 wave/SIMD)
+    const bool want_stamps = f->opt.mdr_stamps;
+    const size_t solo = f->opt.mdr_solo ? 60 * 1024 : 0;      // 1 workgroup per CU (1 wave/SIMD)
     unsigned long long* d_st = nullptr;
     if (want_stamps) { GATOR_HIP_CHECK(hipMalloc(&d_st, 512 * sizeof(unsigned long long))); GATOR_HIP_CHECK(hipMemset(d_st, 0, 512 * sizeof(unsigned long long))); }
 #else
@@ -1883,11 +1882,11 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
     f->mdr_ctr_clean = false;
     const double R = (double)nwg / f->n_cu;
     const bool auto_persist = R >= 3.0;      // (round 3 also asked for a wasted fractional generation >= 4 %; with chunked launches the persistent form wins from R = 3 on: sweep in DESIGN.md)
-    bool persist = f->mdr_persist < 0 ? auto_persist : f->mdr_persist > 0;
+    bool persist = f->opt.mdr_persist < 0 ? auto_persist : f->opt.mdr_persist > 0;
     // the queues are per XCD and a workgroup serves the queue of the XCD it runs on: that drains every queue only when the device is
     // the whole 8-XCD part (a partitioned device shows fewer CUs; its workgroups would all sit on one XCD).  A placement that leaves
     // an XCD empty anyway is caught by k_mdr_head (completion counts) and answered by api.hip (four launches from then on).
-    if (f->n_cu != 256 && f->mdr_persist < 0) persist = false;
+    if (f->n_cu != 256 && f->opt.mdr_persist < 0) persist = false;
 #ifdef GATOR_DIAG
     if (want_stamps) persist = false;       // the stamps describe the per-stage launches
 #endif
@@ -1911,11 +1910,11 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
             if (li == 0) k_mdr_layer<0, 3><<<nwg, 256, solo, st>>>(a, nwg);
             else if (li < 3) k_mdr_layer<1, 3><<<nwg, 256, solo, st>>>(a, nwg);
             else k_mdr_layer<2, 3><<<nwg, 256, 0, st>>>(a, nwg);
-        } else if (f->mdr_x3 == 2) {
+        } else if (f->opt.mdr_x3 == 2) {
             if (li == 0) k_mdr_layer<0, 2><<<nwg, 256, solo, st>>>(a, nwg);
             else if (li < 3) k_mdr_layer<1, 2><<<nwg, 256, solo, st>>>(a, nwg);
             else k_mdr_layer<2, 2><<<nwg, 256, 0, st>>>(a, nwg);
-        } else if (f->mdr_x3 == 1) {
+        } else if (f->opt.mdr_x3 == 1) {
             if (li == 0) k_mdr_layer<0, 1><<<nwg, 256, solo, st>>>(a, nwg);
             else if (li < 3) k_mdr_layer<1, 1><<<nwg, 256, solo, st>>>(a, nwg);
             else k_mdr_layer<2, 1><<<nwg, 256, 0, st>>>(a, nwg);
@@ -1926,9 +1925,8 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
         }
     }
 #ifdef GATOR_DIAG
-    static const bool want_ends = getenv("GATOR_MDR_ENDS") != nullptr;
     unsigned long long* d_ends = nullptr;
-    if (want_ends && persist) {
+    if (f->opt.mdr_ends && persist) {
         GATOR_HIP_CHECK(hipMalloc(&d_ends, 3 * 1024 * sizeof(unsigned long long)));
         GATOR_HIP_CHECK(hipMemset(d_ends, 0, 3 * 1024 * sizeof(unsigned long long)));
         GATOR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_persist_ends), &d_ends, sizeof(d_ends)));
@@ -1938,7 +1936,7 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
         if (!ctr_clean) GATOR_HIP_CHECK(hipMemsetAsync(f->mdr_ctr, 0, mdr_ctr_words(B) * sizeof(unsigned), st));
         StageTimer tm(c, "mdr_layers", stream);
         int grid = 2 * f->n_cu;             // two workgroups per CU is what the registers allow; any grid drains the queues
-        if (f->mdr_persist_grid > 0) grid = f->mdr_persist_grid;      // GATOR_MDR_PERSIST_GRID (tests: a grid that leaves XCDs without a workgroup)
+        if (f->opt.mdr_persist_grid > 0) grid = f->opt.mdr_persist_grid;      // GATOR_MDR_PERSIST_GRID (tests: a grid that leaves XCDs without a workgroup)
         // A large batch runs as several launches over chunks of 256 .. 511 samples.  The tickets are stage-major, so a sample's Q/K/V/residual
         // tiles (448 KB) are read one stage after they were written: at B = 256 / 384 the 115 / 172 MB in between stay in the Infinity
         // Cache, at B = 512 and above they do not and the launch costs 1.545 - 1.565 us per sample instead of 1.495 (measured, round 4).
@@ -1952,10 +1950,10 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
         // nothing either, B = 512 .. 2048, two repetitions.)
         // (the one-plane form's Q / K / V tiles are half the size: chunks of 342 - 512 samples measure 6 % faster than 256 at B = 2 048 -- 3.25
         // against 3.45 ms per forward, two repetitions, one box -- so it runs ceil(B / 384) launches)
-        int nch = f->mdr_persist_chunk > 0 ? (B + f->mdr_persist_chunk - 1) / f->mdr_persist_chunk : (xa == 3 ? (B + 383) / 384 : B / 256);
+        int nch = f->opt.mdr_persist_chunk > 0 ? (B + f->opt.mdr_persist_chunk - 1) / f->opt.mdr_persist_chunk : (xa == 3 ? (B + 383) / 384 : B / 256);
         if (nch < 1) nch = 1;
         if (nch > kMdrCtrChunks) nch = kMdrCtrChunks;
-        const size_t tq = f->mdr_x3 == 1 ? kTileX3 : (xa == 3 ? kTileX1 : kTile);
+        const size_t tq = f->opt.mdr_x3 == 1 ? kTileX3 : (xa == 3 ? kTileX1 : kTile);
         plan = MdrChunkPlan{nch, B / nch, B % nch};
         for (int ch = 0, b0 = 0; ch < nch; ++ch) {
             const int n = B / nch + (ch < B % nch ? 1 : 0);
@@ -1975,8 +1973,8 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
             }
             pc_.ctr = f->mdr_ctr + plan.block(ch);
             if (xa == 3) k_mdr_persist<3><<<grid, 256, 0, st>>>(pc_);
-            else if (f->mdr_x3 == 2) k_mdr_persist<2><<<grid, 256, 0, st>>>(pc_);
-            else if (f->mdr_x3 == 1) k_mdr_persist<1><<<grid, 256, 0, st>>>(pc_);
+            else if (f->opt.mdr_x3 == 2) k_mdr_persist<2><<<grid, 256, 0, st>>>(pc_);
+            else if (f->opt.mdr_x3 == 1) k_mdr_persist<1><<<grid, 256, 0, st>>>(pc_);
             else k_mdr_persist<0><<<grid, 256, 0, st>>>(pc_);
             b0 += n;
         }
@@ -2029,8 +2027,8 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
     ha.persist_ctr = persist ? f->mdr_ctr : nullptr;
     ha.plan = plan;
     ha.status = c->status_dev;
-    ha.vcp2 = f->x3 && f->up_x2 ? (_Float16*)f->vcp3 : nullptr;
-    ha.vcp3 = f->x3 && !f->up_x2 ? (__bf16*)f->vcp3 : nullptr; ha.vcp3_plane = upsample_x3_vcp_elems(f->cap) / 3;     // plane stride fixed by the workspace capacity
+    ha.vcp2 = f->opt.up_x3 == 2 ? (_Float16*)f->vcp3 : nullptr;
+    ha.vcp3 = f->opt.up_x3 == 1 ? (__bf16*)f->vcp3 : nullptr; ha.vcp3_plane = upsample_x3_vcp_elems(f->cap) / 3;     // plane stride fixed by the workspace capacity
     ha.alpha = c->alpha;
     {
         StageTimer tm(c, "mdr_head", stream);

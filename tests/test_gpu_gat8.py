@@ -126,3 +126,28 @@ def test_fused_tail_agrees_with_the_two_tail_launches(monkeypatch, name):
     assert torch.equal(vp, v1[perm.cuda()]) and torch.equal(pp, p1[perm.cuda()])
     vs, ps = m1(x[10:13].cuda())
     assert torch.equal(vs, v1[10:13]) and torch.equal(ps, p1[10:13])
+
+
+def test_switches_are_read_per_context(monkeypatch):
+    """Every switch of the fused path is read when a context is created, for that context alone (fused_api.hip: read_fused_options).
+    A context created under GATOR_GAT8_LOBYTE=0 streams the three fp16 planes, whose k_gat8 has no fused tail: its forward runs the two
+    tail launches (stage 'gat_tail').  A context created after it without the switch takes the byte-lo stream and the fused tail.  At
+    B = 256, J = 17 the fused tail is the default form."""
+    monkeypatch.delenv('GATOR_GAT8_TAIL', raising=False)
+    monkeypatch.delenv('GATOR_GAT_TILED', raising=False)
+    x = torch.from_numpy(synthetic.synthetic_pose2d(256, 17, seed=256)).cuda()
+    monkeypatch.setenv('GATOR_GAT8_LOBYTE', '0')
+    z, m0 = build_model('h36m17_bn', 'fused')
+    m0(x)                                          # the first forward creates the context
+    monkeypatch.delenv('GATOR_GAT8_LOBYTE')
+    z, m1 = build_model('h36m17_bn', 'fused')
+    m1(x)
+    for m in (m0, m1):
+        m.profile(1)
+        m(x)
+    torch.cuda.synchronize()
+    m0.device_status(); m1.device_status()
+    p1, p0 = m1.profile_read(), m0.profile_read()      # (the first context read after the second)
+    assert 'gat' in p0 and 'gat' in p1
+    assert 'gat_tail' in p0, p0
+    assert 'gat_tail' not in p1, p1

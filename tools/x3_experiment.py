@@ -1,5 +1,5 @@
 """Experiment: split-precision (bf16x3) vertex regressor vs the fp32-MFMA one: error against fp64 and kernel time.
-Run twice: with and without GATOR_UPSAMPLE_X3=1 (the switch is read once per process)."""
+Run twice: with and without GATOR_UPSAMPLE_X3=1 (the switch is read when a context is created)."""
 import os, sys, json, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests.helpers import build_model
