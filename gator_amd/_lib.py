@@ -27,7 +27,7 @@ class GemmProblem(ctypes.Structure):            # include/gator_train.h: gator_g
 
 ABI_VERSION = 2                                 # include/gator_hip.h: GATOR_ABI_VERSION this binding was written against
 EDEVICE, EDEVICE_DEFERRED = -7, -8
-REASON_PERSIST_INCOMPLETE, REASON_NONFINITE = 1, 2      # gator_status_reason
+REASON_PERSIST_INCOMPLETE, REASON_NONFINITE, REASON_INPUT_NONFINITE = 1, 2, 3      # gator_status_reason
 
 
 class GatorConfig(ctypes.Structure):

@@ -236,7 +236,7 @@ extern "C" int gator_create(const gator_tensor* tensors, int32_t n, const gator_
         }
         c->status_host = (unsigned*)hp;
         c->status_dev = (unsigned*)dp;
-        *c->status_host = 0u;
+        for (int r = 0; r < DEV_REASONS; ++r) c->status_host[r] = 0u;
     }
     // arena: one device allocation holding a private copy of every tensor (256-B aligned), + folded constants
     size_t total = 0;
@@ -289,27 +289,40 @@ extern "C" int gator_create(const gator_tensor* tensors, int32_t n, const gator_
     return GATOR_OK;
 }
 
-// What a kernel left in the ctx's sticky status word (an EARLIER call's failure: nothing here synchronises).  Reported once, then cleared.
-// `executed`: the report rides on an entry point that has queued its own work normally (finish_fwd): the caller's buffers are being written.
-static int report_device_status(gator_ctx* c, unsigned st, const char* fn, bool executed) {
+// What the kernels left in the ctx's sticky status words (an EARLIER call's failure: nothing here synchronises), as a mask of (1 << reason).
+// Reported once, then cleared.  `executed`: the report rides on an entry point that has queued its own work normally (finish_fwd): the
+// caller's buffers are being written.  One reason is reported: the operand range first (a caller heals from it: re-create the ctx with
+// GATOR_ARITH_EXACT_SPLIT), then the persistent launch (handled here), then a non-finite input pose (nothing to heal).
+static int report_device_status(gator_ctx* c, unsigned mask, const char* fn, bool executed) {
     const int code = executed ? GATOR_EDEVICE_DEFERRED : GATOR_EDEVICE;
-    if (st) c->status_reason = (int)st;
-    const char* tail = executed ? "  THIS call was queued normally; its outputs are valid unless the next call reports again." : "";
-    if (st == DEV_PERSIST_INCOMPLETE) {
+    const int st = mask & (1u << DEV_NONFINITE) ? DEV_NONFINITE : mask & (1u << DEV_PERSIST_INCOMPLETE) ? DEV_PERSIST_INCOMPLETE
+                   : mask & (1u << DEV_INPUT_NONFINITE) ? DEV_INPUT_NONFINITE : DEV_OK;
+    if (st) c->status_reason = st;
+    if (mask & (1u << DEV_PERSIST_INCOMPLETE))
         fused_disable_persist(c);        // e.g. an XCD without workgroups (CU mask): its queue is never served.  The four-launch form has no such dependency.
+    const char* tail = executed ? "  THIS call was queued normally; its outputs are valid unless the next call reports again." : "";
+    if (st == DEV_PERSIST_INCOMPLETE)
         return fail(code, "%s: an earlier forward on this ctx did not complete its persistent MDR launch (a sample's stage tiles were never "
                                    "finished: an XCD without workgroups, or the hang guard); the vertices of that forward are NaN.  This ctx now uses the "
                                    "four-launch form of the MDR stages (same results); GATOR_MDR_PERSIST=0 selects it from the start.%s", fn, tail);
-    }
     if (st == DEV_NONFINITE)
-        return fail(code, "%s: an earlier forward on this ctx produced non-finite or out-of-range coarse vertices.  Either its input poses "
-                                   "were not finite (the reference returns NaN for those too), or the weights drive an activation out of the default "
-                                   "arithmetic's range (|vert431| must stay below 4094 m, and every activation that feeds a token-wise linear below "
-                                   "4094: they travel as fp16 planes of 16 x value); a ctx created with gator_config.arithmetic = GATOR_ARITH_EXACT_SPLIT "
-                                   "(model.arithmetic = 'exact') runs the bf16 forms without that range limit.%s", fn, tail);
+        return fail(code, "%s: an earlier forward on this ctx produced non-finite or out-of-range coarse vertices in samples whose input poses are "
+                                   "finite: the weights drive an activation out of the default arithmetic's range (|vert431| must stay below 4094 m, "
+                                   "and every activation that feeds a token-wise linear below 4094: they travel as fp16 planes of 16 x value); a ctx "
+                                   "created with gator_config.arithmetic = GATOR_ARITH_EXACT_SPLIT (model.arithmetic = 'exact') runs the bf16 forms "
+                                   "without that range limit.%s", fn, tail);
+    if (st == DEV_INPUT_NONFINITE)
+        return fail(code, "%s: an earlier forward on this ctx had samples with a non-finite input pose (NaN / inf keypoints); their vertices are "
+                                   "NaN, as the reference's are, and no other sample is affected.  Nothing to change on the ctx.%s", fn, tail);
     return GATOR_OK;
 }
-static unsigned take_status_word(gator_ctx* c) { return c->status_host ? __atomic_exchange_n(c->status_host, 0u, __ATOMIC_RELAXED) : 0u; }
+static unsigned take_status_word(gator_ctx* c) {
+    unsigned mask = 0u;
+    if (c->status_host)
+        for (int r = 1; r < DEV_REASONS; ++r)
+            if (__atomic_exchange_n(c->status_host + r, 0u, __ATOMIC_RELAXED)) mask |= 1u << r;
+    return mask;
+}
 
 extern "C" int gator_status_reason(gator_ctx* c) { return c ? c->status_reason : 0; }
 extern "C" int gator_c3_state(gator_ctx* c, float* logit_bound) {
@@ -336,7 +349,7 @@ static int check_fwd(gator_ctx* c, const void* a, const void* b, int B, const ch
     if (!c || !a || !b || B <= 0) return fail(GATOR_EINVAL, "%s: null pointer or batch <= 0", fn);
     if (const unsigned st = take_status_word(c)) {
         c->deferred_status = st;
-        if (st == DEV_PERSIST_INCOMPLETE) fused_disable_persist(c);
+        if (st & (1u << DEV_PERSIST_INCOMPLETE)) fused_disable_persist(c);
     }
     c->profiling = c->prof_stride > 0 && (c->prof_calls++ % c->prof_stride) == 0;
     GATOR_HIP_CHECK(hipSetDevice(c->device));

@@ -121,43 +121,69 @@ int read_fused_options(const gator_ctx* c, FusedOptions* o) {
     return GATOR_OK;
 }
 
+// Largest eigenvalue of a symmetric n x n matrix (row-major; destroyed): cyclic Jacobi rotations until the off-diagonal part is gone to
+// double rounding.  Unlike a power iteration it needs no start vector, so no weight can hide its top direction from it.
+static double sym_eig_max(std::vector<double>& A, int n) {
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        double off = 0, all = 0;
+        for (int p = 0; p < n; ++p)
+            for (int q = 0; q < n; ++q) { all += A[p * n + q] * A[p * n + q]; if (q > p) off += A[p * n + q] * A[p * n + q]; }
+        if (!(off > 1e-30 * all)) break;
+        for (int p = 0; p < n; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = A[p * n + q];
+                if (apq == 0) continue;
+                const double th = (A[q * n + q] - A[p * n + p]) / (2 * apq);
+                const double t = (th >= 0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1));
+                const double cs = 1 / std::sqrt(t * t + 1), sn = t * cs;
+                for (int k = 0; k < n; ++k) {       // A <- A J, then A <- J^T A: zeroes A[p][q]
+                    const double kp = A[k * n + p], kq = A[k * n + q];
+                    A[k * n + p] = cs * kp - sn * kq; A[k * n + q] = sn * kp + cs * kq;
+                }
+                for (int k = 0; k < n; ++k) {
+                    const double pk = A[p * n + k], qk = A[q * n + k];
+                    A[p * n + k] = cs * pk - sn * qk; A[q * n + k] = sn * pk + cs * qk;
+                }
+            }
+    }
+    double m = 0;
+    for (int i = 0; i < n; ++i) m = std::max(m, A[i * n + i]);
+    return m;
+}
+
 // Guard of config 3's 16-bit mode (round 6): its 431 x 431 attention carries q and k on ONE fp16 plane each, which moves a
 // score by up to 2^-11 |q| |k|.  |q| |k| is bounded from the weights alone: the custom LayerNorm in front of the in-projections gives
 // every token unit unbiased standard deviation, |x| <= max|a_2| sqrt(63) + |b_2| (vanilla_transformer_encoder.py:31-34), and per head
-// |q . k| <= sigma_max(Wq_h^T Wk_h) |x|^2 / sqrt(d_k) (biases aside).  Returns the largest bound over layers and heads, in the exp2
-// domain; gator_c3_state() reports it.
+// |q_h| <= sigma_max(Wq_h) |x| + |bq_h|, |k_h| likewise, so |q_h . k_h| / sqrt(d_k) <= (sigma_max(Wq_h) |x| + |bq_h|) (sigma_max(Wk_h) |x| +
+// |bk_h|) / sqrt(d_k).  sigma_max is exact: the largest eigenvalue of the 32 x 32 Gram matrix W_h W_h^T, in double.  Returns the largest
+// bound over layers and heads, in the exp2 domain; gator_c3_state() reports it.
 float c3_logit_bound(const Weights& w) {
-    float worst = 0.f;
+    double worst = 0;
     for (int li = 0; li < 3; ++li) {
         const MdrLayerW& r = w.lay[li];
-        const std::vector<float> wq = d2h(r.sa_w[0], 64 * 64), wk = d2h(r.sa_w[1], 64 * 64), a2 = d2h(r.a2, 64), b2 = d2h(r.b2, 64);
+        const std::vector<float> wq = d2h(r.sa_w[0], 64 * 64), wk = d2h(r.sa_w[1], 64 * 64), bq = d2h(r.sa_b[0], 64), bk = d2h(r.sa_b[1], 64),
+                                 a2 = d2h(r.a2, 64), b2 = d2h(r.b2, 64);
         double amax = 0, bn = 0;
         for (int i = 0; i < 64; ++i) { amax = std::max(amax, (double)std::fabs(a2[i])); bn += (double)b2[i] * b2[i]; }
         const double xn = amax * std::sqrt(63.0) + std::sqrt(bn);
-        for (int hd = 0; hd < 2; ++hd) {
-            // M = Wq_h^T Wk_h (64 x 64); sigma_max by power iteration on M^T M
-            std::vector<double> M(64 * 64, 0.0), v(64, 1.0), t(64), u(64);
-            for (int i = 0; i < 64; ++i)
-                for (int j = 0; j < 64; ++j) {
+        // |W_h x + b_h| <= sigma_max(W_h) |x| + |b_h| for head hd's 32 rows of an in-projection
+        auto head_norm = [&](const std::vector<float>& W, const std::vector<float>& bias, int hd) {
+            std::vector<double> G(32 * 32);
+            double bb = 0;
+            for (int i = 0; i < 32; ++i) {
+                bb += (double)bias[32 * hd + i] * bias[32 * hd + i];
+                for (int j = 0; j < 32; ++j) {
                     double acc = 0;
-                    for (int c2 = 0; c2 < 32; ++c2) acc += (double)wq[(32 * hd + c2) * 64 + i] * (double)wk[(32 * hd + c2) * 64 + j];
-                    M[i * 64 + j] = acc;
+                    for (int k = 0; k < 64; ++k) acc += (double)W[(32 * hd + i) * 64 + k] * (double)W[(32 * hd + j) * 64 + k];
+                    G[i * 32 + j] = acc;
                 }
-            double sig = 0;
-            for (int it = 0; it < 64; ++it) {
-                for (int i = 0; i < 64; ++i) { double acc = 0; for (int j = 0; j < 64; ++j) acc += M[i * 64 + j] * v[j]; t[i] = acc; }
-                for (int j = 0; j < 64; ++j) { double acc = 0; for (int i = 0; i < 64; ++i) acc += M[i * 64 + j] * t[i]; u[j] = acc; }
-                double n = 0;
-                for (int j = 0; j < 64; ++j) n += u[j] * u[j];
-                n = std::sqrt(n);
-                if (!(n > 0)) break;
-                sig = std::sqrt(n);                      // |M^T M v| -> sigma_max^2 for a unit v
-                for (int j = 0; j < 64; ++j) v[j] = u[j] / n;
             }
-            worst = std::max(worst, (float)(sig * xn * xn / std::sqrt(32.0) * 1.4426950408889634));
-        }
+            return std::sqrt(std::max(sym_eig_max(G, 32), 0.0)) * xn + std::sqrt(bb);
+        };
+        for (int hd = 0; hd < 2; ++hd)
+            worst = std::max(worst, head_norm(wq, bq, hd) * head_norm(wk, bk, hd) / std::sqrt(32.0) * 1.4426950408889634);
     }
-    return worst;
+    return (float)worst;
 }
 
 int fused_create_gat(gator_ctx* c, FusedState* f, void* stream) {

@@ -1369,9 +1369,27 @@ struct HeadArgs {
     _Float16* vcp2;         // non-null: write the scaled hi/lo fp16 planes of the two-plane vertex GEMM (upsample_x2.hip) instead
     const unsigned* persist_ctr;   // non-null: the counter blocks of the forward's persistent launches.  The sample's launch must not have tripped its
     MdrChunkPlan plan;             // hang guard and must have counted all 14 last-stage tiles of the sample; else its vertices are NaN (loud, not silent)
-    unsigned* status;              // the ctx's sticky device status word (host-mapped; internal.h: DeviceStatus), read by the next API call
+    unsigned* status;              // the ctx's sticky device status words, one per DeviceStatus reason (host-mapped; internal.h), read by the next API call
+    const float* pose2d;           // the forward's input poses [B][J][2] (non-null on the whole-forward path): a bad sample whose own input is not
+    int J;                         // finite reports DEV_INPUT_NONFINITE -- the reference returns NaN for it too -- instead of DEV_NONFINITE
     int alpha;
 };
+
+// A wave whose tokens of sample b hold a bad coarse vertex reports why: its persistent launch did not finish the sample (1), the sample's own
+// input pose is not finite (3), else a non-finite activation or the operand range (2).  Each reason has its own status word, set by a plain
+// store, so the reports of one forward never overwrite each other whatever the order of their waves.  The input is only read when bad.
+__device__ __forceinline__ void head_report(const HeadArgs& a, int b, bool bad, bool poisoned) {
+    if (!a.status || !__any(bad)) return;
+    const int lane = threadIdx.x & 63;
+    bool in_bad = false;
+    if (a.pose2d && !poisoned) {
+        for (int i = lane; i < 2 * a.J; i += 64) in_bad = in_bad || !__builtin_isfinite(a.pose2d[(size_t)b * 2 * a.J + i]);
+        in_bad = __any(in_bad);
+    }
+    if (lane == 0)      // sticky, host-visible: the next API call on the ctx (or gator_device_status) reports it
+        __hip_atomic_store(a.status + (poisoned ? DEV_PERSIST_INCOMPLETE : in_bad ? DEV_INPUT_NONFINITE : DEV_NONFINITE), 1u, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // where a coarse vertex coordinate goes: the reference layout (tap / stage API) and the packed A operand of whichever vertex GEMM the ctx runs
 __device__ __forceinline__ void head_store(const HeadArgs& a, int b, int v, int c, float val) {
@@ -1402,7 +1420,7 @@ __device__ __forceinline__ void head_store(const HeadArgs& a, int b, int v, int 
 // Light by construction: no conv, no cross-lane sums.
 template <int NT>
 __device__ __forceinline__ void head_finish(const HeadArgs& a, const double* __restrict__ hpart_b, int b, bool poisoned, float (*bc)[3]) {
-    const int t = threadIdx.x, lane = t & 63;
+    const int t = threadIdx.x;
     const float* hf = a.hf + (size_t)b * kV * 32;
     constexpr int NR = (kV + NT - 1) / NT;
     // every global read up front: this thread's tokens' head features, and (threads 0..59) the partials of output (row, position) t
@@ -1455,8 +1473,7 @@ __device__ __forceinline__ void head_finish(const HeadArgs& a, const double* __r
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (a.status && __any(bad) && lane == 0)      // sticky, host-visible: the next API call on the ctx (or gator_device_status) reports it
-        __hip_atomic_store(a.status, poisoned ? (unsigned)DEV_PERSIST_INCOMPLETE : (unsigned)DEV_NONFINITE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    head_report(a, b, bad, poisoned);
 }
 
 struct MdrPersistArgs {
@@ -1797,8 +1814,7 @@ __global__ __launch_bounds__(NT, HOIST ? 2 : 4) void k_mdr_head(const HeadArgs a
             }
         }
     }
-    if (a.status && __any(bad) && lane == 0)      // sticky, host-visible: the next API call on the ctx (or gator_device_status) reports it
-        __hip_atomic_store(a.status, poisoned ? (unsigned)DEV_PERSIST_INCOMPLETE : (unsigned)DEV_NONFINITE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    head_report(a, b, bad, poisoned);
 }
 
 __global__ __launch_bounds__(256) void k_mdr_head_finish(const HeadArgs a, const double* __restrict__ hpart) {
@@ -1831,7 +1847,6 @@ LayerW make_layer(const FusedState* f, const gator_ctx* c, int li) {
 
 // pc [B,J,133] (reference layout) -> f->vc [B,431,3] (vert431) ; taps: f->lbf
 int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream, const float* x_out, const float* pose2d, bool half16) {
-    (void)pose2d;
     // half16 (BASELINE config 3): the layers on ONE fp16 activation plane (XA = 3); needs the default weight / joint-tile forms (GATOR_MDR_X3=2)
     if (half16 && f->opt.mdr_x3 != 2) return fail(GATOR_EUNSUPPORTED, "16-bit MDR layers need GATOR_MDR_X3=2 (the default)");
     const int xa = half16 ? 3 : f->opt.mdr_x3;
@@ -2027,6 +2042,7 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
     ha.persist_ctr = persist ? f->mdr_ctr : nullptr;
     ha.plan = plan;
     ha.status = c->status_dev;
+    ha.pose2d = pose2d; ha.J = c->J;      // nullptr from the MDR-only entry point: its input is the pose features, not the poses
     ha.vcp2 = f->opt.up_x3 == 2 ? (_Float16*)f->vcp3 : nullptr;
     ha.vcp3 = f->opt.up_x3 == 1 ? (__bf16*)f->vcp3 : nullptr; ha.vcp3_plane = upsample_x3_vcp_elems(f->cap) / 3;     // plane stride fixed by the workspace capacity
     ha.alpha = c->alpha;

@@ -107,8 +107,10 @@ int gator_destroy(gator_ctx* ctx);
  * (the reference raises at the point of use, lib/core/base.py:210-237; this is the asynchronous equivalent). */
 int gator_device_status(gator_ctx* ctx, int32_t sync);
 /* Why the last GATOR_EDEVICE / GATOR_EDEVICE_DEFERRED of this ctx was returned: 1 = a persistent MDR launch did not finish (the ctx has switched to
- * the four-launch form), 2 = non-finite / out-of-range coarse vertices (input poses not finite, or the default arithmetic's operand range:
- * re-create the ctx with GATOR_ARITH_EXACT_SPLIT -- gator_amd/models/_base.py does exactly that by itself), 0 = none yet. */
+ * the four-launch form), 2 = non-finite / out-of-range coarse vertices in samples with finite input poses (the default arithmetic's operand range:
+ * re-create the ctx with GATOR_ARITH_EXACT_SPLIT -- gator_amd/models/_base.py does exactly that by itself), 3 = samples whose input pose is not
+ * finite (their vertices are NaN, as the reference's are; nothing to change), 0 = none yet.  When one forward has several reasons, 2 is
+ * reported before 1 and 1 before 3; the MDR-only entry point (gator_mdr_forward_f32) does not see the poses and reports 2 for those. */
 int gator_status_reason(gator_ctx* ctx);
 
 /* Replaces: GATOR.forward (lib/models/GATOR.py:16-22).

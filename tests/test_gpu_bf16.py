@@ -151,10 +151,10 @@ def test_config3_attention_long_way_under_large_logits(gain, monkeypatch):
 
 @pytest.mark.parametrize('gain,one_plane', [(1.0, True), (3.0, True), (8.0, False)])
 def test_config3_guard_keeps_two_planes_under_sharp_attention(gain, one_plane):
-    """Round 6: gator_create bounds the self-attention logits from the weights (sigma_max(Wq_h^T Wk_h) x the custom LayerNorm's bound on
-    |x|^2); above 2^10 in the exp2 domain the MDR layers of gator_forward_bf16 keep two planes for that ctx.  The shipped synthetic weights (bound ~50)
-    and the logits-x-9 weights (~470, measured 0.63 mm) stay in the mode; logits x 64 (~3 300, measured 7.6 mm in the mode) fall out of it and meet
-    the mode's bar again -- a checkpoint with sharp attention degrades in speed, not silently in millimetres."""
+    """Round 6: gator_create bounds the self-attention logits from the weights ((sigma_max(Wq_h) |x| + |bq_h|)(sigma_max(Wk_h) |x| + |bk_h|)
+    with the custom LayerNorm's bound on |x|); above 2^10 in the exp2 domain the MDR layers of gator_forward_bf16 keep two planes for that ctx.  The shipped
+    synthetic weights (bound ~75) and the logits-x-9 weights (~670, measured 0.63 mm) stay in the mode; logits x 64 (~4 800, measured 7.6 mm in the mode)
+    fall out of it and meet the mode's bar again -- a checkpoint with sharp attention degrades in speed, not silently in millimetres."""
     from oracle import gator_oracle as go
     z, m = build_model('h36m17_bn', 'fused', device=None)
     zz, c, sd_o = oracle_setup('h36m17_bn')
@@ -196,3 +196,98 @@ def test_config3_persistent_launch_equals_four_launches_bitwise(monkeypatch):
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), B
     m1.device_status()
     m0.device_status()
+
+
+def _sylvester(n):
+    h = np.ones((1, 1), np.float32)
+    while h.shape[0] < n:
+        h = np.block([[h, h], [h, -h]])
+    return h
+
+
+def _c3_bounds(sd):
+    """(the fixed guard's bound, the round-6 power iteration's) of the self-attention logits, restated in numpy float64 from the weights:
+    per layer and head, (sigma_max(Wq_h) |x| + |bq_h|) (sigma_max(Wk_h) |x| + |bk_h|) / sqrt(32) in the exp2 domain, |x| <= max|a_2| sqrt(63)
+    + |b_2|; and sigma_max(Wq_h^T Wk_h) |x|^2 / sqrt(32) by 64 power steps from the all-ones vector."""
+    new = old = 0.0
+    for sfx in ('', '_1', '_2'):
+        g = lambda k: np.asarray(sd['pose2mesh.' + k % sfx], np.float32).astype(np.float64)
+        wq, wk, bq, bk = g('selfatt%s.linears.0.weight'), g('selfatt%s.linears.1.weight'), g('selfatt%s.linears.0.bias'), g('selfatt%s.linears.1.bias')
+        a2, b2 = g('norm%s.a_2'), g('norm%s.b_2')
+        xn = np.abs(a2).max() * np.sqrt(63.0) + np.sqrt((b2 ** 2).sum())
+        for h in range(2):
+            r = slice(32 * h, 32 * h + 32)
+            sq, sk = np.linalg.svd(wq[r], compute_uv=False)[0], np.linalg.svd(wk[r], compute_uv=False)[0]
+            new = max(new, (sq * xn + np.linalg.norm(bq[r])) * (sk * xn + np.linalg.norm(bk[r])) / np.sqrt(32.0) * np.log2(np.e))
+            M, v, sig = wq[r].T @ wk[r], np.ones(64), 0.0
+            for _ in range(64):
+                u = M.T @ (M @ v)
+                n = np.sqrt((u * u).sum())
+                if not n > 0:
+                    break
+                sig, v = np.sqrt(n), u / n
+            old = max(old, sig * xn * xn / np.sqrt(32.0) * np.log2(np.e))
+    return new, old
+
+
+@pytest.mark.parametrize('name', ['h36m17_bn', 'coco19_alpha'])
+def test_config3_guard_bound_formula(name):
+    """gator_c3_state's bound on the golden weights against the numpy restatement of the formula (the golden variants stay on one plane)."""
+    z, m = build_model(name, 'fused')
+    zz, c, sd = oracle_setup(name)
+    m.precision = 'bf16'
+    m(torch.from_numpy(synthetic.synthetic_pose2d(4, c.J, seed=2)).cuda())
+    torch.cuda.synchronize()
+    state, bound = m.c3_state()
+    new, old = _c3_bounds(sd)
+    print('\n[config 3 guard, %s] bound %.2f (numpy %.2f; the power iteration gave %.2f)' % (name, bound, new, old))
+    assert state and abs(bound - new) <= 1e-4 * new
+
+
+def _adversarial(sd, case):
+    """Weights that the power iteration misjudged: Hadamard q / k rows in one head (M 1 = 0 exactly), or the q / k biases scaled alone."""
+    sd = dict(sd)
+    if case.startswith('hadamard'):
+        li, h, a = {'hadamard_l0h0': (0, 0, 2.0), 'hadamard_l2h1': (2, 1, 2.0)}[case]
+        rows = torch.from_numpy(_sylvester(64)[1:33] * a)          # rows other than the all-ones one: every row sums to zero
+        for n in (0, 1):
+            k = 'pose2mesh.selfatt%s.linears.%d.weight' % (('', '_1', '_2')[li], n)
+            t = sd[k].clone()
+            t[32 * h:32 * h + 32] = rows
+            sd[k] = t
+    else:
+        for sfx in ('', '_1', '_2'):
+            for n in (0, 1):
+                k = 'pose2mesh.selfatt%s.linears.%d.bias' % (sfx, n)
+                sd[k] = sd[k] * 1000.0
+    return sd
+
+
+@pytest.mark.parametrize('case', ['hadamard_l0h0', 'hadamard_l2h1', 'bias_x1000'])
+def test_config3_guard_against_adversarial_weights(case):
+    """The guard must be an upper bound whatever the weights.  Hadamard rows (times 2) as Wq_h and Wk_h of one head: M = Wq_h^T Wk_h sends
+    the all-ones vector to exactly 0, so a power iteration started there returns sigma = 0 for that head (true sigma_max(M) = 256); the
+    q / k biases x 800: the logits reach the gain-8 level through the bias terms alone.  Either the ctx keeps two planes and meets the
+    mode's bar against the fp64 oracle of the same weights, or its bound is <= 2^10 and the bar holds on one plane."""
+    from oracle import gator_oracle as go
+    z, m = build_model('h36m17_bn', 'fused', device=None)
+    zz, c, sd_o = oracle_setup('h36m17_bn')
+    sd_o = _adversarial(sd_o, case)
+    sd = m.state_dict()
+    sd.update({k: v for k, v in sd_o.items() if k in sd})
+    m.load_state_dict(sd)
+    m = m.cuda()
+    m.precision = 'bf16'
+    x = torch.from_numpy(synthetic.synthetic_pose2d(24, 17, seed=9))
+    v, p = m(x.cuda())
+    torch.cuda.synchronize()
+    m.device_status()
+    state, bound = m.c3_state()
+    new, old = _c3_bounds(sd_o)
+    r64, _ = go.gator_forward(sd_o, c, x, torch.float64)
+    e = np.abs(v.cpu().numpy().astype(np.float64) - r64.numpy()) * 1e3
+    print('\n[config 3 guard, %s] bound %.1f (fixed formula %.1f, power iteration %.1f) -> MDR layers on %s; vs fp64: max %.3f mm rms %.4f mm'
+          % (case, bound, new, old, 'one plane' if state else 'two planes', e.max(), np.sqrt((e ** 2).mean())))
+    assert bound >= new * (1 - 1e-4)                                 # an upper bound of the logits, not an estimate from below
+    assert (not state) or bound <= 1024.0
+    assert e.max() < 1.0 and np.sqrt((e ** 2).mean()) < 0.2

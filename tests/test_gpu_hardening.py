@@ -271,3 +271,53 @@ def test_attention_rescale_paths_under_large_logits(gain):
     v2, _ = m(x.cuda())
     vs, _ = m(x[5:9].cuda())
     assert torch.equal(v, v2) and torch.equal(vs, v[5:9])
+
+
+@pytest.mark.parametrize('level', [0.95, 1.05])
+@pytest.mark.parametrize('form', ['default', 'upsample_x3', 'exact'])
+def test_coarse_vertex_range_at_its_edge(form, level, monkeypatch):
+    """The two-plane vertex regressor carries 16 x vert431 in fp16 planes: |vert431| < 4 094 (k_mdr_head / k_mdr_head_finish flag the rest).
+    A constant added to every bias_conv1d row shifts every coarse vertex by that constant (the softmax mix of MDR.py:161-166 sums to 1),
+    driving max|vert431| to 0.95 x and 1.05 x the limit.  Below it, and in the forms without the limit (GATOR_UPSAMPLE_X3=1, arithmetic =
+    'exact') at both levels: no report, and the scale-free bar of test_scale_free_parity on the whole mesh.  Above it, the default form
+    is loud (NaN, then reason 2) and heals to the same bar: there is no window where the answer is silently wrong."""
+    import warnings
+    from oracle import gator_oracle as go
+    monkeypatch.delenv('GATOR_UPSAMPLE_X3', raising=False)
+    if form == 'upsample_x3':
+        monkeypatch.setenv('GATOR_UPSAMPLE_X3', '1')
+    z, m = build_model('h36m17_bn', 'fused', device=None)
+    zz, c, sd_o = oracle_setup('h36m17_bn')
+    x = torch.from_numpy(synthetic.synthetic_pose2d(16, 17, seed=5))
+    taps = {}
+    go.gator_forward(sd_o, c, x, torch.float64, taps)
+    vc = taps['vert431']
+    key = 'pose2mesh.bias_conv1d.bias'
+    shift = level * 4094.0 - float(vc.max())
+    sd = m.state_dict()
+    sd[key] = sd[key] + shift
+    sd_o[key] = sd_o[key] + shift
+    m.load_state_dict(sd)
+    if form == 'exact':
+        m.arithmetic = 'exact'
+    m = m.cuda()
+    taps = {}
+    r64, _ = go.gator_forward(sd_o, c, x, torch.float64, taps)
+    r32, _ = go.gator_forward(sd_o, c, x, torch.float32)
+    top = float(taps['vert431'].abs().max())
+    assert abs(top / 4094.0 - level) < 1e-3
+    v, p = m(x.cuda())
+    torch.cuda.synchronize()
+    if form == 'default' and level > 1.0:
+        assert not torch.isfinite(v).all()                  # loud in the data ...
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter('always')
+            v, p = m(x.cuda())                              # ... the next call carries reason 2 and heals
+            torch.cuda.synchronize()
+        assert m.arithmetic == 'exact' and any('exact' in str(i.message) for i in w)
+    m.device_status()
+    ours = np.abs(v.cpu().numpy().astype(np.float64) - r64.numpy())
+    ref = np.abs(r32.numpy().astype(np.float64) - r64.numpy())
+    print('\n[%s, max|vert431| = %.3f x 4094] ours vs fp64: max %.3e m rms %.3e m ; ref fp32 vs fp64: max %.3e m rms %.3e m'
+          % (form, top / 4094.0, ours.max(), np.sqrt((ours ** 2).mean()), ref.max(), np.sqrt((ref ** 2).mean())))
+    assert ours.max() <= 1.5 * ref.max()

@@ -1,0 +1,307 @@
+"""Poisoned samples: a sample whose input pose holds NaN / inf keypoints (a detector that lost a joint) must change no other sample's
+numbers, in every forward form -- several kernels put several samples into one workgroup or tile (the sample-tiled encoder, the vertex
+regressor's M tiles, the persistent MDR launch, the two sub-batch streams, the hipGraph replay) -- and must come out non-finite exactly
+where the fp64 oracle's does.  And it must not cost the module its arithmetic: the device reports such a forward with reason 3
+(GATOR_EDEVICE_DEFERRED, include/gator_hip.h: gator_status_reason), which the heal policy (gator_amd/models/_base.py: _run) answers with a
+warning, where reason 2 -- the default arithmetic's operand range -- still switches the module to arithmetic = 'exact'."""
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from gator_amd import _lib
+from gator_amd import eval as geval
+from gator_amd import synthetic
+from tests.helpers import build_model, oracle_setup
+
+pytestmark = pytest.mark.gpu
+
+KINDS = ('nan1', 'inf1', 'nanall')
+_ORACLE = {}
+
+
+def _poison(x, p, kind):
+    """A copy of the batch x [B,J,2] (host) that differs in sample p only."""
+    y = x.clone()
+    if kind == 'nan1':
+        y[p, 3, 1] = float('nan')
+    elif kind == 'inf1':
+        y[p, 0, 0] = float('inf')
+    else:
+        y[p] = float('nan')
+    return y
+
+
+def _oracle_finite(name, sample):
+    """-> (verts finite [6890,3], pose3d finite [J,3]) of the fp64 oracle on ONE sample [J,2] (host)."""
+    key = (name, sample.numpy().tobytes())
+    if key not in _ORACLE:
+        from oracle import gator_oracle as go
+        zz, c, sd = oracle_setup(name)
+        v, p = go.gator_forward(sd, c, sample[None], torch.float64)
+        _ORACLE[key] = (torch.isfinite(v[0]), torch.isfinite(p[0]))
+    return _ORACLE[key]
+
+
+def _assert_isolated(clean, bad, p, what):
+    """Every sample but p bitwise equal between the clean and the poisoned run."""
+    for a, b in zip(clean, bad):
+        keep = torch.ones(a.shape[0], dtype=torch.bool, device=a.device)
+        keep[p] = False
+        assert torch.equal(a[keep], b[keep]), '%s: a sample other than %d changed' % (what, p)
+
+
+def _assert_poisoned_like_oracle(name, xp, p, verts, pose3d, what):
+    fv, fp = _oracle_finite(name, xp[p])
+    assert not fv.all(), 'the oracle gives a finite mesh for a non-finite pose: the case tests nothing'
+    assert torch.equal(torch.isfinite(verts[p]).cpu(), fv), '%s: sample %d is non-finite elsewhere than the fp64 oracle' % (what, p)
+    assert torch.equal(torch.isfinite(pose3d[p]).cpu(), fp), '%s: pose3d of sample %d is non-finite elsewhere than the fp64 oracle' % (what, p)
+
+
+def _read_report(m, reports):
+    """The poisoned run's report, read and cleared with device_status() before any compared forward can carry it."""
+    torch.cuda.synchronize()
+    if reports:
+        with pytest.raises(_lib.DeviceStatusError, match='non-finite'):
+            m.device_status()
+    m.device_status()
+
+
+def _pair(m, name, x, p, kind, what, reports=True, fwd=None):
+    """Clean batch first, the batch poisoned in sample p second, through the same module."""
+    fwd = fwd or (lambda t: m(t))
+    xp = _poison(x, p, kind)
+    clean = [t.clone() for t in fwd(x.cuda())]
+    torch.cuda.synchronize()
+    m.device_status()
+    bad = fwd(xp.cuda())
+    _read_report(m, reports)
+    _assert_isolated(clean, bad, p, '%s %s' % (what, kind))
+    _assert_poisoned_like_oracle(name, xp, p, bad[0], bad[1], '%s %s' % (what, kind))
+    assert m.arithmetic == 'default' or what.startswith('exact')
+    return clean, bad
+
+
+FORMS = [('default', {}), ('gat8_tail0', {'GATOR_GAT8_TAIL': '0'}), ('gat8_0', {'GATOR_GAT8': '0'}),
+         ('persist0', {'GATOR_MDR_PERSIST': '0'}), ('persist1', {'GATOR_MDR_PERSIST': '1'}),
+         ('head_partials0', {'GATOR_MDR_HEAD_PARTIALS': '0'}), ('upsample_x3_1', {'GATOR_UPSAMPLE_X3': '1'}),
+         ('upsample_x3_0', {'GATOR_UPSAMPLE_X3': '0'})]
+
+
+def _clear_switches(monkeypatch):
+    for k in ('GATOR_GAT8_TAIL', 'GATOR_GAT8', 'GATOR_MDR_PERSIST', 'GATOR_MDR_HEAD_PARTIALS', 'GATOR_UPSAMPLE_X3', 'GATOR_GAT_TILED',
+              'GATOR_GAT_TILED_MIN_BATCH', 'GATOR_SUBBATCH_STREAMS'):
+        monkeypatch.delenv(k, raising=False)
+
+
+def _model_under(monkeypatch, name, env, impl='fused'):
+    """A module whose context is created (first forward) under `env`: the fused path reads its switches once per context."""
+    _clear_switches(monkeypatch)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    z, m = build_model(name, impl)
+    J = 17 if name == 'h36m17_bn' else 19
+    m(torch.from_numpy(synthetic.synthetic_pose2d(2, J, seed=1)).cuda())
+    torch.cuda.synchronize()
+    _clear_switches(monkeypatch)
+    return m
+
+
+CASES = [(f, e, 'h36m17_bn') for f, e in FORMS] + [(f, e, 'coco19_alpha') for f, e in FORMS if f in ('default', 'persist1', 'upsample_x3_1')]
+
+
+@pytest.mark.parametrize('form,env,name', CASES, ids=['%s-%s' % (c[0], c[2]) for c in CASES])
+def test_poisoned_sample_is_isolated(form, env, name, monkeypatch):
+    m = _model_under(monkeypatch, name, env)
+    J = 17 if name == 'h36m17_bn' else 19
+    x = torch.from_numpy(synthetic.synthetic_pose2d(24, J, seed=40))
+    for kind in KINDS:
+        _pair(m, name, x, 5, kind, form)
+
+
+@pytest.mark.parametrize('name,B', [('h36m17_bn', 17), ('coco19_alpha', 15)])
+def test_poisoned_sample_is_isolated_on_the_tiled_encoder(name, B, monkeypatch):
+    """GATOR_GAT_TILED=1: 7 (J = 17) resp. 6 (J = 19) samples share a workgroup's dense token tiles; p on both sides of each workgroup
+    edge and the last sample of the ragged last workgroup."""
+    m = _model_under(monkeypatch, name, {'GATOR_GAT_TILED': '1'})
+    J = 17 if name == 'h36m17_bn' else 19
+    S = 7 if J == 17 else 6
+    x = torch.from_numpy(synthetic.synthetic_pose2d(B, J, seed=41))
+    assert m.encoder_for_batch(B) == 'tiled'
+    for p in sorted({0, S - 1, S, 6, 7, B - 1}):
+        for kind in ('nan1', 'nanall'):
+            _pair(m, name, x, p, kind, 'tiled p=%d' % p)
+
+
+def test_poisoned_sample_is_isolated_across_the_tiled_split(monkeypatch):
+    """The shipped policy at a batch of one full round of the sample-tiled encoder plus a remainder that k_gat8 takes: p on each side."""
+    m = _model_under(monkeypatch, 'h36m17_bn', {})
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    n_tiled = n_cu * 7
+    B = n_tiled + 64
+    assert B <= 4096 and m.encoder_for_batch(B) == 'tiled'
+    x = torch.from_numpy(synthetic.synthetic_pose2d(B, 17, seed=42))
+    for p in (0, n_tiled - 1, n_tiled, B - 1):
+        _pair(m, 'h36m17_bn', x, p, 'nan1', 'split p=%d' % p)
+
+
+@pytest.mark.parametrize('form', ['exact', 'bf16', 'basic'])
+def test_poisoned_sample_is_isolated_other_arithmetic(form, monkeypatch):
+    """arithmetic = 'exact', precision = 'bf16' (config 3) and the bring-up implementation, which has no device status to report."""
+    m = _model_under(monkeypatch, 'h36m17_bn', {}, impl='basic' if form == 'basic' else 'fused')
+    if form == 'exact':
+        m.arithmetic = 'exact'
+    if form == 'bf16':
+        m.precision = 'bf16'
+    x = torch.from_numpy(synthetic.synthetic_pose2d(24, 17, seed=43))
+    for kind in KINDS:
+        _pair(m, 'h36m17_bn', x, 11, kind, form, reports=form != 'basic')
+    assert m.arithmetic == ('exact' if form == 'exact' else 'default')
+
+
+def test_poisoned_sample_is_isolated_in_subbatch_streams(monkeypatch):
+    m = _model_under(monkeypatch, 'coco19_alpha', {})
+    m.subbatch_streams = 2
+    x = torch.from_numpy(synthetic.synthetic_pose2d(160, 19, seed=44))
+    for p in (10, 150):                     # halves of 96 and 64 samples
+        for kind in ('nan1', 'nanall'):
+            _pair(m, 'coco19_alpha', x, p, kind, 'subbatch p=%d' % p)
+
+
+def test_poisoned_sample_is_isolated_in_graph_replay(monkeypatch):
+    """set_graph_replay: the same input and output tensors, so the poisoned forward is a replay of the graph the clean ones captured."""
+    m = _model_under(monkeypatch, 'h36m17_bn', {})
+    m.set_graph_replay(True)
+    B = 24
+    x = torch.from_numpy(synthetic.synthetic_pose2d(B, 17, seed=45))
+    xin = x.cuda()
+    out = (torch.empty(B, 6890, 3, device='cuda'), torch.empty(B, 17, 3, device='cuda'))
+    for kind in KINDS:
+        xin.copy_(x.cuda())
+        for _ in range(3):                  # first sight, capture, replay
+            m(xin, out=out)
+        torch.cuda.synchronize()
+        m.device_status()
+        clean = [t.clone() for t in out]
+        n = m.graph_launches()
+        xp = _poison(x, 7, kind)
+        xin.copy_(xp.cuda())
+        m(xin, out=out)
+        _read_report(m, True)
+        assert m.graph_launches() == n + 1
+        _assert_isolated(clean, out, 7, 'graph ' + kind)
+        _assert_poisoned_like_oracle('h36m17_bn', xp, 7, out[0], out[1], 'graph ' + kind)
+
+
+def test_poisoned_sample_is_isolated_in_joint_epilogue(monkeypatch):
+    """forward_joints (the vertex GEMM's joint-regression epilogue) and the per-sample joint_errors behind it."""
+    from oracle import gator_oracle as go
+    m = _model_under(monkeypatch, 'h36m17_bn', {})
+    jr = synthetic.load_j_regressors()['h36m']
+    m.set_joint_regressor(jr)
+    x = torch.from_numpy(synthetic.synthetic_pose2d(24, 17, seed=46))
+    gt = torch.from_numpy(np.random.RandomState(0).randn(24, 17, 3).astype(np.float32) * 300.0).cuda()
+
+    def fwd(t):
+        joints, pose3d, verts = m.forward_joints(t, with_verts=True)
+        return verts, pose3d, joints, geval.joint_errors(joints, gt, pred_scale=1000.0)
+    for kind in KINDS:
+        clean, bad = _pair(m, 'h36m17_bn', x, 9, kind, 'joints', fwd=fwd)
+        zz, c, sd = oracle_setup('h36m17_bn')
+        ref, _ = go.gator_forward(sd, c, _poison(x, 9, kind)[9:10], torch.float64)
+        rj = go.regress_joints(jr, ref)
+        assert torch.equal(torch.isfinite(bad[2][9]).cpu(), torch.isfinite(rj[0]))
+        assert not torch.isfinite(bad[3][9]).all()
+
+
+# ---- the heal policy and non-finite inputs ----------------------------------------------------------------------------------------
+
+def test_nonfinite_input_does_not_switch_the_arithmetic():
+    """One NaN keypoint under the default 'heal' policy: the NEXT forward of finite poses warns that an input was non-finite, keeps the
+    default arithmetic and returns its bit pattern (a fresh default module's on the same batch)."""
+    z, m = build_model('h36m17_bn', 'fused')
+    assert m.on_device_status == 'heal'
+    x = torch.from_numpy(synthetic.synthetic_pose2d(16, 17, seed=50))
+    m(_poison(x, 3, 'nan1').cuda())
+    torch.cuda.synchronize()
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter('always')
+        v, p = m(x.cuda())
+        torch.cuda.synchronize()
+    assert m.arithmetic == 'default'
+    assert any('non-finite input' in str(i.message) for i in w), [str(i.message) for i in w]
+    z, fresh = build_model('h36m17_bn', 'fused')
+    fv, fp = fresh(x.cuda())
+    assert torch.equal(v, fv) and torch.equal(p, fp)
+    m.device_status()
+
+
+def test_nonfinite_input_raises_its_own_reason():
+    z, m = build_model('coco19_alpha', 'fused')
+    m.on_device_status = 'raise'
+    x = torch.from_numpy(synthetic.synthetic_pose2d(16, 19, seed=51))
+    m(_poison(x, 15, 'inf1').cuda())
+    with pytest.raises(_lib.DeferredDeviceStatus) as ei:
+        m(x.cuda())
+    assert ei.value.reason == _lib.REASON_INPUT_NONFINITE != _lib.REASON_NONFINITE
+    assert 'non-finite input' in str(ei.value)
+    m.device_status()
+
+
+def test_range_violation_heals_next_to_a_nonfinite_input():
+    """A forward with both a NaN-input sample and weights that break the operand range (test_operand_range_violation_heals_by_itself):
+    the range violation wins, whatever the order of the reports, and the module heals."""
+    z, m = build_model('h36m17_bn', 'fused', device=None)
+    sd = m.state_dict()
+    key = 'pose2mesh.encoder_1.mlp.fc1.weight'
+    sd[key] = sd[key] * 3e4
+    m.load_state_dict(sd)
+    m = m.cuda()
+    x = torch.from_numpy(synthetic.synthetic_pose2d(16, 17, seed=5))
+    m(_poison(_poison(x, 0, 'nanall'), 15, 'nan1').cuda())      # one forward, three samples over the range, two with a NaN input
+    torch.cuda.synchronize()
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter('always')
+        v, _ = m(x.cuda())
+        torch.cuda.synchronize()
+    assert m.arithmetic == 'exact' and any('exact' in str(i.message) for i in w)
+    assert torch.isfinite(v).all()
+    m.device_status()
+
+
+class _CountingDist:
+    """One rank's collectives, counted (ShardedForward's dist surface)."""
+
+    def __init__(self):
+        self.calls = 0
+
+    def all_gather_into_tensor(self, out, inp):
+        self.calls += 1
+        out.copy_(inp.reshape(out.shape))
+
+    def all_reduce(self, t):
+        self.calls += 1
+
+
+def test_sharded_forward_keeps_its_collectives_and_arithmetic():
+    from gator_amd.parallel import ShardedForward
+    z, m = build_model('h36m17_bn', 'fused')
+    d = _CountingDist()
+    run = ShardedForward(m, 1, 0, d, always_gather=True)
+    x = torch.from_numpy(synthetic.synthetic_pose2d(32, 17, seed=52))
+    want, _ = m(x.cuda())
+    run.step(x.cuda())
+    run.wait()
+    n = d.calls
+    assert n > 0
+    run.step(_poison(x, 20, 'nan1').cuda())
+    run.wait()
+    with warnings.catch_warnings(record=True):
+        warnings.simplefilter('always')
+        v, _ = run.step(x.cuda())
+        run.wait()
+        torch.cuda.synchronize()
+    assert d.calls == 3 * n and m.arithmetic == 'default'
+    assert torch.equal(v, want)
+    m.device_status()
