@@ -28,7 +28,9 @@ int gator_t_unary(int op, const float* x, const int64_t* stride_x, float* out, c
                   float p0, float p1, gator_stream stream);
 
 /* out[kept dims] (+)= sum over the dims with reduce4[d] != 0; out is contiguous over the kept dims in order.  Fixed summation
- * order, double accumulators.  ws: device scratch of gator_t_reduce_ws_bytes() bytes (may be NULL when that is 0). */
+ * order, double accumulators.  ws: device scratch of gator_t_reduce_ws_bytes() bytes (may be NULL when that is 0).  That size is an
+ * upper bound for EVERY stride pattern of the shape (dense, transposed, stride 0, a row stride above the width): the call never
+ * touches a byte beyond it.  accumulate != 0 adds the sum to the prior contents of out in both forms, split or not. */
 int64_t gator_t_reduce_ws_bytes(const int64_t* shape4, const int32_t* reduce4);
 int gator_t_reduce_sum(const float* x, const int64_t* stride_x, const int64_t* shape4, const int32_t* reduce4, float* out,
                        int accumulate, void* ws, gator_stream stream);
@@ -37,7 +39,11 @@ int gator_t_reduce_sum(const float* x, const int64_t* stride_x, const int64_t* s
  * strides in elements: A (m, k), B (k, n), C (m, n), and per batch level for each operand (0 broadcasts).
  * ksplit > 1 (needs nb1 == nb2 == 1): K is cut into ksplit slices summed in slice order through ws (ksplit*(M*N+M) floats).
  * a_rowsum != NULL (unbatched only): also a_rowsum[m] = alpha * sum_k A[m][k] from the tiles already in LDS - the bias gradient
- * rides on its weight-gradient GEMM (A = dY^T) instead of a reduction pass of its own. */
+ * rides on its weight-gradient GEMM (A = dY^T) instead of a reduction pass of its own.  a_rowsum is OVERWRITTEN (accumulate applies to C
+ * only); with several column tiles every tile forms the same sums and the first one stores them.
+ * K = 0 is legal: C = bias (+ C if accumulate), a_rowsum = 0; A and B must still be non-NULL.  Slices of a split that start beyond K
+ * (the slice length is rounded up to 32) contribute zeros.  Rejected before any launch, with a message in gator_last_error(): a_rowsum
+ * or ksplit > 1 on a batched product, ksplit > 1 without ws, nb1 * nb2 > 65535, M or N <= 0, K < 0, a NULL A / B / C. */
 int gator_t_gemm(const float* A, const float* B, float* C, int M, int N, int K, const int64_t* stride_a2, const int64_t* stride_b2,
                  const int64_t* stride_c2, int nb1, int nb2, const int64_t* batch_a2, const int64_t* batch_b2,
                  const int64_t* batch_c2, const float* bias, float alpha, int accumulate, int ksplit, float* ws,
@@ -120,7 +126,10 @@ int gator_t_softmax_bwd(const float* p, const float* dp, int64_t rows, int n, fl
 /* dropout: keep[i] = philox4x32-7(seed, offset'; i) >= rate * 2^32; out = x * keep / (1 - rate); mask (uint8) is stored for
  * gator_t_mask_scale (the backward: out = x * mask * scale).  x == NULL writes the scaled mask itself (DropPath's per-sample factor).
  * offset' = offset + 2^32 * step_counter[0] when step_counter (a DEVICE uint64) is given: a step captured in a hipGraph draws new
- * masks on every replay.  gator_t_step_advance adds one to the counter (launch it once per step, inside the graph). */
+ * masks on every replay.  gator_t_step_advance adds one to the counter (launch it once per step, inside the graph).
+ * The stream, exactly: Philox4x32 of Salmon et al. (Random123) at 7 rounds; element i is output word i & 3 of the block with the 128-bit
+ * counter {lo32(i >> 2), hi32(i >> 2), lo32(offset'), hi32(offset')} and the key {lo32(seed), hi32(seed)}; the threshold is
+ * (uint32)((double)rate * 2^32) of the FLOAT rate, saturated at 0xffffffff (tests/train_refs.py restates it in numpy). */
 int gator_t_dropout(const float* x, int64_t n, float rate, uint64_t seed, uint64_t offset, const uint64_t* step_counter, float* out,
                     uint8_t* mask, gator_stream stream);
 int gator_t_step_advance(uint64_t* step_counter, gator_stream stream);
@@ -146,6 +155,8 @@ int gator_t_adam(float* param, const float* grad, float* exp_avg, float* exp_avg
  * inc_ptr [V+1] / inc_idx [3F]: for every vertex the list of (3*face + corner) entries it appears in (ascending), so the
  * gradient is GATHERED per vertex in a fixed order (no atomics, bit-reproducible).
  * Each writes loss_out[0] = weight * loss and, if grad != NULL, ACCUMULATES weight * d loss / d pred into grad (layout of pred).
+ * At the kinks the gradient is torch's: 0 where pred * valid == target * valid, where a cosine or a length residual is exactly 0.
+ * One difference, where torch itself yields NaN: an edge of length exactly 0 contributes the gradient 0 (torch: sqrt'(0) * 0).
  * ws: device scratch, gator_t_loss_ws_bytes(B, F) bytes. */
 int64_t gator_t_loss_ws_bytes(int64_t B, int64_t F);   /* also covers the coord loss of B*F*9 elements or fewer: pass F >= numel/(9B) */
 int gator_t_coord_loss(const float* pred, const float* target, const float* valid, const int64_t* stride_valid,

@@ -170,3 +170,139 @@ def test_gradient_slot_may_feed_only_one_slot_aware_op():
     ops.xw(x, W, 1)
     with pytest.raises(RuntimeError, match='two gradient-slot-aware ops'):
         ops.xw(x, W, 1)
+
+
+# ---- reductions: accumulate, inputs that are not plain, the workspace bound ----------------------------------------------------
+def _sum_case(name):
+    """(x CPU float32 view, dims): the shapes of test_sum plus strided / broadcast / degenerate inputs"""
+    rs = np.random.RandomState(sum(map(ord, name)))
+    r = lambda *s: torch.from_numpy(rs.randn(*s).astype(np.float32))
+    return {
+        'cols (5000,12)/0': lambda: (r(5000, 12), (0,)),
+        'cols unsplit (40,300)/0': lambda: (r(40, 300), (0,)),
+        'general (7,300,5)/1': lambda: (r(7, 300, 5), (1,)),
+        'general split (3,70000)/1': lambda: (r(3, 70000), (1,)),
+        'stride 0 reduced': lambda: (r(7, 1, 5).expand(7, 300, 5), (1,)),
+        'stride 0 kept': lambda: (r(7, 1, 5).expand(7, 300, 5), (0,)),
+        'transposed /1': lambda: (r(300, 7).t(), (1,)),
+        'transposed /0': lambda: (r(300, 7).t(), (0,)),
+        'narrowed cols ld > N': lambda: (r(5000, 20).narrow(1, 3, 12), (0,)),
+        'R = 1 cols': lambda: (r(1, 12), (0,)),
+        'R = 1 general': lambda: (r(5, 1, 7), (1,)),
+        'one output of 3e6': lambda: (r(1, 1, 1, 3_000_000), (3,)),
+        '(64,431,3)/(0,2)': lambda: (r(64, 431, 3), (0, 2)),
+        '(4096,64)/0': lambda: (r(4096, 64), (0,)),
+    }[name]()
+
+
+SUM_CASES = ['cols (5000,12)/0', 'cols unsplit (40,300)/0', 'general (7,300,5)/1', 'general split (3,70000)/1', 'stride 0 reduced', 'stride 0 kept', 'transposed /1', 'transposed /0',
+             'narrowed cols ld > N', 'R = 1 cols', 'R = 1 general', 'one output of 3e6', '(64,431,3)/(0,2)', '(4096,64)/0']
+
+
+def _to_device_view(x):
+    """the same values and strides on the device (expand / t / narrow are kept as views of a dense base)"""
+    base = torch.as_strided(x, (x.untyped_storage().size() // 4,), (1,), 0).cuda()          # the whole storage, flat
+    return torch.as_strided(base, x.shape, x.stride(), x.storage_offset())
+
+
+def _sum_check(name, got, x, dims, prior=None):
+    """1e-5 * max|ref| as test_sum; the 3e6-element sum is longer than anything that criterion was set on, so there the same sum in
+    torch-CPU float32 sets the noise: |ours - ref64| <= 4 |torch32 - ref64| + 2e-5 max|ref64|"""
+    ref = x.double().sum(dims, keepdim=True) + (prior.double() if prior is not None else 0)
+    err = float((got.cpu().double() - ref).abs().max())
+    scale = float(ref.abs().max())
+    if x.numel() // ref.numel() > 100000:
+        n32 = float(((x.contiguous().sum(dims, keepdim=True) + (prior if prior is not None else 0)).double() - ref).abs().max())
+        bound = 4 * n32 + 2e-5 * scale
+        print('sum %s: |ours - ref64| %.3e  |torch32 - ref64| %.3e  floor %.3e' % (name, err, n32, 2e-5 * scale))
+    else:
+        bound = 1e-5 * scale
+    assert tuple(got.shape) == tuple(ref.shape) and err <= bound, (name, err, bound)
+
+
+@pytest.mark.parametrize('name', SUM_CASES)
+def test_raw_sum_on_views_and_with_accumulate(name):
+    x, dims = _sum_case(name)
+    xd = _to_device_view(x)
+    assert xd.stride() == x.stride()
+    _sum_check(name, ops.raw_sum(xd, dims, keepdim=True), x, dims)
+    kept = [1 if i in dims else n for i, n in enumerate(x.shape)]
+    prior = torch.from_numpy(np.random.RandomState(1).randn(*kept).astype(np.float32)) * float(x.double().sum(dims).abs().max())
+    out = prior.cuda()
+    got = ops.raw_sum(xd, dims, keepdim=True, out=out, accumulate=True)
+    assert got.data_ptr() == out.data_ptr()
+    _sum_check(name + ' accumulate', got, x, dims, prior)
+
+
+@pytest.mark.parametrize('name', SUM_CASES)
+def test_reduce_workspace_stays_below_the_promised_bound(name):
+    """gator_t_reduce_ws_bytes promises an upper bound without knowing the strides.  The call gets n_out * 1024 * 8 bytes (nsplit <= 1024:
+    the most any plan can use) filled with a byte pattern; every byte beyond the promised size must still hold it."""
+    import ctypes
+    from gator_amd import _lib
+    I64x4, I32x4 = ctypes.c_int64 * 4, ctypes.c_int32 * 4
+    x, dims = _sum_case(name)
+    xd = _to_device_view(x)
+    pad = 4 - x.dim()
+    n4, s4 = [1] * pad + list(x.shape), [0] * pad + list(x.stride())
+    red = [1 if (i - pad) in dims else 0 for i in range(4)]
+    n_out = int(np.prod([n for n, r in zip(n4, red) if not r]))
+    lib = _lib.load()
+    bound = int(lib.gator_t_reduce_ws_bytes(I64x4(*n4), I32x4(*red)))
+    assert 0 < bound <= n_out * 1024 * 8 and bound % 8 == 0
+    ws = torch.full((n_out * 1024 * 8,), 0xA5, dtype=torch.uint8, device='cuda')
+    out = torch.empty([1 if r else n for n, r in zip(n4, red)], device='cuda')
+    _lib.check(lib.gator_t_reduce_sum(xd.data_ptr(), I64x4(*s4), I64x4(*n4), I32x4(*red), out.data_ptr(), 0, ws.data_ptr(),
+                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'gator_t_reduce_sum')
+    torch.cuda.synchronize()
+    assert bool((ws[bound:] == 0xA5).all()), name
+    _sum_check(name, out.reshape([1 if i in dims else n for i, n in enumerate(x.shape)]), x, dims)
+    if name == 'cols (5000,12)/0':
+        # the check sees real writes: here the column form's nsplit and the bound's follow the same rule (R / (2 nsplit) >= 32: 128 slices)
+        assert bound == 12 * 128 * 8 and not bool((ws[bound - 8:bound] == 0xA5).all())
+
+
+# ---- elementwise: the vectorised path's tail and the misaligned operands that must leave it -------------------------------------
+@pytest.mark.parametrize('n', [1, 2, 3, 5, 4099])
+@pytest.mark.parametrize('shift', [(0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1)])
+def test_elementwise_tails_and_misaligned_operands(n, shift):
+    """t.view(-1)[1:] of a float tensor is dense but 4 bytes off a 16-byte boundary"""
+    rs = np.random.RandomState(n)
+    a, b = rs.randn(n).astype(np.float32), rs.randn(n).astype(np.float32)
+
+    def dev(v, off):
+        t = torch.zeros(n + 8, device='cuda')
+        assert t.data_ptr() % 16 == 0
+        t[off:off + n] = torch.from_numpy(v).cuda()
+        return t, t[off:off + n]
+
+    (ta, ad), (tb, bd) = dev(a, shift[0]), dev(b, shift[1])
+    for op, fn in ((ops.ADD, np.add), (ops.MUL, np.multiply)):
+        to, od = dev(np.zeros(n, np.float32), shift[2])
+        ops.raw_binary(op, ad, bd, out=od)
+        want = fn(a.astype(np.float64), b.astype(np.float64))
+        assert np.abs(od.cpu().numpy() - want).max() <= 2e-5 * np.abs(want).max()
+        assert float(to[:shift[2]].abs().sum()) == 0.0 and float(to[shift[2] + n:].abs().sum()) == 0.0       # nothing outside the n elements
+    to, od = dev(np.zeros(n, np.float32), shift[2])
+    ops.raw_unary(ops.U_AFFINE, ad, 2.0, 1.0, out=od)
+    assert np.array_equal(od.cpu().numpy(), 2.0 * a + 1.0) and float(to[:shift[2]].abs().sum()) == 0.0 and float(to[shift[2] + n:].abs().sum()) == 0.0
+    if shift == (0, 0, 0):
+        x, y = [torch.from_numpy(v).cuda().requires_grad_(True) for v in (a, b)]
+        gx, gy = torch.autograd.grad(ops.add(ops.mul(x, y), y), [x, y], grad_outputs=torch.ones(n, device='cuda'))
+        assert np.array_equal(gx.cpu().numpy(), b) and np.array_equal(gy.cpu().numpy(), a + 1.0)
+
+
+def test_unary_dgelu_sign_and_greater_than():
+    """ops 2 (gelu'), 8 (sign) and 11 (x > p0) are reached only from backward passes: directly against float64"""
+    rs = np.random.RandomState(3)
+    x = np.concatenate([rs.randn(4099) * 3, [0.0, -0.0, 1e-30, -1e-30, 0.5, -0.5, 8.0, -8.0]]).astype(np.float32)
+    xd = torch.from_numpy(x).cuda()
+    x64 = torch.from_numpy(x).double().requires_grad_(True)
+    dg, = torch.autograd.grad(F.gelu(x64).sum(), x64)
+    got = ops.raw_unary(ops.U_DGELU, xd).cpu().double()
+    assert float((got - dg).abs().max()) <= 2e-5 * float(dg.abs().max())
+    assert np.array_equal(ops.raw_unary(ops.U_SIGN, xd).cpu().numpy(), np.sign(x))
+    for p0 in (0.0, 0.5, -8.0, float('inf')):
+        assert np.array_equal(ops.raw_unary(ops.U_GT, xd, p0).cpu().numpy(), (x > np.float32(p0)).astype(np.float32))
+    xs = xd[1:]                                                    # the strided (misaligned) kernel gives the same answers
+    assert np.array_equal(ops.raw_unary(ops.U_SIGN, xs).cpu().numpy(), np.sign(x[1:]))

@@ -50,3 +50,35 @@ def test_parameter_buffer_split_and_rates():
     r = M.Rates()
     assert r.gat_path[0] == 0.0 and abs(r.gat_path[-1] - 0.2) < 1e-12 and r.gat_attn == 0.4 and r.mdr_self == 0.1
     assert M.Rates(0.0).gat_attn == 0.0
+
+
+def test_philox_reference_reproduces_the_random123_known_answers():
+    """The numpy Philox4x32 of tests/train_refs.py at 10 rounds against the known-answer vectors published with Random123
+    (kat_vectors, philox4x32 10): the mask reference of the GPU dropout tests is independent of the code under test."""
+    from tests.train_refs import philox4x32
+    kat = [((0, 0, 0, 0), (0, 0), (0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8)),
+           ((0xffffffff,) * 4, (0xffffffff,) * 2, (0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd)),
+           ((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344), (0xa4093822, 0x299f31d0), (0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1))]
+    for ctr, key, want in kat:
+        assert tuple(int(w) for w in philox4x32([ctr], [key], 10)[0]) == want
+    got = philox4x32([k[0] for k in kat], [k[1] for k in kat], 10)         # rows are independent blocks
+    assert [tuple(int(w) for w in r) for r in got] == [k[2] for k in kat]
+    assert not np.array_equal(philox4x32([kat[2][0]], [kat[2][1]], 7), got[2:])
+
+
+def test_keep_mask_reference_statistics_at_the_device_round_count():
+    from tests.train_refs import DEVICE_ROUNDS, keep_mask, keep_threshold
+    assert DEVICE_ROUNDS == 7
+    n = 1 << 18
+    masks = {}
+    for rate in (0.1, 0.4):
+        m = masks[rate] = keep_mask(123, 1, n, rate)
+        assert m.dtype == np.uint8 and m.shape == (n,) and set(np.unique(m)) <= {0, 1}
+        assert abs(float(m.mean()) - (1.0 - rate)) < 0.01
+    a, b = masks[0.4].astype(np.float64), keep_mask(123, 2, n, 0.4).astype(np.float64)
+    assert abs(float(np.corrcoef(a, b)[0, 1])) < 0.01
+    # the counter layout: a prefix of a longer mask, the step in the high word of the offset, the saturated threshold
+    assert np.array_equal(keep_mask(123, 1, 5, 0.4), masks[0.4][:5])
+    assert np.array_equal(keep_mask(123, 1, 64, 0.4, step=3), keep_mask(123, 1 + (3 << 32), 64, 0.4))
+    assert not np.array_equal(keep_mask(123, 1, 64, 0.4, step=3), masks[0.4][:64])
+    assert keep_threshold(0.0) == 0 and keep_threshold(0.5) == 1 << 31 and keep_threshold(0.99999999999) == 0xffffffff
