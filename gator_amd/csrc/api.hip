@@ -188,13 +188,12 @@ extern "C" int gator_abi_version(void) { return GATOR_ABI_VERSION; }
 
 static void prof_clear(gator_ctx* c, bool destroy);
 
+gator_ctx::~gator_ctx() {
+    fused_destroy(this);
+    prof_clear(this, true);
+}
+
 extern "C" int gator_destroy(gator_ctx* c) {
-    if (!c) return GATOR_OK;
-    fused_destroy(c);
-    prof_clear(c, true);
-    if (c->ws) (void)hipFree(c->ws);
-    if (c->arena) (void)hipFree(c->arena);
-    if (c->status_host) (void)hipHostFree(c->status_host);
     delete c;
     return GATOR_OK;
 }
@@ -228,13 +227,11 @@ extern "C" int gator_create(const gator_tensor* tensors, int32_t n, const gator_
     c->prefix_mdr = both ? "pose2mesh." : "";
     (void)hipGetDevice(&c->device);
     {   // sticky device status word: pinned, device-visible host memory (no synchronisation needed to read it)
-        void *hp = nullptr, *dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
-            if (hp) (void)hipHostFree(hp);
+        void* dp = nullptr;
+        if (c->status_host.alloc(64) != GATOR_OK || hipHostGetDevicePointer(&dp, c->status_host, 0) != hipSuccess) {
             delete c;
             return fail(GATOR_ENOMEM, "gator_create: hipHostMalloc of the status word failed");
         }
-        c->status_host = (unsigned*)hp;
         c->status_dev = (unsigned*)dp;
         for (int r = 0; r < DEV_REASONS; ++r) c->status_host[r] = 0u;
     }
@@ -250,7 +247,7 @@ extern "C" int gator_create(const gator_tensor* tensors, int32_t n, const gator_
     const int J = c->J;
     const size_t folded = ((size_t)kH * J * J + kDepth * J + (size_t)kDepth * J * J + 2 * J * J + (size_t)J * kC) * sizeof(float) + 6 * 256;
     c->arena_bytes = total + folded;
-    if (hipMalloc(&c->arena, c->arena_bytes) != hipSuccess) { delete c; return fail(GATOR_ENOMEM, "gator_create: hipMalloc(%zu) failed", c->arena_bytes); }
+    if (c->arena.alloc(c->arena_bytes) != GATOR_OK) { delete c; return fail(GATOR_ENOMEM, "gator_create: hipMalloc(%zu) failed", c->arena_bytes); }
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
         const gator_tensor& t = tensors[i];
@@ -263,7 +260,7 @@ extern "C" int gator_create(const gator_tensor* tensors, int32_t n, const gator_
         r.data = c->arena + off;
         if (bytes) {
             hipError_t e = hipMemcpy(c->arena + off, t.data, bytes, t.is_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice);
-            if (e != hipSuccess) { int rc = fail(GATOR_EHIP, "gator_create: copying '%s' failed: %s", t.name, hipGetErrorString(e)); gator_destroy(c); return rc; }
+            if (e != hipSuccess) { delete c; return fail(GATOR_EHIP, "gator_create: copying '%s' failed: %s", t.name, hipGetErrorString(e)); }
         }
         off += (bytes + 255) & ~(size_t)255;
         c->t[t.name] = r;
@@ -277,14 +274,14 @@ extern "C" int gator_create(const gator_tensor* tensors, int32_t n, const gator_
     c->pos_embed = carve((size_t)J * kC);
     if (c->parts & GATOR_PART_GAT) {
         auto it = c->t.find("const.edge_input");
-        if (it == c->t.end() || it->second.ndim != 3) { gator_destroy(c); return fail(GATOR_EMISSING, "gator_create: 'const.edge_input' [J,J,D] missing"); }
+        if (it == c->t.end() || it->second.ndim != 3) { delete c; return fail(GATOR_EMISSING, "gator_create: 'const.edge_input' [J,J,D] missing"); }
         c->D = (int)it->second.shape[2];
     }
     int rc = resolve_weights(c);
     if (rc == GATOR_OK && (c->parts & GATOR_PART_GAT)) rc = basic_fold_constants(c, nullptr);
     if (rc == GATOR_OK && cfg->max_batch > 0 && c->impl == GATOR_IMPL_BASIC) rc = ensure_workspace(c, cfg->max_batch);
     if (rc == GATOR_OK) rc = fused_create(c, nullptr);
-    if (rc != GATOR_OK) { gator_destroy(c); return rc; }
+    if (rc != GATOR_OK) { delete c; return rc; }
     *out = c;
     return GATOR_OK;
 }

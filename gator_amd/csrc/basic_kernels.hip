@@ -401,14 +401,8 @@ BasicLayout basic_layout(int J, int B) {
 
 int ensure_workspace(gator_ctx* c, int B) {
     if (B <= c->cap_batch && c->ws) return GATOR_OK;
-    if (c->ws) {
-        GATOR_HIP_CHECK(hipDeviceSynchronize());
-        GATOR_HIP_CHECK(hipFree(c->ws));
-        c->ws = nullptr;
-    }
-    const size_t n = basic_layout(c->J, B).total;
-    GATOR_HIP_CHECK(hipMalloc(&c->ws, n * sizeof(float)));
-    c->ws_floats = n;
+    if (c->ws) GATOR_HIP_CHECK(hipDeviceSynchronize());
+    GATOR_TRY(c->ws.alloc(basic_layout(c->J, B).total * sizeof(float)));
     c->cap_batch = B;
     return GATOR_OK;
 }
@@ -418,9 +412,9 @@ int basic_fold_constants(gator_ctx* c, void* stream) {
     const int J = c->J, D = c->D;
     const Weights& w = c->w;
     // edge encoder: ea[d][h*J*J + ij] = Linear(J^2 -> 8J^2)(edge_input[:, :, d])      modules.py:100-101
-    float *eaT = nullptr, *ea = nullptr;
-    GATOR_HIP_CHECK(hipMalloc(&eaT, (size_t)D * J * J * sizeof(float)));
-    GATOR_HIP_CHECK(hipMalloc(&ea, (size_t)D * kH * J * J * sizeof(float)));
+    DevBuf<float> eaT, ea;
+    GATOR_TRY(eaT.alloc((size_t)D * J * J * sizeof(float)));
+    GATOR_TRY(ea.alloc((size_t)D * kH * J * J * sizeof(float)));
     std::vector<float> h_ei((size_t)J * J * D), h_t((size_t)D * J * J);
     GATOR_HIP_CHECK(hipMemcpy(h_ei.data(), w.edge_input, h_ei.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (int ij = 0; ij < J * J; ++ij)
@@ -434,8 +428,8 @@ int basic_fold_constants(gator_ctx* c, void* stream) {
     k_fold_graph<<<1, 256, 0, st>>>(w.graph_adj, nullptr, w.sp, w.pos_id, w.pos_num, c->adj_diag, c->adj_off, c->mask1,
                                     c->mask2, c->pos_embed, J, -1);
     GATOR_HIP_CHECK(hipStreamSynchronize(st));
-    GATOR_HIP_CHECK(hipFree(eaT));
-    GATOR_HIP_CHECK(hipFree(ea));
+    eaT.reset();
+    ea.reset();
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;
 }

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "fused_state.h"
@@ -21,42 +22,45 @@ static void graphs_clear(FusedState* f) {
     for (auto& g : f->graphs) graph_slot_free(g);
     f->graphs.clear();
 }
-// The launchers read the workspace through the FusedWs base of FusedState; a scope loads set `i` into it and stores it back
-// (possibly re-allocated) on exit.  Set 0 is the normal workspace, set 1 the second half-batch in sub-batch mode.
+// The launchers read the workspace through FusedState::ws; a scope points it at set `i` and restores the previous set on exit.
 struct WsScope {
-    FusedState* f; int i;
-    WsScope(FusedState* f_, int i_) : f(f_), i(i_) { static_cast<FusedWs&>(*f) = f->sets[i]; }
-    ~WsScope() { f->sets[i] = static_cast<FusedWs&>(*f); }
+    FusedState* f; FusedWs* prev;
+    WsScope(FusedState* f_, int i) : f(f_), prev(f_->ws) { f->ws = &f->sets[i]; }
+    ~WsScope() { f->ws = prev; }
 };
 
+// (Re-)allocates the set in use for a batch of B: one block, zeroed once, carved into its regions.
 int fused_ensure_ws(gator_ctx* c, int B) {
     FusedState* f = c->fused;
-    if (f->ws && B <= f->cap) return GATOR_OK;
-    if (f->ws) {
+    FusedWs& w = *f->ws;
+    if (w.base && B <= w.cap) return GATOR_OK;
+    if (w.base) {
         GATOR_HIP_CHECK(hipDeviceSynchronize());
         graphs_clear(f);                                 // captured forwards hold pointers into the old workspace
-        GATOR_HIP_CHECK(hipFree(f->ws));
-        f->ws = nullptr;
     }
     const int cap = B, MT = (cap + 31) / 32, J = c->J;
     const size_t tiles = (size_t)cap * kVT * 2 * kTile;
+    // The layout, every region once and in block order: without a block it only adds the sizes up, with one it also points the members into it.
     size_t n = 0;
-    auto take = [&](size_t k) { size_t o = n; n += (k + 63) & ~(size_t)63; return o; };
-    const size_t o_vcp = take((size_t)MT * 3 * kCB * kTile), o_vc = take((size_t)cap * kV * 3), o_vf = take(3 * tiles),
-                 o_q = take(9 * tiles / 2), o_k = take(9 * tiles / 2), o_v = take(9 * tiles / 2) /* THREE tile sets each (k_mdr_persist writes every set once per forward); q/k/v sized for X3 tiles (1.5x) */, o_jkv = take((size_t)cap * 12 * kTile),
-                 o_hf = take((size_t)cap * kV * 32), o_lbf = take((size_t)cap * kV * kE), o_feat = take((size_t)cap * J * kC),
-                 o_xout = take((size_t)cap * J * 3), o_pc = take((size_t)cap * J * 133),
-                 o_vcp3 = take(std::max(upsample_x3_vcp_elems(cap), upsample_x2_vcp_elems(cap)) / 2), o_lpart = take(gat_tail_part_floats(cap, J)), o_ctr = take(mdr_ctr_words(cap)), o_hpart = take((size_t)cap * kVT * 128);
-    GATOR_HIP_CHECK(hipMalloc(&f->ws, n * sizeof(float)));
-    GATOR_HIP_CHECK(hipMemset(f->ws, 0, n * sizeof(float)));
+    auto layout = [&](float* block) {
+        n = 0;
+        auto region = [&](auto*& member, size_t floats) {      // (64-float aligned offsets: 8-byte alignment of hpart's doubles holds)
+            if (block) member = reinterpret_cast<std::remove_reference_t<decltype(member)>>(block + n);
+            n += (floats + 63) & ~(size_t)63;
+        };
+        region(w.vcp, (size_t)MT * 3 * kCB * kTile); region(w.vc, (size_t)cap * kV * 3);
+        // THREE tile sets each (k_mdr_persist writes every set once per forward); q/k/v sized for X3 tiles (1.5x)
+        region(w.vf, 3 * tiles); region(w.q, 9 * tiles / 2); region(w.k, 9 * tiles / 2); region(w.v, 9 * tiles / 2);
+        region(w.jkv, (size_t)cap * 12 * kTile); region(w.hf, (size_t)cap * kV * 32); region(w.lbf, (size_t)cap * kV * kE);
+        region(w.feat, (size_t)cap * J * kC); region(w.vcp3, std::max(upsample_x3_vcp_elems(cap), upsample_x2_vcp_elems(cap)) / 2);
+        region(w.lpart, gat_tail_part_floats(cap, J)); region(w.mdr_ctr, mdr_ctr_words(cap)); region(w.hpart, (size_t)cap * kVT * 128);
+    };
+    layout(nullptr);
+    GATOR_TRY(w.base.alloc(n * sizeof(float)));
+    GATOR_HIP_CHECK(hipMemset(w.base, 0, n * sizeof(float)));
     GATOR_HIP_CHECK(hipDeviceSynchronize());      // the memset runs on the null stream; a non-blocking stream would not wait for it
-    f->ws_floats = n;
-    f->cap = cap;
-    f->vcp = f->ws + o_vcp; f->vc = f->ws + o_vc; f->vf = f->ws + o_vf; f->q = f->ws + o_q; f->k = f->ws + o_k;
-    f->v = f->ws + o_v; f->jkv = f->ws + o_jkv; f->hf = f->ws + o_hf; f->lbf = f->ws + o_lbf; f->feat = f->ws + o_feat;
-    f->xout = f->ws + o_xout; f->pc = f->ws + o_pc; f->vcp3 = f->ws + o_vcp3; f->lpart = f->ws + o_lpart;
-    f->mdr_ctr = reinterpret_cast<unsigned*>(f->ws + o_ctr);
-    f->hpart = f->ws + o_hpart;      // (64-float aligned offsets: 8-byte alignment of the doubles holds)
+    w.cap = cap;
+    layout(w.base);
     return GATOR_OK;
 }
 
@@ -186,12 +190,24 @@ float c3_logit_bound(const Weights& w) {
     return (float)worst;
 }
 
+// Packs each linear into the tiles at p, one after the other, and stores where it went.
+struct PackItem { const float* src; int64_t wsn, wsk; int N, K; const float** dst; };
+template <size_t n>
+int pack_linears(const PackItem (&items)[n], float*& p, void* stream) {
+    for (const PackItem& it : items) {
+        GATOR_TRY(fused_pack_linear(it.src, it.wsn, it.wsk, it.N, it.K, p, stream));
+        *it.dst = p;
+        p += (size_t)nblk32(it.N) * nblk32(it.K) * kTile;
+    }
+    return GATOR_OK;
+}
+
 int fused_create_gat(gator_ctx* c, FusedState* f, void* stream) {
     const Weights& w = c->w;
     const int J = c->J;
     const size_t blk_tiles = 48 + 16 + 16 + 16 + 16 + 4 + 20 + 64 + 64 + 4 + 4 + 1 + 1;     // 274
     const size_t total = (kDepth * blk_tiles + 8 + 2 + 8 + 4 + 12) * kTile;
-    GATOR_HIP_CHECK(hipMalloc(&f->gbuf, total * sizeof(float)));
+    GATOR_TRY(f->gbuf.alloc(total * sizeof(float)));
     float* p = f->gbuf;
     auto take = [&](size_t tiles) { float* r = p; p += tiles * kTile; return r; };
     std::vector<float> host;
@@ -205,17 +221,12 @@ int fused_create_gat(gator_ctx* c, FusedState* f, void* stream) {
     for (int i = 0; i < kDepth; ++i) {
         const GatBlockW& r = w.blk[i];
         GatBlockPk& q = f->gblk[i];
-        struct { const float* src; int64_t wsn, wsk; int N, K; const float** dst; } items[] = {
+        const PackItem items[] = {
             {r.qkv_w, 128, 1, 384, 128, &q.qkv}, {r.proj_w, 128, 1, 128, 128, &q.proj},
             {r.gcn_W, 1, 128, 128, 128, &q.w0}, {r.gcn_W + 128 * 128, 1, 128, 128, 128, &q.w1},     // applied as x @ W (modules.py:244-245)
             {r.xl0_w, 128, 1, 128, 128, &q.lin0}, {r.xl1_w, 128, 1, 16, 128, &q.lin1}, {r.xlb_w, 144, 1, 128, 144, &q.back},
             {r.fc1_w, 128, 1, 512, 128, &q.fc1}, {r.fc2_w, 512, 1, 128, 512, &q.fc2}};
-        for (auto& it : items) {
-            float* dst = take((size_t)nblk32(it.N) * nblk32(it.K));
-            int rc = fused_pack_linear(it.src, it.wsn, it.wsk, it.N, it.K, dst, stream);
-            if (rc) return rc;
-            *it.dst = dst;
-        }
+        GATOR_TRY(pack_linears(items, p, stream));
         const std::vector<float> M = d2h(r.gcn_M, (size_t)J * kC), b1 = d2h(r.xl1_b, 16);
         // C-layout tiles (channel on the lane, token in the register): tile[nb][g][lane][j] <-> token 8g+4h+j, channel 32nb+(lane&31)
         std::vector<float> mc(4 * kTile), md(4 * kTile);
@@ -244,12 +255,12 @@ int fused_create_gat(gator_ctx* c, FusedState* f, void* stream) {
     }
     if (f->opt.gat_x3) {   // split-precision image of every block's weight grids (the tables mc/md/aoffT/f1b in between are converted too, unused)
         const int64_t ntiles = (p - f->gblk[0].qkv) / kTile;
-        GATOR_HIP_CHECK(hipMalloc(&f->gxbuf, (size_t)ntiles * kTileX3 * sizeof(float)));
+        GATOR_TRY(f->gxbuf.alloc((size_t)ntiles * kTileX3 * sizeof(float)));
         int rc = fused_repack_x3(f->gblk[0].qkv, f->gxbuf, ntiles, stream);
         if (rc) return rc;
         if (f->opt.gat_tiled_h4) {
             float left = 0.f;
-            GATOR_HIP_CHECK(hipMalloc(&f->gxbuf_h3, (size_t)ntiles * kTileX3 * sizeof(float)));
+            GATOR_TRY(f->gxbuf_h3.alloc((size_t)ntiles * kTileX3 * sizeof(float)));
             // the scale comes from the nine weight grids of each block (264 tiles), not from the mc / mdT / aoffT / f1b tables behind them
             rc = fused_repack_h3(f->gblk[0].qkv, f->gxbuf_h3, ntiles, &f->gat_tiled_wshift, &left, stream, (int64_t)blk_tiles, 264);
             if (rc == GATOR_OK && left > 1e-7f) rc = fail(GATOR_EUNSUPPORTED, "GAT weights span more than fp16 x 3 planes hold exactly: use GATOR_GAT_TILED_H4=0");
@@ -334,19 +345,18 @@ int fused_create(gator_ctx* c, void* stream) {
     }
     const size_t n_up = f->opt.up_x3 == 0 ? (size_t)3 * kOB * kCB * kTile : 0, n_layer = (size_t)64 * kTile;
     const size_t total = n_up + 3 * n_layer + 24 * kTile + 64 + (size_t)kVT * 2 * kTile + 3 * 64 + 1024;
-    GATOR_HIP_CHECK(hipMalloc(&f->wbuf, total * sizeof(float)));
-    f->wbuf_floats = total;
+    GATOR_TRY(f->wbuf.alloc(total * sizeof(float)));
     float* p = f->wbuf;
     auto take = [&](size_t k) { float* r = p; p += k; return r; };
     // upsample_conv.weight [6890][431][3] -> one packed [216][14] tile grid per tap
     float* up = take(n_up);
     if (f->opt.up_x3 == 2) {
-        GATOR_HIP_CHECK(hipMalloc(&f->up_w2, upsample_x2_weight_elems() * 2));
+        GATOR_TRY(f->up_w2.alloc(upsample_x2_weight_elems() * 2));
         int rc = pack_upsample_x2(w.up_w, f->up_w2, &f->up_w2_unscale, stream);
         if (rc == GATOR_OK) rc = upsample_x2_prepare_device();
         if (rc) return rc;
     } else if (f->opt.up_x3 == 1) {
-        GATOR_HIP_CHECK(hipMalloc(&f->up_w3, upsample_x3_weight_elems() * 2));
+        GATOR_TRY(f->up_w3.alloc(upsample_x3_weight_elems() * 2));
         int rc = pack_upsample_x3(w.up_w, f->up_w3, stream);
         if (rc) return rc;
     } else {
@@ -359,15 +369,11 @@ int fused_create(gator_ctx* c, void* stream) {
     for (int li = 0; li < 3; ++li) {
         const MdrLayerW& r = w.lay[li];
         MdrLayerP& q = f->lay[li];
-        struct { const float* src; int N, K; const float** dst; } items[] = {
-            {r.wq, 64, 64, &q.wq}, {r.wk, 64, 64, &q.wk}, {r.wv, 64, 64, &q.wv}, {r.proj_w, 64, 64, &q.proj}, {r.fc1_w, 256, 64, &q.fc1}, {r.fc2_w, 64, 256, &q.fc2},
-            {r.sa_w[0], 64, 64, &q.sa[0]}, {r.sa_w[1], 64, 64, &q.sa[1]}, {r.sa_w[2], 64, 64, &q.sa[2]}, {r.sa_w[3], 64, 64, &q.sa[3]}};
-        for (auto& it : items) {
-            float* dst = take((size_t)nblk32(it.N) * nblk32(it.K) * kTile);
-            int rc = fused_pack_linear(it.src, it.K, 1, it.N, it.K, dst, stream);
-            if (rc) return rc;
-            *it.dst = dst;
-        }
+        const PackItem items[] = {      // (row-major [N][K] weights)
+            {r.wq, 64, 1, 64, 64, &q.wq}, {r.wk, 64, 1, 64, 64, &q.wk}, {r.wv, 64, 1, 64, 64, &q.wv}, {r.proj_w, 64, 1, 64, 64, &q.proj},
+            {r.fc1_w, 64, 1, 256, 64, &q.fc1}, {r.fc2_w, 256, 1, 64, 256, &q.fc2},
+            {r.sa_w[0], 64, 1, 64, 64, &q.sa[0]}, {r.sa_w[1], 64, 1, 64, 64, &q.sa[1]}, {r.sa_w[2], 64, 1, 64, 64, &q.sa[2]}, {r.sa_w[3], 64, 1, 64, 64, &q.sa[3]}};
+        GATOR_TRY(pack_linears(items, p, stream));
     }
     // head: one 32-row linear. rows 0..19 motion_linear[0..19] (mat_A), 24..26 bias_linear, 27 scale_linear (alpha head),
     // 28..30 motion_linear[20..22] (mat_C)   -- MDR.py:156-162
@@ -384,18 +390,18 @@ int fused_create(gator_ctx* c, void* stream) {
             std::copy(sw.begin(), sw.end(), hw.begin() + 27 * 64);
             hb[27] = sb[0];
         }
-        float* tmp = nullptr;
-        GATOR_HIP_CHECK(hipMalloc(&tmp, hw.size() * sizeof(float)));
+        DevBuf<float> tmp;
+        GATOR_TRY(tmp.alloc(hw.size() * sizeof(float)));
         GATOR_HIP_CHECK(hipMemcpy(tmp, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice));
         float* dst = take(2 * kTile);
         int rc = fused_pack_linear(tmp, 64, 1, 32, 64, dst, stream);
         GATOR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-        GATOR_HIP_CHECK(hipFree(tmp));
+        tmp.reset();
         if (rc) return rc;
         f->head_w = dst;
         if (f->opt.mdr_x3) {     // split-precision image of the three layers' tile grids and the head tiles (contiguous in wbuf)
             const int64_t ntiles = (dst + 2 * kTile - f->lay[0].wq) / kTile;
-            GATOR_HIP_CHECK(hipMalloc(&f->wxbuf, (size_t)ntiles * kTileX3 * sizeof(float)));
+            GATOR_TRY(f->wxbuf.alloc((size_t)ntiles * kTileX3 * sizeof(float)));
             if (f->opt.mdr_x3 == 2) {     // three fp16 planes under one power-of-two scale (x3_common.h: the 4-product linears)
                 float left = 0.f;
                 rc = fused_repack_h3(f->lay[0].wq, f->wxbuf, ntiles, &f->mdr_wshift, &left, stream);
@@ -420,9 +426,9 @@ int fused_create(gator_ctx* c, void* stream) {
         f->jfeat128_p = d128;
         if (f->opt.mdr_x3 == 2) {      // the same eight tiles as three fp16 planes under their own power-of-two scale (k_gat8's fused tail, gat_roles.hip)
             float left = 0.f;
-            GATOR_HIP_CHECK(hipMalloc(&f->jf128_h3, (size_t)8 * kTileX3 * sizeof(float)));
+            GATOR_TRY(f->jf128_h3.alloc((size_t)8 * kTileX3 * sizeof(float)));
             rc = fused_repack_h3(d128, f->jf128_h3, 8, &f->jf128_wshift, &left, stream);
-            if (rc == GATOR_OK && left > 1e-7f) { (void)hipFree(f->jf128_h3); f->jf128_h3 = nullptr; f->opt.gat8_tail = false; }      // (the two tail launches stay)
+            if (rc == GATOR_OK && left > 1e-7f) { f->jf128_h3.reset(); f->opt.gat8_tail = false; }      // (the two tail launches stay)
             if (rc) return rc;
         }
         const std::vector<float> jw = d2h(w.jfeat_w, 64 * 133);
@@ -468,31 +474,16 @@ int fused_create(gator_ctx* c, void* stream) {
     return GATOR_OK;
 }
 
+FusedState::~FusedState() {
+    for (FusedWs& w : sets) { w.base.reset(); w.vcp16.reset(); }
+    graphs_clear(this);
+    if (cap_stream) (void)hipStreamDestroy((hipStream_t)cap_stream);
+    if (aux_stream) (void)hipStreamDestroy((hipStream_t)aux_stream);
+    if (ev_fork) (void)hipEventDestroy((hipEvent_t)ev_fork);
+    if (ev_join) (void)hipEventDestroy((hipEvent_t)ev_join);
+}
+
 void fused_destroy(gator_ctx* c) {
-    if (!c->fused) return;
-    for (int i = 0; i < 2; ++i) {       // the FusedWs base of FusedState is only a view of one of the sets
-        if (c->fused->sets[i].ws) (void)hipFree(c->fused->sets[i].ws);
-        if (c->fused->sets[i].vcp16) (void)hipFree(c->fused->sets[i].vcp16);
-    }
-    graphs_clear(c->fused);
-    if (c->fused->cap_stream) (void)hipStreamDestroy((hipStream_t)c->fused->cap_stream);
-    if (c->fused->aux_stream) (void)hipStreamDestroy((hipStream_t)c->fused->aux_stream);
-    if (c->fused->ev_fork) (void)hipEventDestroy((hipEvent_t)c->fused->ev_fork);
-    if (c->fused->ev_join) (void)hipEventDestroy((hipEvent_t)c->fused->ev_join);
-    if (c->fused->wbuf) (void)hipFree(c->fused->wbuf);
-    if (c->fused->gbuf) (void)hipFree(c->fused->gbuf);
-    if (c->fused->gxbuf) (void)hipFree(c->fused->gxbuf);
-    if (c->fused->gxbuf_h3) (void)hipFree(c->fused->gxbuf_h3);
-    if (c->fused->g8stream) (void)hipFree(c->fused->g8stream);
-    if (c->fused->g8stream_b) (void)hipFree(c->fused->g8stream_b);
-    if (c->fused->wxbuf) (void)hipFree(c->fused->wxbuf);
-    if (c->fused->jf128_h3) (void)hipFree(c->fused->jf128_h3);
-    if (c->fused->up_w16) (void)hipFree(c->fused->up_w16);
-    if (c->fused->blk_tap) (void)hipFree(c->fused->blk_tap);
-    for (void* p : {c->fused->jr_blk, c->fused->jr_ent, (void*)c->fused->jr_w, (void*)c->fused->jr_rowptr, (void*)c->fused->jr_P})
-        if (p) (void)hipFree(p);
-    if (c->fused->up_w3) (void)hipFree(c->fused->up_w3);
-    if (c->fused->up_w2) (void)hipFree(c->fused->up_w2);
     delete c->fused;
     c->fused = nullptr;
 }
@@ -511,8 +502,8 @@ static int fused_upsample_in(gator_ctx* c, const float* vert431, int B, float* v
     int rc = fused_ensure_ws(c, B);
     if (rc) return rc;
     FusedState* f = c->fused;
-    rc = f->opt.up_x3 == 0 ? launch_pack_vc(vert431, B, f->vcp, stream)
-         : f->opt.up_x3 == 2 ? launch_pack_vc_x2(vert431, B, f->vcp3, stream) : launch_pack_vc_x3(vert431, B, f->cap, f->vcp3, stream);
+    rc = f->opt.up_x3 == 0 ? launch_pack_vc(vert431, B, f->ws->vcp, stream)
+         : f->opt.up_x3 == 2 ? launch_pack_vc_x2(vert431, B, f->ws->vcp3, stream) : launch_pack_vc_x3(vert431, B, f->ws->cap, f->ws->vcp3, stream);
     if (rc) return rc;
     StageTimer tm(c, "upsample", stream);
     return launch_upsample_any(f, c, B, verts, stream);
@@ -526,17 +517,17 @@ int fused_upsample(gator_ctx* c, const float* vert431, int B, float* verts, void
 static int ensure_bf16(gator_ctx* c, int B, void* stream) {
     FusedState* f = c->fused;
     if (!f->up_w16) {      // first bf16 call: pack the regressor weights once
-        GATOR_HIP_CHECK(hipMalloc(&f->up_w16, upsample_bf16_weight_elems() * 2));
+        GATOR_TRY(f->up_w16.alloc(upsample_bf16_weight_elems() * 2));
         int rc = pack_upsample_bf16(c->w.up_w, f->up_w16, stream);
         if (rc) return rc;
         // One-time: the pack must be COMPLETE before any other stream may read up_w16.  In sub-batch mode the second half
         // runs on a different (non-blocking) stream whose fork event was recorded before this pack was queued.
         GATOR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     }
-    if (B > f->vcp16_cap) {
-        if (f->vcp16) { GATOR_HIP_CHECK(hipDeviceSynchronize()); GATOR_HIP_CHECK(hipFree(f->vcp16)); }
-        GATOR_HIP_CHECK(hipMalloc(&f->vcp16, upsample_bf16_vcp_elems(B) * 2));
-        f->vcp16_cap = B;
+    if (B > f->ws->vcp16_cap) {
+        if (f->ws->vcp16) GATOR_HIP_CHECK(hipDeviceSynchronize());
+        GATOR_TRY(f->ws->vcp16.alloc(upsample_bf16_vcp_elems(B) * 2));
+        f->ws->vcp16_cap = B;
     }
     return GATOR_OK;
 }
@@ -558,9 +549,9 @@ static int fused_mdr_forward_impl(gator_ctx* c, const float* pc, int B, float* v
     int rc = fused_ensure_ws(c, B);
     if (rc) return rc;
     FusedState* f = c->fused;
-    rc = launch_mdr(c, f, pc, B, stream, nullptr, nullptr, bf16 && f->opt.c3_mdr);        // also writes the packed vertex-GEMM operand f->vcp / f->vcp3
+    rc = launch_mdr(c, f, pc, B, stream, nullptr, nullptr, bf16 && f->opt.c3_mdr);        // also writes the packed vertex-GEMM operand f->ws->vcp / f->ws->vcp3
     if (rc) return rc;
-    if (bf16 && f->opt.c3_up_bf16) return fused_upsample_bf16_in(c, f->vc, B, verts, stream);
+    if (bf16 && f->opt.c3_up_bf16) return fused_upsample_bf16_in(c, f->ws->vc, B, verts, stream);
     StageTimer tm(c, "upsample", stream);
     return launch_upsample_any(f, c, B, verts, stream);
 }
@@ -589,7 +580,7 @@ static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* 
     if (rc) return rc;
     FusedState::GraphSlot* slot = nullptr;
     for (auto& g : f->graphs)
-        if (g.B == B && g.in == pose2d && g.verts == verts && g.pose3d == pose3d && g.bf16 == bf16 && g.tiled == f->gat_tiled && g.persist == f->opt.mdr_persist && g.ws == f->ws) { slot = &g; break; }
+        if (g.B == B && g.in == pose2d && g.verts == verts && g.pose3d == pose3d && g.bf16 == bf16 && g.tiled == f->gat_tiled && g.persist == f->opt.mdr_persist && g.ws == f->ws->base.get()) { slot = &g; break; }
     if (!slot) {                                         // first sight: remember the key, run directly
         if ((int)f->graphs.size() >= FusedState::kGraphSlots) {
             // evict a key that was never captured if there is one (no replay can be in flight: no device-wide wait), else the least recently used
@@ -600,7 +591,7 @@ static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* 
             f->graphs.erase(lru);
         }
         FusedState::GraphSlot g;
-        g.B = B; g.in = pose2d; g.verts = verts; g.pose3d = pose3d; g.bf16 = bf16; g.tiled = f->gat_tiled; g.persist = f->opt.mdr_persist; g.ws = f->ws;
+        g.B = B; g.in = pose2d; g.verts = verts; g.pose3d = pose3d; g.bf16 = bf16; g.tiled = f->gat_tiled; g.persist = f->opt.mdr_persist; g.ws = f->ws->base.get();
         g.used = ++f->graph_clock;
         f->graphs.push_back(g);
         return fused_forward_one(c, pose2d, B, verts, pose3d, stream, bf16);
@@ -633,8 +624,8 @@ static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* 
     }
     GATOR_HIP_CHECK(hipGraphLaunch((hipGraphExec_t)slot->exec, (hipStream_t)stream));
     ++f->graph_launches;
-    c->set_tap(TAP_FEAT, f->feat, (int64_t)B * c->J * kC);      // the same taps a direct forward leaves (launch_mdr sets vert431 only while it runs)
-    c->set_tap(TAP_VERT431, f->vc, (int64_t)B * kV * 3);
+    c->set_tap(TAP_FEAT, f->ws->feat, (int64_t)B * c->J * kC);      // the same taps a direct forward leaves (launch_mdr sets vert431 only while it runs)
+    c->set_tap(TAP_VERT431, f->ws->vc, (int64_t)B * kV * 3);
     return GATOR_OK;
 }
 
@@ -715,28 +706,28 @@ static int fused_forward_one(gator_ctx* c, const float* pose2d, int B, float* ve
     const bool fused_tail = n_tiled < B && gat8_tail_supported(f, enc16);
     {   // x_out [B,3J] IS pose3d [B,J,3]: the tail writes the caller's buffer and produces the MDR joint K/V
         StageTimer tm(c, "gat", stream);
-        if (n_tiled > 0) rc = launch_gat_tiled(c, f, pose2d, n_tiled, f->feat, stream, B, enc16);
+        if (n_tiled > 0) rc = launch_gat_tiled(c, f, pose2d, n_tiled, f->ws->feat, stream, B, enc16);
         if (rc == GATOR_OK && n_tiled < B) {
             const size_t o = (size_t)n_tiled * c->J;
-            float* tail_jkv = fused_tail ? f->jkv + (size_t)n_tiled * 12 * kTile : nullptr;
-            rc = launch_gat(c, f, pose2d + o * 2, B - n_tiled, pose3d + o * 3, f->feat + o * kC, stream, true, B, n_tiled, enc16, tail_jkv);
+            float* tail_jkv = fused_tail ? f->ws->jkv + (size_t)n_tiled * 12 * kTile : nullptr;
+            rc = launch_gat(c, f, pose2d + o * 2, B - n_tiled, pose3d + o * 3, f->ws->feat + o * kC, stream, true, B, n_tiled, enc16, tail_jkv);
         }
     }
     if (rc) return rc;
     const int n_tail = fused_tail ? n_tiled : B;
     if (n_tail > 0) {   // lifter + MDR joint tokens as two batched launches (gat_tail.hip)
         StageTimer tm(c, "gat_tail", stream);
-        rc = launch_gat_tail(c, f, pose2d, f->feat, n_tail, pose3d, stream, true, !fused_tail);
+        rc = launch_gat_tail(c, f, pose2d, f->ws->feat, n_tail, pose3d, stream, true, !fused_tail);
         if (rc) return rc;
     }
-    c->set_tap(TAP_FEAT, f->feat, (int64_t)B * c->J * kC);
+    c->set_tap(TAP_FEAT, f->ws->feat, (int64_t)B * c->J * kC);
     rc = launch_mdr(c, f, nullptr, B, stream, pose3d, pose2d, bf16 && f->opt.c3_mdr);      // pose_combine is never materialised on this path
     if (rc) return rc;
     if (joints) {      // vertex GEMM with the joint-regression epilogue (verts may be null: nothing of 82 kB/mesh is stored)
         if (f->opt.up_x3 == 0 || bf16) return fail(GATOR_EUNSUPPORTED, "gator_forward_joints_f32 needs the split-precision vertex regressor");
         if (B > f->jr_cap) {
-            if (f->jr_P) { GATOR_HIP_CHECK(hipDeviceSynchronize()); GATOR_HIP_CHECK(hipFree(f->jr_P)); f->jr_P = nullptr; }
-            GATOR_HIP_CHECK(hipMalloc(&f->jr_P, (size_t)B * f->jr_nnz * 3 * sizeof(float)));
+            if (f->jr_P) GATOR_HIP_CHECK(hipDeviceSynchronize());
+            GATOR_TRY(f->jr_P.alloc((size_t)B * f->jr_nnz * 3 * sizeof(float)));
             f->jr_cap = B;
         }
         { StageTimer tm(c, "upsample", stream); rc = launch_upsample_any(f, c, B, verts, stream, true); }
@@ -744,7 +735,7 @@ static int fused_forward_one(gator_ctx* c, const float* pose2d, int B, float* ve
         StageTimer tm(c, "jreg_reduce", stream);
         return launch_jreg_reduce(f, B, joints, stream);
     }
-    if (bf16 && f->opt.c3_up_bf16) return fused_upsample_bf16_in(c, f->vc, B, verts, stream);
+    if (bf16 && f->opt.c3_up_bf16) return fused_upsample_bf16_in(c, f->ws->vc, B, verts, stream);
     StageTimer tm(c, "upsample", stream);
     return launch_upsample_any(f, c, B, verts, stream, false, bf16 && f->opt.c3_up_w1);
 }
@@ -778,13 +769,12 @@ int fused_set_joint_regressor(gator_ctx* c, const int32_t* row, const int32_t* c
         if (blk[2 * ob + 1] == 0) blk[2 * ob] = i;
         blk[2 * ob + 1]++;
     }
-    for (void* p : {f->jr_blk, f->jr_ent, (void*)f->jr_w, (void*)f->jr_rowptr, (void*)f->jr_P})
-        if (p) { GATOR_HIP_CHECK(hipDeviceSynchronize()); (void)hipFree(p); }
-    f->jr_P = nullptr; f->jr_cap = 0;
-    GATOR_HIP_CHECK(hipMalloc(&f->jr_blk, blk.size() * 4));
-    GATOR_HIP_CHECK(hipMalloc(&f->jr_ent, ent.size() * 4));
-    GATOR_HIP_CHECK(hipMalloc(&f->jr_w, w.size() * 4));
-    GATOR_HIP_CHECK(hipMalloc(&f->jr_rowptr, rowptr.size() * 4));
+    if (f->jr_nnz) GATOR_HIP_CHECK(hipDeviceSynchronize());      // a forward that reads the old regressor may still run
+    f->jr_P.reset(); f->jr_cap = f->jr_nnz = f->jr_nj = 0;
+    GATOR_TRY(f->jr_blk.alloc(blk.size() * 4));
+    GATOR_TRY(f->jr_ent.alloc(ent.size() * 4));
+    GATOR_TRY(f->jr_w.alloc(w.size() * 4));
+    GATOR_TRY(f->jr_rowptr.alloc(rowptr.size() * 4));
     GATOR_HIP_CHECK(hipMemcpy(f->jr_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice));
     GATOR_HIP_CHECK(hipMemcpy(f->jr_ent, ent.data(), ent.size() * 4, hipMemcpyHostToDevice));
     GATOR_HIP_CHECK(hipMemcpy(f->jr_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));

@@ -63,19 +63,12 @@ __global__ void k_absmax_tiles(const float* __restrict__ w, int64_t n, unsigned*
 }
 }  // namespace
 
-namespace {
-struct DevFree {        // temporaries of the pack routines: freed on every return path
-    void* p = nullptr;
-    ~DevFree() { if (p) (void)hipFree(p); }
-};
-}  // namespace
-
 int fused_repack_h3(const float* src_tiles, float* dst_tiles, int64_t ntiles, int* shift, float* residual, void* stream, int64_t period, int64_t live) {
     hipStream_t st = (hipStream_t)stream;
     const int64_t total = ntiles * kTile;
-    DevFree tmp;
-    GATOR_HIP_CHECK(hipMalloc(&tmp.p, 2 * sizeof(unsigned)));
-    unsigned* d = (unsigned*)tmp.p;
+    DevBuf<unsigned> tmp;      // freed on every return path
+    GATOR_TRY(tmp.alloc(2 * sizeof(unsigned)));
+    unsigned* d = tmp;
     GATOR_HIP_CHECK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned), st));
     k_absmax_tiles<<<512, 256, 0, st>>>(src_tiles, total, d, period, live);
     unsigned bits[2] = {0, 0};

@@ -22,12 +22,10 @@ struct GatBlockPk {                     // packed tiles of one GATBlock
     const float *mc, *mdT, *aoffT, *f1b; // M (channel on lane), diag(A).M (TOKEN on lane), offdiag(A)^T B-operand tile, hop-2 bias term
 };
 
-// Per-sub-batch workspace.  FusedState derives from it so kernels launchers read `f->vf` etc.; fused_forward swaps the
-// base part between the two sets when it runs two half-batches on two streams.
+// Per-sub-batch workspace: one block carved into regions (fused_api.hip: fused_ensure_ws).  FusedState holds two sets and a pointer to the
+// one in use (`f->ws->vf`); fused_forward points it at the second set for the second half-batch when it runs two halves on two streams.
 struct FusedWs {
-    // workspace (per cap batch)
-    float* ws = nullptr;
-    size_t ws_floats = 0;
+    DevBuf<float> base;                 // the block (per cap batch); everything below but vcp16 points into it
     int cap = 0;
     float *vcp = nullptr;               // [MT][3][kCB][4][64][4]  packed vert431 (A operand of the fp32-MFMA upsample GEMM)
     void* vcp3 = nullptr;               // split-precision A operand of the vertex GEMM: bf16 [plane 3][MT][3][28][64][8] (hi/mid/lo, upsample_x3.hip)
@@ -37,12 +35,12 @@ struct FusedWs {
     float *jkv = nullptr;               // [B][3 layers][2 (k,v)][2 heads][kTile]
     float *hf = nullptr;                // [B][431][32] head features
     float *lbf = nullptr;               // [B][431][64] tap: verts tokens after LBF3 (reference layout)
-    float *feat = nullptr, *xout = nullptr, *pc = nullptr;
+    float *feat = nullptr;              // [B][J][128] encoder output
     float* hpart = nullptr;             // [cap][14][64] DOUBLES: the head conv's per-tile partial sums (mdr_fused.hip: head_conv_partial)
     float *lpart = nullptr;             // [MT][J][2][kTile] lifter partial tiles (gat_tail.hip)
     bool mdr_ctr_clean = false;         // the joint-token kernel queued before launch_mdr has zeroed mdr_ctr for it
     unsigned* mdr_ctr = nullptr;        // k_mdr_persist: the counter blocks of a forward's launches, mdr_ctr_words(cap) words (mdr_fused.hip: MdrChunkPlan)
-    void* vcp16 = nullptr;              // bf16 packed vert431 for the bf16 vertex GEMM (cap-sized)
+    DevBuf<void> vcp16;                 // bf16 packed vert431 for the bf16 vertex GEMM (cap-sized)
     int vcp16_cap = 0;
 };
 
@@ -90,46 +88,46 @@ struct FusedOptions {
     bool mdr_ends = false;              // GATOR_MDR_ENDS (set): the last persistent launch prints when its workgroups started and ended
 };
 
-struct FusedState : FusedWs {
+struct FusedState {
+    ~FusedState();                      // fused_api.hip: graphs, streams and events; the buffers free themselves
     FusedOptions opt;                   // the switches this ctx was created with, narrowed by the weights and the device
-    float* wbuf = nullptr;              // all packed weights
-    float* gbuf = nullptr;              // packed GAT weights + tables
+    DevBuf<float> wbuf;                 // all packed weights
+    DevBuf<float> gbuf;                 // packed GAT weights + tables
     GatBlockPk gblk[kDepth];
     const float *g_biasT = nullptr, *g_m1T = nullptr, *g_m2T = nullptr, *g_gl3 = nullptr, *g_posT = nullptr, *g_vecs = nullptr;
-    size_t wbuf_floats = 0;
     // upsample: Wp[tap][ob][cb][4][64][4]
     const float* up_w = nullptr;
-    void* up_w3 = nullptr;              // bf16 [plane 3][tap][ob][28][64][8]  hi/mid/lo split of upsample_conv.weight
+    DevBuf<void> up_w3;                 // bf16 [plane 3][tap][ob][28][64][8]  hi/mid/lo split of upsample_conv.weight
     int gat_tiled = -1;                 // encoder policy in force (opt.gat_tiled until gator_set_encoder changes it)
     int n_cu = 256;                     // compute units of the ctx's device
-    float* gxbuf = nullptr;             // X3 tiles of the GAT block weights, tile-for-tile image of gbuf from gblk[0].qkv on
-    float* gxbuf_h3 = nullptr;          // the same grids as three fp16 planes of 2^gat_tiled_wshift * w (k_gat_tiled's four-product form)
+    DevBuf<float> gxbuf;                // X3 tiles of the GAT block weights, tile-for-tile image of gbuf from gblk[0].qkv on
+    DevBuf<float> gxbuf_h3;             // the same grids as three fp16 planes of 2^gat_tiled_wshift * w (k_gat_tiled's four-product form)
     int gat_tiled_wshift = 0;
-    float* g8stream = nullptr;          // the same tiles as four per-wave streams in consumption order (gat_roles.hip)
-    float* g8stream_b = nullptr;        // ... and its byte-lo image (H3B tiles, 5 KiB: gat_roles.hip), what k_gat8<true, LR, false, true> streams
+    DevBuf<float> g8stream;             // the same tiles as four per-wave streams in consumption order (gat_roles.hip)
+    DevBuf<float> g8stream_b;           // ... and its byte-lo image (H3B tiles, 5 KiB: gat_roles.hip), what k_gat8<true, LR, false, true> streams
     int gat8_wshift = 0;                // its weight stream holds three fp16 planes of 2^gat8_wshift * w
-    float* wxbuf = nullptr;             // X3 tiles of the MDR layer + head weights, tile-for-tile image of wbuf from lay[0].wq on
-    float* jf128_h3 = nullptr;          // get_joint_feature columns 5..132 as H3 tiles [2][4] of 2^jf128_wshift * w (k_gat8's fused tail)
+    DevBuf<float> wxbuf;                // X3 tiles of the MDR layer + head weights, tile-for-tile image of wbuf from lay[0].wq on
+    DevBuf<float> jf128_h3;             // get_joint_feature columns 5..132 as H3 tiles [2][4] of 2^jf128_wshift * w (k_gat8's fused tail)
     int jf128_wshift = 0;
     int mdr_wshift = 0;                 // mdr_x3 = 2: wxbuf holds three fp16 planes of 2^mdr_wshift * w
     float c3_logit_bound = 0.f;         // bound on |q . k| / sqrt(d_k) of the MDR self-attention in the exp2 domain, from the weights (fused_create)
-    void* up_w2 = nullptr;              // fp16 [ob/2][28][2][tap 3][plane 2][64][8]  scaled hi/lo split of upsample_conv.weight
+    DevBuf<void> up_w2;                 // fp16 [ob/2][28][2][tap 3][plane 2][64][8]  scaled hi/lo split of upsample_conv.weight
     float up_w2_unscale = 1.f;          // 2^-(weight shift + activation shift), applied to the finished sums
-    void* up_w16 = nullptr;             // bf16 [tap][ob][28][64][8] (packed on the first bf16 call, which waits for the pack)
+    DevBuf<void> up_w16;                // bf16 [tap][ob][28][64][8] (packed on the first bf16 call, which waits for the pack)
     // joint regressor fused into the vertex GEMM's epilogue (gator_set_joint_regressor / gator_forward_joints_f32)
-    void *jr_blk = nullptr, *jr_ent = nullptr;    // int2 [kOB] (first, count) ; int2 [nnz] (vertex, slot)
-    float* jr_w = nullptr;                        // [nnz] weights in entry order
-    int* jr_rowptr = nullptr;                     // [nj + 1] CSR row pointers over the slots (sorted by joint, then vertex)
-    float* jr_P = nullptr;                        // [cap][nnz][3] partial products
+    DevBuf<void> jr_blk, jr_ent;                  // int2 [kOB] (first, count) ; int2 [nnz] (vertex, slot)
+    DevBuf<float> jr_w;                           // [nnz] weights in entry order
+    DevBuf<int> jr_rowptr;                        // [nj + 1] CSR row pointers over the slots (sorted by joint, then vertex)
+    DevBuf<float> jr_P;                           // [cap][nnz][3] partial products
     int jr_nnz = 0, jr_nj = 0, jr_cap = 0;
-    float* blk_tap = nullptr;           // debug: residual stream after every GATBlock [depth][B][J][128] (gator_enable_block_taps)
+    DevBuf<float> blk_tap;              // debug: residual stream after every GATBlock [depth][B][J][128] (gator_enable_block_taps)
     int blk_tap_cap = 0;
     // MDR
     MdrLayerP lay[3];
     const float* head_w = nullptr;      // [1 nb][2 kb] combined motion/bias/scale linear
     const float* head_b = nullptr;      // [32]
     const float* tok_base = nullptr;    // [14][2][4][64][4]  v431 part of get_verts_feature + bias + pos_v  (T-layout tiles)
-    const float* tok_w3 = nullptr;
+    const float* tok_w3 = nullptr;      // [3][64]            pose3d part of get_verts_feature (columns 3..5), row-major [i][ch]
     // hipGraph replay of the full forward (gator_set_graph_replay / GATOR_GRAPH=1).  A forward is identified by (batch, the three
     // caller pointers, precision, encoder pin, persistent-launch state, workspace): the first time a key is seen the forward runs
     // directly (lazy allocations happen there), the second time it is captured on a private stream, from then on one hipGraphLaunch
@@ -146,13 +144,14 @@ struct FusedState : FusedWs {
     std::vector<GraphSlot> graphs;
     unsigned long long graph_clock = 0, graph_launches = 0;
     // sub-batch pipelining (two half-batches on two streams: one half's kernel tails are filled by the other's work)
-    FusedWs sets[2];
+    FusedWs sets[2];                    // set 0 is the normal workspace, set 1 the second half-batch's
+    FusedWs* ws = &sets[0];             // the set in use (fused_api.hip: WsScope)
     void* aux_stream = nullptr;
     void *ev_fork = nullptr, *ev_join = nullptr;
     const float* jfeat_p = nullptr;     // get_joint_feature.weight packed [2 nb][5 kb]
     const float* jfeat5 = nullptr;      // its columns 0..4 (pose2d, pose3d/1000) as [5][64]
     const float* jfeat128_p = nullptr;  // its columns 5..132 (feat) packed [2 nb][4 kb]
-    const float* posj_T = nullptr;      // [2] T-layout tiles of pos_j_id_embed[1..J]      // [3][64]            pose3d part of get_verts_feature (columns 3..5), row-major [i][ch]
+    const float* posj_T = nullptr;      // [2] T-layout tiles of pos_j_id_embed[1..J]
 };
 
 // fused_pack.hip

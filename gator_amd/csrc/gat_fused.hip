@@ -671,8 +671,8 @@ int gat_prepare_device() {
 // debug buffer of the per-block taps, [depth][B][J][128], allocated on first use only
 int gat_ensure_blk_tap(gator_ctx* c, FusedState* f, int B) {
     if (B > f->blk_tap_cap) {
-        if (f->blk_tap) { GATOR_HIP_CHECK(hipDeviceSynchronize()); GATOR_HIP_CHECK(hipFree(f->blk_tap)); f->blk_tap = nullptr; }
-        GATOR_HIP_CHECK(hipMalloc(&f->blk_tap, (size_t)kDepth * B * c->J * kC * sizeof(float)));
+        if (f->blk_tap) GATOR_HIP_CHECK(hipDeviceSynchronize());
+        GATOR_TRY(f->blk_tap.alloc((size_t)kDepth * B * c->J * kC * sizeof(float)));
         f->blk_tap_cap = B;
     }
     c->set_tap(TAP_GAT_BLOCKS, f->blk_tap, (int64_t)kDepth * B * c->J * kC);
@@ -720,15 +720,15 @@ int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x
     }
 #ifdef GATOR_DIAG
     a.stamps = nullptr;
-    unsigned long long* d_st = nullptr;
+    DevBuf<unsigned long long> d_st;
     if (f->opt.gat_stamps) {
-        GATOR_HIP_CHECK(hipMalloc(&d_st, 20 * sizeof(unsigned long long)));
-        a.stamps = d_st;
+        GATOR_TRY(d_st.alloc(20 * sizeof(unsigned long long)));
+        a.stamps = d_st.get();
     }
 #endif
     if (split_tail && f->opt.gat8) {                                                      // the two-role form (gat_roles.hip)
 #ifdef GATOR_DIAG
-        if (d_st) GATOR_HIP_CHECK(hipFree(d_st));                                         // (it prints its own stamps)
+        d_st.reset();                                                                     // (it prints its own stamps)
 #endif
         // tail_jkv: k_gat8 runs the lifter + joint tokens of ITS samples as its epilogue (and zeroes the MDR counters of the whole forward)
         return launch_gat8(c, f, pose2d, B, feat, stream, B_total, tap_row0, half16, tail_jkv ? x_out : nullptr, tail_jkv, tail_jkv ? (B_total > 0 ? B_total : B) : 0);
@@ -746,7 +746,7 @@ int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x
     if (d_st) {     // diagnostic build: synchronous read-back
         unsigned long long hst[20];
         GATOR_HIP_CHECK(hipMemcpy(hst, d_st, sizeof(hst), hipMemcpyDeviceToHost));
-        GATOR_HIP_CHECK(hipFree(d_st));
+        d_st.reset();
         static const char* nm[10] = {"embed", "ln1+qkv+attn+mgcn", "barrier1", "proj+prefetch+barrier2", "xfeat+barrier3",
                                      "back+barrier4", "ln2+fc1+gelu", "barrier5", "fc2+barrier6", "tail"};
         unsigned long long tot = 0;

@@ -1499,33 +1499,32 @@ int gat8_build_stream(FusedState* f, void* stream) {
         }
         if (o - idx.data() != (ptrdiff_t)(w + 1) * kWaveTiles) return fail(GATOR_EINVAL, "gat8_build_stream: tile count");
     }
-    struct DevFree { void* p = nullptr; ~DevFree() { if (p) (void)hipFree(p); } } t_idx, t_h3;      // temporaries: freed on every return path
-    GATOR_HIP_CHECK(hipMalloc(&t_idx.p, idx.size() * sizeof(int)));
-    int* d_idx = (int*)t_idx.p;
+    DevBuf<int> d_idx;      // temporaries: freed on every return path
+    DevBuf<float> h3;
+    GATOR_TRY(d_idx.alloc(idx.size() * sizeof(int)));
     GATOR_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
-    GATOR_HIP_CHECK(hipMalloc(&f->g8stream, (size_t)kStreamFloats * sizeof(float)));
+    GATOR_TRY(f->g8stream.alloc((size_t)kStreamFloats * sizeof(float)));
     if (f->opt.gat8_h4) {      // the four-product form streams three fp16 planes of 2^shift * w: the fp32 tiles are put in stream order
         float left = 0.f;  // first, so that the shift comes from exactly the weights the kernel multiplies (not the tables in between)
-        GATOR_HIP_CHECK(hipMalloc(&t_h3.p, idx.size() * kTile * sizeof(float)));
-        float* h3 = (float*)t_h3.p;
-        k_gather_tiles<kTile><<<(unsigned)idx.size(), 128, 0, (hipStream_t)stream>>>(f->gblk[0].qkv, d_idx, h3);
+        GATOR_TRY(h3.alloc(idx.size() * kTile * sizeof(float)));
+        k_gather_tiles<kTile><<<(unsigned)idx.size(), 128, 0, (hipStream_t)stream>>>(f->gblk[0].qkv, d_idx.get(), h3.get());
         int rc = fused_repack_h3(h3, f->g8stream, (int64_t)idx.size(), &f->gat8_wshift, &left, stream);
         if (rc == GATOR_OK && left > 1e-7f) rc = fail(GATOR_EUNSUPPORTED, "GAT weights span more than fp16 x 3 planes hold exactly: use GATOR_GAT8_H4=0");
         if (rc) return rc;
         if (f->opt.gat8_lobyte) {      // the byte-lo image of the same stream (H3B): used only if every lo value survives the round trip
-            DevFree t_bad;
-            GATOR_HIP_CHECK(hipMalloc(&t_bad.p, sizeof(unsigned)));
-            GATOR_HIP_CHECK(hipMemsetAsync(t_bad.p, 0, sizeof(unsigned), (hipStream_t)stream));
-            GATOR_HIP_CHECK(hipMalloc(&f->g8stream_b, (size_t)kStreamFloatsB * sizeof(float)));
-            k_h3_to_h3b<<<(unsigned)idx.size(), 64, 0, (hipStream_t)stream>>>(f->g8stream, f->g8stream_b, (unsigned*)t_bad.p);
+            DevBuf<unsigned> d_bad;
+            GATOR_TRY(d_bad.alloc(sizeof(unsigned)));
+            GATOR_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(unsigned), (hipStream_t)stream));
+            GATOR_TRY(f->g8stream_b.alloc((size_t)kStreamFloatsB * sizeof(float)));
+            k_h3_to_h3b<<<(unsigned)idx.size(), 64, 0, (hipStream_t)stream>>>(f->g8stream.get(), f->g8stream_b.get(), d_bad.get());
             GATOR_HIP_CHECK(hipGetLastError());
             unsigned nbad = 0;
-            GATOR_HIP_CHECK(hipMemcpyAsync(&nbad, t_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
+            GATOR_HIP_CHECK(hipMemcpyAsync(&nbad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
             GATOR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-            if (nbad) { f->opt.gat8_lobyte = false; (void)hipFree(f->g8stream_b); f->g8stream_b = nullptr; }
+            if (nbad) { f->opt.gat8_lobyte = false; f->g8stream_b.reset(); }
         }
     } else {
-        k_gather_tiles<kTileX3><<<(unsigned)idx.size(), 128, 0, (hipStream_t)stream>>>(f->gxbuf, d_idx, f->g8stream);
+        k_gather_tiles<kTileX3><<<(unsigned)idx.size(), 128, 0, (hipStream_t)stream>>>(f->gxbuf.get(), d_idx.get(), f->g8stream.get());
     }
     GATOR_HIP_CHECK(hipGetLastError());
     GATOR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
@@ -1561,7 +1560,7 @@ int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* 
     if (tail) {
         Gat8Tail& tl = a.tl;
         tl.lifter_w = w.lifter_w; tl.lifter_b = w.lifter_b; tl.x_out = tail_x_out; tl.jkv = tail_jkv;
-        if (ctr_B > 0 && f->opt.mdr_persist != 0) { tl.mdr_ctr = f->mdr_ctr; tl.ctr_B = ctr_B; f->mdr_ctr_clean = true; }
+        if (ctr_B > 0 && f->opt.mdr_persist != 0) { tl.mdr_ctr = f->ws->mdr_ctr; tl.ctr_B = ctr_B; f->ws->mdr_ctr_clean = true; }
         tl.jf_p = f->jfeat128_p;
         for (int i = 0; i < 3; ++i) { tl.j_wk_p[i] = f->lay[i].wk; tl.j_wv_p[i] = f->lay[i].wv; }
         tl.jf5 = f->jfeat5; tl.jf_h3 = f->jf128_h3; tl.jf_b = w.jfeat_b; tl.posj_T = f->posj_T;
@@ -1591,15 +1590,18 @@ int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* 
     a.dbg = f->opt.gat8_dbg;
     const bool want_stamps = f->opt.gat_stamps;
     constexpr int kSt = 2 * kDepth * 23 * 2 + kDepth * 8;
+    DevBuf<unsigned long long> d_stamps, d_tstamps;
     if (want_stamps) {
-        GATOR_HIP_CHECK(hipMalloc(&a.stamps, kSt * sizeof(unsigned long long)));
+        GATOR_TRY(d_stamps.alloc(kSt * sizeof(unsigned long long)));
+        a.stamps = d_stamps.get();
         GATOR_HIP_CHECK(hipMemset(a.stamps, 0, kSt * sizeof(unsigned long long)));
     }
 #endif
 #ifdef GATOR_DIAG
     a.tl.tstamps = nullptr;
     if (want_stamps && tail) {
-        GATOR_HIP_CHECK(hipMalloc(&a.tl.tstamps, 64 * sizeof(unsigned long long)));
+        GATOR_TRY(d_tstamps.alloc(64 * sizeof(unsigned long long)));
+        a.tl.tstamps = d_tstamps.get();
         GATOR_HIP_CHECK(hipMemset(a.tl.tstamps, 0, 64 * sizeof(unsigned long long)));
     }
 #endif
@@ -1623,7 +1625,7 @@ int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* 
     if (a.tl.tstamps) {
         unsigned long long ts[64];
         GATOR_HIP_CHECK(hipMemcpy(ts, a.tl.tstamps, sizeof(ts), hipMemcpyDeviceToHost));
-        GATOR_HIP_CHECK(hipFree(a.tl.tstamps));
+        d_tstamps.reset();
         fprintf(stderr, "[k_gat8 tail stamps, one workgroup, B=%d] s_memtime cycles since wave 0 entered: entry | loads issued + joint-token MFMAs | lifter done | at barrier | past barrier | jf + LN done | job 1 | job 2\n", B);
         for (int v = 0; v < 8; ++v) {
             fprintf(stderr, "  wave %d:", v);
@@ -1634,7 +1636,7 @@ int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* 
     if (a.stamps) {     // diagnostic build: synchronous read-back; blocks 1..5 averaged (block 0 carries the cold start)
         std::vector<unsigned long long> hs(kSt);
         GATOR_HIP_CHECK(hipMemcpy(hs.data(), a.stamps, kSt * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        GATOR_HIP_CHECK(hipFree(a.stamps));
+        d_stamps.reset();
         double tot[2] = {0, 0};
         fprintf(stderr, "[k_gat8 stamps, wg0, B=%d] cycles per step, mean of blocks 1-5: step | product work wait | helper work wait\n", B);
         for (int n = 0; n < 23; ++n) {

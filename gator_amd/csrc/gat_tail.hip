@@ -178,16 +178,16 @@ int launch_gat_tail(gator_ctx* c, FusedState* f, const float* pose2d, const floa
     const Weights& w = c->w;
     const int J = c->J, MT = (B + 31) / 32;
     hipStream_t st = (hipStream_t)stream;
-    LifterArgs la{feat, w.lifter_w, f->lpart, B, J};
+    LifterArgs la{feat, w.lifter_w, f->ws->lpart, B, J};
     k_gat_lifter<<<MT * J, 128, 0, st>>>(la);
     JointTailArgs a{};
-    a.pose2d = pose2d; a.feat = feat; a.part = f->lpart; a.lifter_b = w.lifter_b; a.x_out = x_out; a.B = B; a.J = J;
+    a.pose2d = pose2d; a.feat = feat; a.part = f->ws->lpart; a.lifter_b = w.lifter_b; a.x_out = x_out; a.B = B; a.J = J;
     a.jkv = nullptr;
     a.mdr_ctr = nullptr;
     a.x2 = f->opt.mdr_x3 == 2;
     if (joint) {
-        if (f->opt.mdr_persist != 0 && zero_ctr) { a.mdr_ctr = f->mdr_ctr; f->mdr_ctr_clean = true; }      // (!zero_ctr: k_gat8's fused tail zeroes them for the whole forward)
-        a.jkv = f->jkv; a.jf5 = f->jfeat5; a.jf_p = f->jfeat128_p; a.jf_b = w.jfeat_b; a.posj_T = f->posj_T;
+        if (f->opt.mdr_persist != 0 && zero_ctr) { a.mdr_ctr = f->ws->mdr_ctr; f->ws->mdr_ctr_clean = true; }      // (!zero_ctr: k_gat8's fused tail zeroes them for the whole forward)
+        a.jkv = f->ws->jkv; a.jf5 = f->jfeat5; a.jf_p = f->jfeat128_p; a.jf_b = w.jfeat_b; a.posj_T = f->posj_T;
         for (int i = 0; i < 3; ++i) { a.j_n1w[i] = w.lay[i].n1w; a.j_n1b[i] = w.lay[i].n1b; a.j_wk_p[i] = f->lay[i].wk; a.j_wv_p[i] = f->lay[i].wv; }
     }
     k_gat_joint<<<B, 256, 0, st>>>(a);

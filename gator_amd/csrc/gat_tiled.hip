@@ -609,7 +609,7 @@ int launch_gat_tiled(gator_ctx* c, FusedState* f, const float* pose2d, int B, fl
     for (int i = 0; i < kDepth; ++i) {
         const GatBlockPk& p = f->gblk[i];
         TiledBlk& q = a.blk[i];
-        const float* image = f->opt.gat_tiled_h4 ? f->gxbuf_h3 : f->gxbuf;
+        const float* image = f->opt.gat_tiled_h4 ? f->gxbuf_h3.get() : f->gxbuf.get();
         auto sel = [&](const float* t) { return image + (size_t)(t - f->gblk[0].qkv) / kTile * kTileX3; };
         q.qkv = sel(p.qkv); q.proj = sel(p.proj); q.w0 = sel(p.w0); q.w1 = sel(p.w1); q.lin0 = sel(p.lin0); q.lin1 = sel(p.lin1);
         q.back = sel(p.back); q.fc1 = sel(p.fc1); q.fc2 = sel(p.fc2);

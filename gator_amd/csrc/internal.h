@@ -7,11 +7,36 @@
 #include <string>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "gator_hip.h"
 
 namespace gator {
 
 int fail(int code, const char* fmt, ...);   // records the thread-local error message, returns `code`
+
+// Owner of one hipMalloc'ed block (Pinned = true: of one hipHostMalloc'ed, device-mapped block): null until alloc(), freed by reset() and
+// by the destructor, move-only.  It never synchronises and never sets the device: a site that replaces a buffer which queued work may
+// still read waits for the device itself, before alloc() / reset().
+template <class T, bool Pinned = false>
+class DevBuf {
+    T* p_ = nullptr;
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+    ~DevBuf() { reset(); }
+    void reset() { if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_)); p_ = nullptr; }
+    int alloc(size_t bytes) {      // frees what it held; GATOR_EHIP if the allocation fails
+        reset();
+        const hipError_t e = Pinned ? hipHostMalloc((void**)&p_, bytes, hipHostMallocMapped) : hipMalloc((void**)&p_, bytes);
+        if (e == hipSuccess) return GATOR_OK;
+        p_ = nullptr;
+        return fail(GATOR_EHIP, "%s(%zu bytes) failed: %s", Pinned ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
+    }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+};
 
 constexpr int kC = 128;       // GAT embed dim        (lib/core/base.py:57)
 constexpr int kH = 8;         // GAT heads            (lib/models/GAT.py:46)
@@ -68,10 +93,11 @@ struct ProfRec { const char* name; void* start; void* stop; };
 }  // namespace gator
 
 struct gator_ctx {
+    ~gator_ctx();                      // api.hip: the fused state, the profiling events, then the members below
     int J = 0, alpha = 0, impl = 0, device = 0, D = 0, parts = 3, subbatch_streams = 0, arithmetic = 0;
     std::string prefix_gat, prefix_mdr;
     std::map<std::string, gator::TensorRef> t;
-    char* arena = nullptr;
+    gator::DevBuf<char> arena;
     size_t arena_bytes = 0;
     gator::Weights w{};
     // folded, input-independent constants (device, fp32)
@@ -82,8 +108,7 @@ struct gator_ctx {
     float* mask2 = nullptr;        // [J,J]     sp==2
     float* pos_embed = nullptr;    // [J,128]   pos_id_embed[1..J] + pos_num_embed[deg], GAT.py:141-144
     // bring-up path workspace
-    float* ws = nullptr;
-    size_t ws_floats = 0;
+    gator::DevBuf<float> ws;
     int cap_batch = 0;
     int last_batch = 0;
     // debug taps of the last forward: fixed slots (no allocation / map insertion on the forward path)
@@ -92,7 +117,7 @@ struct gator_ctx {
     void clear_taps() { for (auto& t : taps) t = gator::Tap{}; }
     void set_tap(int id, const float* p, int64_t n) { taps[id].p = p; taps[id].n = n; }
     gator::FusedState* fused = nullptr;
-    unsigned* status_host = nullptr;   // sticky device status (gator::DeviceStatus): pinned host words, one per reason, the kernels write ...
+    gator::DevBuf<unsigned, true> status_host;   // sticky device status (gator::DeviceStatus): pinned host words, one per reason, the kernels write ...
     unsigned* status_dev = nullptr;    // ... through this device pointer
     int status_reason = 0;             // DeviceStatus of the last report (gator_status_reason)
     unsigned deferred_status = 0;      // an EARLIER call's status mask, taken by the running entry point and reported when it returns (api.hip: finish_fwd)
@@ -125,10 +150,10 @@ int fused_set_joint_regressor(gator_ctx* c, const int32_t* row, const int32_t* c
 int fused_forward_joints(gator_ctx* c, const float* pose2d, int B, float* joints, float* pose3d, float* verts, void* stream);
 int fused_set_encoder(gator_ctx* c, int mode);
 int fused_c3_state(const gator_ctx* c, float* bound);
-void fused_disable_persist(gator_ctx* c);
+void fused_disable_persist(gator_ctx* c);      // from now on the four MDR stages run as four launches on this ctx
 int fused_set_graph_replay(gator_ctx* c, int on);          // returns the number of graph launches so far (>= 0)
 // samples of a batch of B that the sample-tiled encoder takes under the policy in force (unpinned: under the ctx's own AUTO policy)
-int fused_tiled_samples(const gator_ctx* c, int B, bool unpinned = false);      // from now on the four MDR stages run as four launches on this ctx
+int fused_tiled_samples(const gator_ctx* c, int B, bool unpinned = false);
 }  // namespace gator
 
 namespace gator {
@@ -145,3 +170,4 @@ struct StageTimer {
         hipError_t _e = (expr);                                                                       \
         if (_e != hipSuccess) return gator::fail(GATOR_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
+#define GATOR_TRY(expr) do { const int _rc = (expr); if (_rc != GATOR_OK) return _rc; } while (0)

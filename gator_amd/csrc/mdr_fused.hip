@@ -1845,7 +1845,7 @@ LayerW make_layer(const FusedState* f, const gator_ctx* c, int li) {
 
 }  // namespace
 
-// pc [B,J,133] (reference layout) -> f->vc [B,431,3] (vert431) ; taps: f->lbf
+// pc [B,J,133] (reference layout) -> f->ws->vc [B,431,3] (vert431) ; taps: f->ws->lbf
 int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream, const float* x_out, const float* pose2d, bool half16) {
     // half16 (BASELINE config 3): the layers on ONE fp16 activation plane (XA = 3); needs the default weight / joint-tile forms (GATOR_MDR_X3=2)
     if (half16 && f->opt.mdr_x3 != 2) return fail(GATOR_EUNSUPPORTED, "16-bit MDR layers need GATOR_MDR_X3=2 (the default)");
@@ -1853,23 +1853,23 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
     hipStream_t st = (hipStream_t)stream;
     const Weights& w = c->w;
     JointArgs ja;
-    ja.pc = pc; ja.jw_p = f->jfeat_p; ja.jb = w.jfeat_b; ja.posj_T = f->posj_T; ja.jkv = f->jkv; ja.J = c->J;
+    ja.pc = pc; ja.jw_p = f->jfeat_p; ja.jb = w.jfeat_b; ja.posj_T = f->posj_T; ja.jkv = f->ws->jkv; ja.J = c->J;
     for (int i = 0; i < 3; ++i) { ja.n1w[i] = w.lay[i].n1w; ja.n1b[i] = w.lay[i].n1b; ja.wk_p[i] = f->lay[i].wk; ja.wv_p[i] = f->lay[i].wv; }
     ja.mdr_ctr = nullptr;
     ja.x2 = f->opt.mdr_x3 == 2;
     if (pc) {
-        if (f->opt.mdr_persist != 0) { ja.mdr_ctr = f->mdr_ctr; f->mdr_ctr_clean = true; }
+        if (f->opt.mdr_persist != 0) { ja.mdr_ctr = f->ws->mdr_ctr; f->ws->mdr_ctr_clean = true; }
         StageTimer tm(c, "mdr_joint", stream);
         k_mdr_joint<<<B, 128, 0, st>>>(ja);
     }    // else: done by k_gat's epilogue / k_gat_joint
-    const size_t per = (size_t)f->cap * kVT * 2 * kTile;      // one [B][14][2] tile set
-    const size_t perq = (size_t)f->cap * kVT * 2 * (f->opt.mdr_x3 == 1 ? kTileX3 : kTile);      // q/k/v tile sets: X3 tiles are 1.5x, fp32 and X2 tiles 4 KiB (X1 tiles 2 KiB: half of a set is used)
-    float* set[3][4] = {{f->vf, f->q, f->k, f->v}, {f->vf + per, f->q + perq, f->k + perq, f->v + perq},
-                        {f->vf + 2 * per, f->q + 2 * perq, f->k + 2 * perq, f->v + 2 * perq}};
+    const size_t per = (size_t)f->ws->cap * kVT * 2 * kTile;      // one [B][14][2] tile set
+    const size_t perq = (size_t)f->ws->cap * kVT * 2 * (f->opt.mdr_x3 == 1 ? kTileX3 : kTile);      // q/k/v tile sets: X3 tiles are 1.5x, fp32 and X2 tiles 4 KiB (X1 tiles 2 KiB: half of a set is used)
+    float* set[3][4] = {{f->ws->vf, f->ws->q, f->ws->k, f->ws->v}, {f->ws->vf + per, f->ws->q + perq, f->ws->k + perq, f->ws->v + perq},
+                        {f->ws->vf + 2 * per, f->ws->q + 2 * perq, f->ws->k + 2 * perq, f->ws->v + 2 * perq}};
     MdrArgs a{};
-    a.B = B; a.J = c->J; a.jkv = f->jkv; a.pc = pc; a.xout = pc ? nullptr : x_out; a.vj = w.vj; a.tok_base = f->tok_base; a.tok_w3 = f->tok_w3;
-    a.head_w = f->opt.mdr_x3 ? f->wxbuf + (size_t)(f->head_w - f->lay[0].wq) / kTile * kTileX3 : f->head_w; a.head_b = f->head_b; a.hf = f->hf; a.lbf = c->block_taps ? f->lbf : nullptr;      // the "mdr_lbf2" tap costs 110 KB of stores per sample: recorded with the block taps only
-    a.hpart = f->opt.mdr_head_partials ? reinterpret_cast<double*>(f->hpart) : nullptr;      // default on; GATOR_MDR_HEAD_PARTIALS=0 at create: the whole head in k_mdr_head (A/B)
+    a.B = B; a.J = c->J; a.jkv = f->ws->jkv; a.pc = pc; a.xout = pc ? nullptr : x_out; a.vj = w.vj; a.tok_base = f->tok_base; a.tok_w3 = f->tok_w3;
+    a.head_w = f->opt.mdr_x3 ? f->wxbuf + (size_t)(f->head_w - f->lay[0].wq) / kTile * kTileX3 : f->head_w; a.head_b = f->head_b; a.hf = f->ws->hf; a.lbf = c->block_taps ? f->ws->lbf : nullptr;      // the "mdr_lbf2" tap costs 110 KB of stores per sample: recorded with the block taps only
+    a.hpart = f->opt.mdr_head_partials ? reinterpret_cast<double*>(f->ws->hpart) : nullptr;      // default on; GATOR_MDR_HEAD_PARTIALS=0 at create: the whole head in k_mdr_head (A/B)
     a.bconv_w = w.bconv_w; a.hbn_w = w.bn_w; a.hbn_b = w.bn_b; a.hbn_mean = w.bn_mean; a.hbn_var = w.bn_var; a.halpha = c->alpha;
     a.lin_s = f->opt.mdr_x3 == 2 ? std::ldexp(kActScale, f->mdr_wshift) : 1.0f;      // 4-product linears: 16 x activations, 2^wshift x weights
     a.lin_inv = 1.0f / a.lin_s;
@@ -1882,8 +1882,8 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
     }
     const bool want_stamps = f->opt.mdr_stamps;
     const size_t solo = f->opt.mdr_solo ? 60 * 1024 : 0;      // 1 workgroup per CU (1 wave/SIMD)
-    unsigned long long* d_st = nullptr;
-    if (want_stamps) { GATOR_HIP_CHECK(hipMalloc(&d_st, 512 * sizeof(unsigned long long))); GATOR_HIP_CHECK(hipMemset(d_st, 0, 512 * sizeof(unsigned long long))); }
+    DevBuf<unsigned long long> d_st, d_ends_buf;
+    if (want_stamps) { GATOR_TRY(d_st.alloc(512 * sizeof(unsigned long long))); GATOR_HIP_CHECK(hipMemset(d_st, 0, 512 * sizeof(unsigned long long))); }
 #else
     constexpr size_t solo = 0;
 #endif
@@ -1893,8 +1893,8 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
     // fractional generation per stage (R = workgroups per CU: 3.5 at B = 256 is billed as 4 by each of the four launches) and, cut
     // into chunks, keeps a sample's tiles cache-resident between stages; below R = 3 (B < ~220) its per-sample dependency chain
     // costs more than it saves.
-    const bool ctr_clean = f->mdr_ctr_clean;      // zeroed for THIS call by the joint-token kernel queued just before (either entry point)
-    f->mdr_ctr_clean = false;
+    const bool ctr_clean = f->ws->mdr_ctr_clean;      // zeroed for THIS call by the joint-token kernel queued just before (either entry point)
+    f->ws->mdr_ctr_clean = false;
     const double R = (double)nwg / f->n_cu;
     const bool auto_persist = R >= 3.0;      // (round 3 also asked for a wasted fractional generation >= 4 %; with chunked launches the persistent form wins from R = 3 on: sweep in DESIGN.md)
     bool persist = f->opt.mdr_persist < 0 ? auto_persist : f->opt.mdr_persist > 0;
@@ -1907,7 +1907,7 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
 #endif
     for (int li = 0; li <= 3; ++li) {
 #ifdef GATOR_DIAG
-        a.stamps = (li == 1) ? d_st : nullptr;
+        a.stamps = (li == 1) ? d_st.get() : nullptr;
 #endif
         // four launches: two sets in turn.  One persistent launch: stage li writes set li and nothing else ever does, so no CU can
         // hold a stale L1 copy of a tile it reads (a line is only read after its one and only write) -- no cache invalidate in the
@@ -1942,13 +1942,14 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
 #ifdef GATOR_DIAG
     unsigned long long* d_ends = nullptr;
     if (f->opt.mdr_ends && persist) {
-        GATOR_HIP_CHECK(hipMalloc(&d_ends, 3 * 1024 * sizeof(unsigned long long)));
+        GATOR_TRY(d_ends_buf.alloc(3 * 1024 * sizeof(unsigned long long)));
+        d_ends = d_ends_buf.get();
         GATOR_HIP_CHECK(hipMemset(d_ends, 0, 3 * 1024 * sizeof(unsigned long long)));
         GATOR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_persist_ends), &d_ends, sizeof(d_ends)));
     }
 #endif
     if (persist) {      // the four stages as persistent launches (k_mdr_persist): tickets and per-sample completion counts start from zero
-        if (!ctr_clean) GATOR_HIP_CHECK(hipMemsetAsync(f->mdr_ctr, 0, mdr_ctr_words(B) * sizeof(unsigned), st));
+        if (!ctr_clean) GATOR_HIP_CHECK(hipMemsetAsync(f->ws->mdr_ctr, 0, mdr_ctr_words(B) * sizeof(unsigned), st));
         StageTimer tm(c, "mdr_layers", stream);
         int grid = 2 * f->n_cu;             // two workgroups per CU is what the registers allow; any grid drains the queues
         if (f->opt.mdr_persist_grid > 0) grid = f->opt.mdr_persist_grid;      // GATOR_MDR_PERSIST_GRID (tests: a grid that leaves XCDs without a workgroup)
@@ -1986,7 +1987,7 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
                 if (s.hpart) s.hpart += (size_t)b0 * kVT * 64;
                 if (s.lbf) s.lbf += (size_t)b0 * kV * kE;
             }
-            pc_.ctr = f->mdr_ctr + plan.block(ch);
+            pc_.ctr = f->ws->mdr_ctr + plan.block(ch);
             if (xa == 3) k_mdr_persist<3><<<grid, 256, 0, st>>>(pc_);
             else if (f->opt.mdr_x3 == 2) k_mdr_persist<2><<<grid, 256, 0, st>>>(pc_);
             else if (f->opt.mdr_x3 == 1) k_mdr_persist<1><<<grid, 256, 0, st>>>(pc_);
@@ -2000,7 +2001,7 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
         GATOR_HIP_CHECK(hipMemcpy(he.data(), d_ends, he.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         unsigned long long* none = nullptr;
         GATOR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_persist_ends), &none, sizeof(none)));
-        GATOR_HIP_CHECK(hipFree(d_ends));
+        d_ends_buf.reset();
         unsigned long long t0 = ~0ull, t1 = 0;
         int n = 0;
         for (int i = 0; i < 1024; ++i) if (he[3 * i + 2]) { t0 = std::min(t0, he[3 * i]); t1 = std::max(t1, he[3 * i + 2]); ++n; }
@@ -2031,20 +2032,20 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
             fprintf(stderr, " %d:(%.0f,%.0f,%llu,x%llu,cu%llu.se%llu)", i * 64, (hst[8 + 4 * i] - t0) / 100.0, (hst[9 + 4 * i] - t0) / 100.0,
                     hst[10 + 4 * i] / 1000, hst[11 + 4 * i] >> 32, (hst[11 + 4 * i] >> 8) & 0xf, (hst[11 + 4 * i] >> 13) & 0x7);
         fprintf(stderr, "\n");
-        GATOR_HIP_CHECK(hipFree(d_st));
+        d_st.reset();
         fprintf(stderr, "[k_mdr_layer<1> stamps, tile 0] attention(2 heads)=%llu outproj+res=%llu cross-attn block=%llu mlp=%llu customLN+qkv=%llu\n",
                 hst[0], hst[1], hst[2], hst[3], hst[4]);
     }
 #endif
     HeadArgs ha;
-    ha.hf = f->hf; ha.bn_w = w.bn_w; ha.bn_b = w.bn_b; ha.bn_mean = w.bn_mean; ha.bn_var = w.bn_var;
-    ha.bconv_w = w.bconv_w; ha.bconv_b = w.bconv_b; ha.vc = f->vc; ha.vcp = f->vcp;
-    ha.persist_ctr = persist ? f->mdr_ctr : nullptr;
+    ha.hf = f->ws->hf; ha.bn_w = w.bn_w; ha.bn_b = w.bn_b; ha.bn_mean = w.bn_mean; ha.bn_var = w.bn_var;
+    ha.bconv_w = w.bconv_w; ha.bconv_b = w.bconv_b; ha.vc = f->ws->vc; ha.vcp = f->ws->vcp;
+    ha.persist_ctr = persist ? f->ws->mdr_ctr : nullptr;
     ha.plan = plan;
     ha.status = c->status_dev;
     ha.pose2d = pose2d; ha.J = c->J;      // nullptr from the MDR-only entry point: its input is the pose features, not the poses
-    ha.vcp2 = f->opt.up_x3 == 2 ? (_Float16*)f->vcp3 : nullptr;
-    ha.vcp3 = f->opt.up_x3 == 1 ? (__bf16*)f->vcp3 : nullptr; ha.vcp3_plane = upsample_x3_vcp_elems(f->cap) / 3;     // plane stride fixed by the workspace capacity
+    ha.vcp2 = f->opt.up_x3 == 2 ? (_Float16*)f->ws->vcp3 : nullptr;
+    ha.vcp3 = f->opt.up_x3 == 1 ? (__bf16*)f->ws->vcp3 : nullptr; ha.vcp3_plane = upsample_x3_vcp_elems(f->ws->cap) / 3;     // plane stride fixed by the workspace capacity
     ha.alpha = c->alpha;
     {
         StageTimer tm(c, "mdr_head", stream);
@@ -2053,8 +2054,8 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
         else k_mdr_head<512, false><<<B, 512, 0, st>>>(ha);
     }
     GATOR_HIP_CHECK(hipGetLastError());
-    c->set_tap(TAP_MDR_LBF2, c->block_taps ? f->lbf : nullptr, c->block_taps ? (int64_t)B * kV * kE : 0);
-    c->set_tap(TAP_VERT431, f->vc, (int64_t)B * kV * 3);
+    c->set_tap(TAP_MDR_LBF2, c->block_taps ? f->ws->lbf : nullptr, c->block_taps ? (int64_t)B * kV * kE : 0);
+    c->set_tap(TAP_VERT431, f->ws->vc, (int64_t)B * kV * 3);
     return GATOR_OK;
 }
 

@@ -243,15 +243,15 @@ int upsample_x2_prepare_device() {
 // Packs upsample_conv.weight [6890][431][3] and returns the factor that undoes both operand scalings in *unscale
 int pack_upsample_x2(const float* up_w, void* dst, float* unscale, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    unsigned* d_max = nullptr;
-    GATOR_HIP_CHECK(hipMalloc(&d_max, sizeof(unsigned)));
+    DevBuf<unsigned> d_max;
+    GATOR_TRY(d_max.alloc(sizeof(unsigned)));
     GATOR_HIP_CHECK(hipMemsetAsync(d_max, 0, sizeof(unsigned), st));
     const int64_t n = (int64_t)kNV * kV * 3;
-    k_absmax<<<1024, 256, 0, st>>>(up_w, n, d_max);
+    k_absmax<<<1024, 256, 0, st>>>(up_w, n, d_max.get());
     unsigned bits = 0;
     GATOR_HIP_CHECK(hipMemcpyAsync(&bits, d_max, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     GATOR_HIP_CHECK(hipStreamSynchronize(st));
-    (void)hipFree(d_max);
+    d_max.reset();
     float wmax;
     static_assert(sizeof(wmax) == sizeof(bits), "float bits");
     memcpy(&wmax, &bits, sizeof(wmax));
@@ -281,11 +281,11 @@ int launch_pack_vc_x2(const float* vc, int B, void* vcp2, void* stream) {
 int launch_upsample_x2(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints, bool w1) {
     const int MT = (B + 31) / 32, MG = (MT + 3) / 4;
     JregEpi2 jr{};
-    if (with_joints) { jr.blk = (const int2*)f->jr_blk; jr.ent = (const int2*)f->jr_ent; jr.w = f->jr_w; jr.P = f->jr_P; jr.nnz = f->jr_nnz; }
+    if (with_joints) { jr.blk = (const int2*)f->jr_blk.get(); jr.ent = (const int2*)f->jr_ent.get(); jr.w = f->jr_w.get(); jr.P = f->jr_P.get(); jr.nnz = f->jr_nnz; }
     const int nwg = (kOB / 2) * MG;
-    if (w1) k_upsample_x2<false><<<nwg, 512, kX2Lds, (hipStream_t)stream>>>((const _Float16*)f->vcp3, (const _Float16*)f->up_w2, c->w.up_b, c->w.v6890,
+    if (w1) k_upsample_x2<false><<<nwg, 512, kX2Lds, (hipStream_t)stream>>>((const _Float16*)f->ws->vcp3, (const _Float16*)f->up_w2.get(), c->w.up_b, c->w.v6890,
                                                                            verts, B, MT, MG, nwg, f->up_w2_unscale, jr);
-    else k_upsample_x2<true><<<nwg, 512, kX2Lds, (hipStream_t)stream>>>((const _Float16*)f->vcp3, (const _Float16*)f->up_w2, c->w.up_b, c->w.v6890,
+    else k_upsample_x2<true><<<nwg, 512, kX2Lds, (hipStream_t)stream>>>((const _Float16*)f->ws->vcp3, (const _Float16*)f->up_w2.get(), c->w.up_b, c->w.v6890,
                                                                        verts, B, MT, MG, nwg, f->up_w2_unscale, jr);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;

@@ -243,7 +243,7 @@ int launch_pack_vc_x3(const float* vc, int B, int cap, void* vcp3, void* stream)
 
 int launch_jreg_reduce(const FusedState* f, int B, float* joints, void* stream) {
     const int64_t n = (int64_t)B * f->jr_nj * 3;
-    k_jreg_reduce<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(f->jr_P, f->jr_rowptr, f->jr_nnz, f->jr_nj, B, joints);
+    k_jreg_reduce<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(f->jr_P.get(), f->jr_rowptr.get(), f->jr_nnz, f->jr_nj, B, joints);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;
 }
@@ -252,10 +252,10 @@ int launch_jreg_reduce(const FusedState* f, int B, float* joints, void* stream) 
 int launch_upsample_x3(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints) {
     const int MT = (B + 31) / 32;
     JregEpi jr{};
-    if (with_joints) { jr.blk = (const int2*)f->jr_blk; jr.ent = (const int2*)f->jr_ent; jr.w = f->jr_w; jr.P = f->jr_P; jr.nnz = f->jr_nnz; }
-    const int64_t w_plane = (int64_t)upsample_x3_weight_elems() / 3, a_plane = (int64_t)upsample_x3_vcp_elems(f->cap) / 3;
+    if (with_joints) { jr.blk = (const int2*)f->jr_blk.get(); jr.ent = (const int2*)f->jr_ent.get(); jr.w = f->jr_w.get(); jr.P = f->jr_P.get(); jr.nnz = f->jr_nnz; }
+    const int64_t w_plane = (int64_t)upsample_x3_weight_elems() / 3, a_plane = (int64_t)upsample_x3_vcp_elems(f->ws->cap) / 3;
     const int nwg = kOB * ((MT + kX3Waves - 1) / kX3Waves);
-    k_upsample_x3<<<nwg, 64 * (kX3Waves + 1), 0, (hipStream_t)stream>>>((const __bf16*)f->vcp3, (const __bf16*)f->up_w3, c->w.up_b,
+    k_upsample_x3<<<nwg, 64 * (kX3Waves + 1), 0, (hipStream_t)stream>>>((const __bf16*)f->ws->vcp3, (const __bf16*)f->up_w3.get(), c->w.up_b,
                                                                        c->w.v6890, verts, B, MT, nwg, a_plane, w_plane, jr);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;
