@@ -44,6 +44,12 @@ __global__ void k_preprocess(const float* __restrict__ in, int B, int jin, int c
 }
 
 // 3x3 SVD by one-sided Jacobi (Hestenes) in fp64: G = H V is driven to orthogonal columns; s_i = |G_i|, U_i = G_i / s_i.
+// V is a product of rotations and column swaps, orthogonal whatever the rank.  A column of G under 1e-14 s_0 is rounding noise:
+// normalised it is a unit vector in no particular relation to the others, and R = V U^T would not be a rotation.  Such columns of U
+// are therefore COMPLETED to an orthonormal basis: rank 2 (coplanar points) U_2 = U_0 x U_1; rank 1 (collinear points, e.g. a
+// collapsed prediction) U_1 = a unit vector orthogonal to U_0, then U_2 = U_0 x U_1.  The completion spans the null space, so the
+// optimum does not depend on it.  Rank 0 (H = 0) keeps U = 0: R = 0, c = 0 / var(a), aligned = the target centroid (NaN when
+// var(a) = 0 too), as the reference's c = 0 gives.  The full-rank path is untouched.
 __device__ void svd3(const double H[3][3], double U[3][3], double s[3], double V[3][3]) {
     double G[3][3];
 #pragma unroll
@@ -94,7 +100,17 @@ __device__ void svd3(const double H[3][3], double U[3][3], double s[3], double V
     for (int j = 0; j < 3; ++j)
 #pragma unroll
         for (int i = 0; i < 3; ++i) U[i][j] = s[j] > 1e-300 ? G[i][j] / s[j] : 0.0;
-    if (s[2] <= 1e-14 * s[0]) {      // rank-deficient covariance (coplanar points): complete U with the cross product
+    if (s[0] > 1e-300 && s[1] <= 1e-14 * s[0]) {      // rank-1 covariance (collinear points): U[:,1] = e x U[:,0], normalised
+        const double u0 = U[0][0], u1 = U[1][0], u2 = U[2][0];
+        const double m0 = fabs(u0), m1 = fabs(u1), m2 = fabs(u2);
+        double w0, w1, w2;           // e = the coordinate axis on which U[:,0] is smallest: |e x U[:,0]| >= sqrt(2/3)
+        if (m0 <= m1 && m0 <= m2) { w0 = 0.0; w1 = -u2; w2 = u1; }
+        else if (m1 <= m2)        { w0 = u2;  w1 = 0.0; w2 = -u0; }
+        else                      { w0 = -u1; w1 = u0;  w2 = 0.0; }
+        const double wn = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+        U[0][1] = w0 / wn; U[1][1] = w1 / wn; U[2][1] = w2 / wn;
+    }
+    if (s[2] <= 1e-14 * s[0]) {      // rank-deficient covariance (coplanar or collinear points): complete U with the cross product
         U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
         U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
         U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];

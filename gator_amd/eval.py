@@ -14,6 +14,17 @@ import torch
 from . import _lib
 
 H36M_EVAL_JOINTS = (1, 2, 3, 4, 5, 6, 8, 10, 11, 12, 13, 14, 15, 16)     # data/PW3D/dataset.py:46
+N_VERTS = 6890                                                            # SMPL vertices (csrc/internal.h: kNV)
+
+
+def _checked_eval_joints(eval_joints, n_joint, who):
+    """The evaluation indices as a list of ints, each in [0, n_joint): the kernels use them as raw offsets, so a negative or too
+    large one is refused here, from the Python list, before anything is sent to the device."""
+    idx = [int(i) for i in eval_joints]
+    bad = [i for i in idx if i < 0 or i >= n_joint]
+    if bad:
+        raise ValueError('%s: evaluation joint index %d outside [0, %d)' % (who, bad[0], n_joint))
+    return idx
 
 
 class JointRegressor:
@@ -21,6 +32,8 @@ class JointRegressor:
 
     def __init__(self, dense, device):
         d = np.asarray(dense, np.float32)
+        if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] != N_VERTS:      # a column is used as a vertex offset on the device, unchecked
+            raise ValueError('JointRegressor: expected a dense [n_joint, %d] matrix, got %s' % (N_VERTS, tuple(d.shape)))
         r, c = np.nonzero(d)
         self.n_joint = int(d.shape[0])
         self.nnz = int(r.size)
@@ -76,7 +89,7 @@ def rigid_align(a, b):
 
 
 def pa_mpjpe(pred_joint, target_joint, eval_joints=H36M_EVAL_JOINTS):
-    idx = torch.as_tensor(eval_joints, device=pred_joint.device)
+    idx = torch.as_tensor(_checked_eval_joints(eval_joints, pred_joint.shape[1], 'pa_mpjpe'), device=pred_joint.device)
     p, t = pred_joint[:, idx], target_joint[:, idx]
     return torch.sqrt(((rigid_align(p, t) - t) ** 2).sum(2)).mean()
 
@@ -87,9 +100,11 @@ def joint_errors(pred_joint, target_joint, eval_joints=H36M_EVAL_JOINTS, root=0,
     if not (pred_joint.is_cuda and target_joint.is_cuda):
         raise RuntimeError('joint_errors: inputs must live on a HIP device')
     p, t = pred_joint.contiguous().float(), target_joint.contiguous().float()
+    if p.dim() != 3 or p.shape[2] != 3 or p.shape != t.shape:
+        raise ValueError('joint_errors: expected two [B,nj,3] tensors, got %s and %s' % (tuple(p.shape), tuple(t.shape)))
     B, nj = p.shape[0], p.shape[1]
+    idx = None if eval_joints is None else torch.as_tensor(_checked_eval_joints(eval_joints, nj, 'joint_errors'), dtype=torch.int32, device=p.device)
     out = torch.empty((B, 2), device=p.device, dtype=torch.float32)
-    idx = None if eval_joints is None else torch.as_tensor(list(eval_joints), dtype=torch.int32, device=p.device)
     st = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
     _lib.check(_lib.load().gator_joint_errors_f32(p.data_ptr(), t.data_ptr(), B, nj, idx.data_ptr() if idx is not None else None,
                                                   int(idx.numel()) if idx is not None else 0, int(root), float(pred_scale), out.data_ptr(), st),

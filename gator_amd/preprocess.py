@@ -41,6 +41,9 @@ def preprocess_chain(joints, rot_deg=None, flip=None, flip_pairs=(), add_pelvis_
     -> (pose2d [B,J(+2),2], valid [B] int32: 0 where process_bbox rejects the box and the reference drops the sample)."""
     if not joints.is_cuda:
         raise RuntimeError('preprocess_chain: joints must live on a HIP device (there is no CPU path)')
+    pair_list = [(int(u), int(v)) for u, v in flip_pairs]
+    if any(u < 0 or v < 0 for u, v in pair_list):       # the kernel skips a pair beyond the sample's joints; a negative one would be a raw offset
+        raise ValueError('preprocess_chain: negative joint index in flip_pairs')
     x = joints.contiguous().float()
     B, J, C = x.shape
     dev = x.device
@@ -48,7 +51,7 @@ def preprocess_chain(joints, rot_deg=None, flip=None, flip_pairs=(), add_pelvis_
     valid = torch.empty((B,), device=dev, dtype=torch.int32)
     rot = None if rot_deg is None else torch.as_tensor(rot_deg, dtype=torch.float32, device=dev).contiguous()
     fl = None if flip is None else torch.as_tensor(flip, dtype=torch.int32, device=dev).contiguous()
-    pairs = torch.as_tensor(list(flip_pairs), dtype=torch.int32, device=dev).reshape(-1, 2).contiguous()
+    pairs = torch.as_tensor(pair_list, dtype=torch.int32, device=dev).reshape(-1, 2).contiguous()
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(_lib.load().gator_preprocess_chain_f32(x.data_ptr(), B, J, C, int(bool(add_pelvis_neck)), rot.data_ptr() if rot is not None else None,
                                                       fl.data_ptr() if fl is not None else None, pairs.data_ptr() if pairs.numel() else None,
