@@ -25,6 +25,12 @@ class GemmProblem(ctypes.Structure):            # include/gator_train.h: gator_g
                 ('ws_off', ctypes.c_int64), ('total_wgs', ctypes.c_int32), ('total_fin', ctypes.c_int32), ('bias', ctypes.c_void_p)]
 
 
+class SmplModel(ctypes.Structure):              # include/gator_hip.h: gator_smpl_model (host pointers)
+    _fields_ = [('struct_size', ctypes.c_int32), ('n_verts', ctypes.c_int32), ('n_joints', ctypes.c_int32), ('n_betas', ctypes.c_int32),
+                ('v_template', ctypes.c_void_p), ('shapedirs', ctypes.c_void_p), ('posedirs', ctypes.c_void_p), ('weights', ctypes.c_void_p),
+                ('j_regressor', ctypes.c_void_p), ('parents', ctypes.c_void_p)]
+
+
 ABI_VERSION = 2                                 # include/gator_hip.h: GATOR_ABI_VERSION this binding was written against
 EDEVICE, EDEVICE_DEFERRED = -7, -8
 REASON_PERSIST_INCOMPLETE, REASON_NONFINITE, REASON_INPUT_NONFINITE = 1, 2, 3      # gator_status_reason
@@ -66,6 +72,10 @@ SIGNATURES = {
     'gator_rigid_align_f32': (_I, [_P, _P, _I, _I, _P, _P]),
     'gator_crop_joints_f32': (_I, [_P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
     'gator_fit_camera_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),
+    'gator_smpl_create': (_I, [_P, ctypes.POINTER(_P)]),
+    'gator_smpl_destroy': (_I, [_P]),
+    'gator_smpl_forward_f32': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P, _P]),
+    'gator_smpl_workspace': (_I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_L)]),
     'gator_comm_unique_id': (_I, [_P]),
     'gator_comm_create': (_I, [_P, _I, _I, ctypes.POINTER(_P)]),
     'gator_comm_destroy': (_I, [_P]),

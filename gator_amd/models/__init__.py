@@ -2,3 +2,4 @@
 from . import GAT, MDR  # noqa: F401  (order matters: GATOR imports both)
 from . import project_net  # noqa: F401
 from . import GATOR  # noqa: F401
+from . import smpl  # noqa: F401  (lib/smpl.py: the SMPL wrapper the datasets hold as mesh_model)

@@ -1,0 +1,186 @@
+"""The SMPL body-model layer on the device (gator_smpl_*, csrc/smpl_lbs.hip): what every training dataset of the reference calls at
+batch 1 on the CPU to build its ground-truth mesh (smplpytorch/pytorch/smpl_layer.py:65-158; data/AMASS/dataset.py:182-213,
+data/COCO/dataset.py:147-166), batched.
+
+  SMPLLayer(pose [B,72], betas [B,10] | None, trans [B,3] | None)  ->  (verts [B,6890,3], joints [B,24,3])      the layer's own call
+  get_smpl_coord(layer, pose, shape, trans)                        ->  (mesh, joints + five face key points), mm   the datasets' wrapper
+  targets_from_smpl(layer, pose, shape, trans, regressors ...)     ->  {'mesh', 'reg_pose3d', 'lift_pose3d'}        Trainer.step's targets
+
+The model's arrays come from the caller: the official files are licence-gated and are no part of this package.  No backward: the
+reference never differentiates through the layer."""
+import ctypes
+import pickle
+
+import numpy as np
+import torch
+
+from . import _lib
+
+FACE_KPS_VERTEX = (331, 2802, 6262, 3489, 3990)      # lib/smpl.py:22: nose, L/R eye, L/R ear as mesh vertices
+
+
+def _plain(x):
+    """A value of a model file as numpy: chumpy arrays carry .r, the joint regressor is a scipy sparse matrix."""
+    if hasattr(x, 'r') and not isinstance(x, np.ndarray):
+        x = x.r
+    if hasattr(x, 'toarray'):
+        x = x.toarray()
+    return np.asarray(x)
+
+
+def _f32(a):
+    return np.ascontiguousarray(_plain(a), dtype=np.float32)
+
+
+def model_arrays(d):
+    """A mapping with the model files' keys (v_template, shapedirs, posedirs, weights, J_regressor, kintree_table, f) -> the layer's
+    arguments as plain numpy arrays: {v_template, shapedirs, posedirs, weights, J_regressor, parents, faces}."""
+    kt = _plain(d['kintree_table']) if 'kintree_table' in d else _plain(d['parents'])
+    faces = d['f'] if 'f' in d else (d['faces'] if 'faces' in d else None)
+    return {'v_template': _f32(d['v_template']), 'shapedirs': _f32(d['shapedirs']) if 'shapedirs' in d else None,
+            'posedirs': _f32(d['posedirs']), 'weights': _f32(d['weights']), 'J_regressor': _f32(d['J_regressor']),
+            'parents': (kt[0] if kt.ndim == 2 else kt).astype(np.int64), 'faces': None if faces is None else _plain(faces).astype(np.int64)}
+
+
+def read_npz(path):
+    with np.load(path) as z:
+        return model_arrays({k: z[k] for k in z.files})
+
+
+def read_pkl(path):
+    """The model pickle as the reference reads it (pickle, latin1).  The official files hold chumpy objects, so unpickling them needs
+    chumpy installed; a file re-saved with plain numpy arrays (and a scipy sparse or dense regressor) needs nothing."""
+    with open(path, 'rb') as fh:
+        return model_arrays(pickle.load(fh, encoding='latin1'))
+
+
+class SMPLLayer:
+    """smplpytorch's SMPL_Layer, forward only, on one HIP device.  Same call order (pose, betas, trans), the same center_idx
+    attribute, th_faces / th_J_regressor / th_weights / kintree_parents as the reference layer exposes them.  out_scale multiplies
+    the (translated or centred) outputs: 1000 for the datasets' millimetres."""
+
+    def __init__(self, v_template, shapedirs, posedirs, weights, J_regressor, parents, faces=None, center_idx=None, device='cuda',
+                 out_scale=1.0, gender='neutral'):
+        vt, w, jr = _f32(v_template), _f32(weights), _f32(J_regressor)
+        if vt.ndim != 2 or w.ndim != 2 or jr.ndim != 2 or vt.shape[1] != 3:
+            raise ValueError('SMPLLayer: v_template [NV,3], weights [NV,NJ] and J_regressor [NJ,NV] are 2-D arrays')
+        nv, nj = vt.shape[0], w.shape[1]
+        sd = np.zeros((nv, 3, 0), np.float32) if shapedirs is None else _f32(shapedirs)
+        pd = _f32(posedirs)
+        par = np.asarray(_plain(parents)).astype(np.int64).reshape(-1)
+        if w.shape[0] != nv or jr.shape != (nj, nv) or sd.ndim != 3 or sd.shape[:2] != (nv, 3) or pd.shape != (nv, 3, (nj - 1) * 9) or par.shape != (nj,):
+            raise ValueError('SMPLLayer: inconsistent model shapes: v_template %s shapedirs %s posedirs %s weights %s J_regressor %s parents %s'
+                             % (vt.shape, sd.shape, pd.shape, w.shape, jr.shape, par.shape))
+        par32 = np.ascontiguousarray(np.where((par < 0) | (par >= 2 ** 31), -1, par).astype(np.int32))
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('SMPLLayer: the layer runs on a HIP device (there is no CPU path)')
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.num_verts, self.num_joints, self.num_betas = nv, nj, sd.shape[2]
+        self.center_idx, self.out_scale, self.gender = center_idx, float(out_scale), gender
+        self.kintree_parents = [int(p) for p in par]
+        self.th_faces = None if faces is None else torch.from_numpy(np.asarray(_plain(faces)).astype(np.int64))
+        self.th_J_regressor = torch.from_numpy(jr)
+        self.th_weights = torch.from_numpy(w)
+        self.th_v_template = torch.from_numpy(vt).unsqueeze(0)
+        model = _lib.SmplModel(ctypes.sizeof(_lib.SmplModel), nv, nj, sd.shape[2], vt.ctypes.data, sd.ctypes.data if sd.size else None,
+                               pd.ctypes.data, w.ctypes.data, jr.ctypes.data, par32.ctypes.data)
+        self._ctx = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().gator_smpl_create(ctypes.byref(model), ctypes.byref(self._ctx)), 'gator_smpl_create')
+
+    @classmethod
+    def from_arrays(cls, v_template, shapedirs, posedirs, weights, J_regressor, parents, faces=None, **kw):
+        return cls(v_template, shapedirs, posedirs, weights, J_regressor, parents, faces=faces, **kw)
+
+    @classmethod
+    def from_npz(cls, path, **kw):
+        return cls(**read_npz(path), **kw)
+
+    @classmethod
+    def from_pkl(cls, path, **kw):
+        return cls(**read_pkl(path), **kw)
+
+    def __del__(self):
+        ctx, self._ctx = getattr(self, '_ctx', None), None
+        if ctx:
+            try:
+                _lib.load().gator_smpl_destroy(ctx)
+            except Exception:
+                pass
+
+    def workspace(self):
+        """(device address, batch capacity) of the ctx's workspace: a test hook."""
+        base, cap = ctypes.c_void_p(), ctypes.c_int64()
+        _lib.check(_lib.load().gator_smpl_workspace(self._ctx, ctypes.byref(base), ctypes.byref(cap)), 'gator_smpl_workspace')
+        return base.value or 0, cap.value
+
+    def _arg(self, x, width, name, B):
+        if x is None:
+            return None
+        if not x.is_cuda or x.device != self.device:
+            raise RuntimeError('SMPLLayer: %s must live on %s' % (name, self.device))
+        x = x.contiguous().float()
+        if x.dim() != 2 or x.shape != (B, width):
+            raise ValueError('SMPLLayer: %s must be [%d,%d], got %s' % (name, B, width, tuple(x.shape)))
+        return x
+
+    def forward(self, th_pose_axisang, th_betas=None, th_trans=None, want_verts=True, want_joints=True):
+        if th_pose_axisang.dim() != 2:
+            raise ValueError('SMPLLayer: pose must be [B,%d], got %s' % (self.num_joints * 3, tuple(th_pose_axisang.shape)))
+        B = th_pose_axisang.shape[0]
+        pose = self._arg(th_pose_axisang, self.num_joints * 3, 'pose', B)
+        betas = self._arg(th_betas, self.num_betas, 'betas', B) if self.num_betas else None
+        trans = self._arg(th_trans, 3, 'trans', B)
+        center = -1 if (self.center_idx is None or trans is not None) else int(self.center_idx)
+        verts = torch.empty((B, self.num_verts, 3), device=self.device, dtype=torch.float32) if want_verts else None
+        joints = torch.empty((B, self.num_joints, 3), device=self.device, dtype=torch.float32) if want_joints else None
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(self.device):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(_lib.load().gator_smpl_forward_f32(self._ctx, ptr(pose), ptr(betas), ptr(trans), B, center, self.out_scale, ptr(verts),
+                                                          ptr(joints), st), 'gator_smpl_forward_f32')
+        return verts, joints
+
+    __call__ = forward
+
+
+def get_smpl_coord(layer, pose, shape, trans=None):
+    """The datasets' get_smpl_coord, batched (data/COCO/dataset.py:147-166, data/AMASS/dataset.py:199-213): a shape with any |beta| > 3
+    becomes the mean shape, the layer runs with millimetre output ((x + trans) * 1000, trans in metres), and the five face key-point
+    vertices are appended to the joints (lib/smpl.py:22-36).  -> (mesh [B,NV,3], joints [B,NJ+5,3]) in mm."""
+    if shape is not None:
+        shape = shape.float()
+        shape = torch.where((shape.abs() > 3).any(dim=1, keepdim=True), torch.zeros_like(shape), shape)
+    saved = layer.out_scale
+    layer.out_scale = 1000.0
+    try:
+        mesh, joints = layer(pose, shape, trans)
+    finally:
+        layer.out_scale = saved
+    idx = torch.as_tensor(FACE_KPS_VERTEX, device=mesh.device)
+    return mesh, torch.cat([joints, mesh[:, idx]], 1)
+
+
+def targets_from_smpl(layer, pose, shape, trans, regressor_h36m, regressor_coco=None, input_joint_name='human36'):
+    """The un-augmented tail of the datasets' __getitem__ (data/AMASS/dataset.py:252-265,301) on the device: mesh and joints from the
+    layer in mm, the H36M (and COCO + pelvis + neck) joints regressed from the mesh, everything root-relative.
+    regressor_*: gator_amd.eval.JointRegressor.  -> the dict Trainer.step takes: 'mesh' [B,6890,3] in metres, 'reg_pose3d' [B,17,3]
+    and 'lift_pose3d' [B,17|19,3] in mm.  The camera-frame root rotation, augmentation and noise stay with the caller."""
+    mesh, _ = get_smpl_coord(layer, pose, shape, trans)
+    h36m = regressor_h36m(mesh)
+    root = h36m[:, :1]
+    if input_joint_name == 'coco':
+        if regressor_coco is None:
+            raise ValueError("targets_from_smpl: input_joint_name 'coco' needs regressor_coco")
+        coco = regressor_coco(mesh)
+        pelvis = (coco[:, 11:12] + coco[:, 12:13]) * 0.5          # add_pelvis_and_neck, data/AMASS/dataset.py:215-227
+        neck = (coco[:, 5:6] + coco[:, 6:7]) * 0.5
+        coco = torch.cat([coco, pelvis, neck], 1)
+        lift = coco - coco[:, -2:-1]
+    elif input_joint_name == 'human36':
+        lift = h36m - root
+    else:
+        raise ValueError("targets_from_smpl: input_joint_name is 'coco' or 'human36', got %r" % (input_joint_name,))
+    return {'mesh': (mesh - root) / 1000, 'reg_pose3d': h36m - root, 'lift_pose3d': lift}

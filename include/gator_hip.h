@@ -258,6 +258,44 @@ int gator_fit_camera_f32(const float* joints3d, int32_t batch, int32_t n_joint_i
                          const double* lrs, int32_t n_schedule, const float* bbox, float img_w, float img_h, float* cam,
                          float* loss, float* orig_cam, void* stream);
 
+/* The SMPL body-model layer (smplpytorch/pytorch/smpl_layer.py:65-158), batched, on the device: what every training dataset of the
+ * reference calls at batch 1 on the CPU to build its target mesh (data/AMASS/dataset.py:182-213).  The model's arrays come from the
+ * caller (the weights are licence-gated and are no part of this library); all six are HOST pointers, copied and packed at create:
+ *     v_template [NV,3]   shapedirs [NV,3,NB] (may be NULL when NB = 0)   posedirs [NV,3,(NJ-1)*9]   weights [NV,NJ]
+ *     j_regressor [NJ,NV] dense   parents int32 [NJ]: parents[j] < j for j >= 1, parents[0] is ignored (the model files hold 2^32-1)
+ * Limits: NV >= 1, 2 <= NJ <= 32, 0 <= NB <= 16 (SMPL: 6890 / 24 / 10; MANO's 778 / 16 / 10 arrays are accepted as well).
+ * struct_size = sizeof of the struct below.  Anything else is GATOR_EINVAL, decided on the host before any device work.  The ctx is
+ * created on the current device; it owns the packed model and a workspace (the samples' coefficient rows and skinning transforms)
+ * that grows only when a larger batch arrives. */
+typedef struct gator_smpl gator_smpl;
+typedef struct {
+    int32_t struct_size, n_verts, n_joints, n_betas;
+    const float* v_template;
+    const float* shapedirs;
+    const float* posedirs;
+    const float* weights;
+    const float* j_regressor;
+    const int32_t* parents;
+} gator_smpl_model;
+int gator_smpl_create(const gator_smpl_model* model, gator_smpl** out);
+int gator_smpl_destroy(gator_smpl* ctx);
+
+/* pose [batch, NJ*3] axis-angle, betas [batch, NB] or NULL (the template shape), trans [batch, 3] or NULL -> verts [batch, NV, 3] and
+ * joints [batch, NJ, 3], either may be NULL; device pointers.
+ *     out = (layer output + trans - centre) * out_scale
+ * trans in the layer's unit (metres), out_scale 1 or 1000 (the datasets' `*= 1000` after their translation); center_idx >= 0 subtracts
+ * that joint from both outputs and goes with trans = NULL only (the layer centres when the whole batch's trans is numerically zero; here
+ * the argument decides, not device data, so nothing synchronises); center_idx < 0: no centring.
+ * Rodrigues as the layer has it: angle = |axisang + 1e-8|, normalised quaternion -- the all-zero pose is the identity, not NaN.
+ * batch = 0 is a no-op.  A repeated call at a batch no larger than an earlier one allocates nothing, never synchronises the host and can
+ * be captured into a graph.  A sample's result does not depend on the batch around it (bit for bit); a non-finite pose or beta makes
+ * that sample's outputs non-finite and changes no other sample.  There is no device status. */
+int gator_smpl_forward_f32(gator_smpl* ctx, const float* pose, const float* betas, const float* trans, int32_t batch,
+                           int32_t center_idx, float out_scale, float* verts, float* joints, void* stream);
+
+/* Test hook: the base of the ctx's workspace and the batch it holds (0 / NULL before the first forward). */
+int gator_smpl_workspace(const gator_smpl* ctx, const void** base, int64_t* capacity);
+
 /* Multi-GPU: samples are independent, the batch is sharded contiguously over one process per GPU, and the path's one
  * collective is the all-gather of the predicted vertices [B/N,6890,3] (+ pose3d [B/N,J,3]) over xGMI.  gator_amd/parallel.py issues
  * it through torch.distributed ("nccl" = RCCL); these entry points do the same on RCCL directly for hosts without torch:
