@@ -803,6 +803,7 @@ int fused_set_encoder(gator_ctx* c, int mode) {
 int fused_forward_joints(gator_ctx* c, const float* pose2d, int B, float* joints, float* pose3d, float* verts, void* stream) {
     FusedState* f = c->fused;
     if (!f || f->jr_nnz == 0) return fail(GATOR_EINVAL, "gator_forward_joints_f32: call gator_set_joint_regressor first");
+    if (f->opt.up_x3 == 0) return fail(GATOR_EUNSUPPORTED, "gator_forward_joints_f32 needs the split-precision vertex regressor");      // before anything is queued
     WsScope ws(f, 0);
     return fused_forward_one(c, pose2d, B, verts, pose3d, stream, false, joints);
 }

@@ -260,8 +260,10 @@ int pack_upsample_x2(const float* up_w, void* dst, float* unscale, void* stream)
         int e;
         (void)std::frexp(wmax, &e);                  // wmax = m * 2^e, m in [0.5, 1)  ->  wmax * 2^(14 - e) in [2^13, 2^14)
         shift = 14 - e;
-        if (shift > 24) shift = 24;                  // all-tiny weights: any scale keeps them normal enough
-        if (shift < -16) shift = -16;
+        // the clamps only keep 2^shift and the epilogue's 2^-(shift + 4) normal floats; every fp32 weight image with max|w| >= 2^-104
+        // gets its full scale (a tighter clamp leaves small weights fp16-subnormal: finite results with a few bits of the weights)
+        if (shift > 118) shift = 118;
+        if (shift < -118) shift = -118;
     }
     const int64_t pairs = (int64_t)upsample_x2_weight_elems() / 1024;
     k_pack_up_x2<<<(unsigned)((pairs * 512 + 255) / 256), 256, 0, st>>>(up_w, (_Float16*)dst, pairs, std::ldexp(1.0f, shift));
