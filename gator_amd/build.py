@@ -14,10 +14,8 @@ FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-ffp-contract=o
          '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC]
 # Measured on gfx950 (tools/microbench/coissue.hip): up to six plain VALU instructions (v_fma_f32, v_cvt_pk_bf16_f32, v_cndmask
 # ...) issue in the shadow of one bf16 MFMA for ~0.6 cycles each, while a v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 never hides
-# and adds 6-8 cycles.  Building the MFMA kernels without the packed forms (the flags below) was tried and is NOT used: the
-# VALU-bound parts (exact GELU, operand splits) lose more than the MFMA-adjacent parts gain (1.00 -> 1.03 ms per step).
-NO_PK = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
-NO_PK_SOURCES = tuple(x for x in os.environ.get('GATOR_NO_PK', '').split(',') if x)
+# and adds 6-8 cycles.  Building the MFMA kernels without the packed forms (-target-feature -packed-fp32-ops) was tried and is not
+# kept: the VALU-bound parts (exact GELU, operand splits) lose more than the MFMA-adjacent parts gain (1.00 -> 1.03 ms per step).
 
 
 def _stale(target, deps):
@@ -51,10 +49,10 @@ def build(force=False, verbose=True, diag=False):
         # the per-source extra flags are part of an object's identity: a stamp beside it records them, and a change (set or unset)
         # forces a rebuild -- an A/B object is never silently reused by a production build, nor the other way round
         stamp = obj + '.flags'
-        want = ' '.join(extra + (NO_PK if s in NO_PK_SOURCES else []))
+        want = ' '.join(extra)
         have = open(stamp).read() if os.path.exists(stamp) else ''
         if force or want != have or _stale(obj, [src] + hdrs):
-            cmd = [hipcc] + FLAGS + extra + (['-DGATOR_DIAG=1'] if diag else []) + (NO_PK if s in NO_PK_SOURCES else []) + \
+            cmd = [hipcc] + FLAGS + extra + (['-DGATOR_DIAG=1'] if diag else []) + \
                 (['-x', 'hip', '-Rpass-analysis=kernel-resource-usage'] if is_hip else []) + ['-c', src, '-o', obj]
             if verbose:
                 print(' '.join(cmd), flush=True)

@@ -717,7 +717,7 @@ static int fused_forward_one(gator_ctx* c, const float* pose2d, int B, float* ve
     const int n_tail = fused_tail ? n_tiled : B;
     if (n_tail > 0) {   // lifter + MDR joint tokens as two batched launches (gat_tail.hip)
         StageTimer tm(c, "gat_tail", stream);
-        rc = launch_gat_tail(c, f, pose2d, f->ws->feat, n_tail, pose3d, stream, true, !fused_tail);
+        rc = launch_gat_tail(c, f, pose2d, f->ws->feat, n_tail, pose3d, stream, !fused_tail);
         if (rc) return rc;
     }
     c->set_tap(TAP_FEAT, f->ws->feat, (int64_t)B * c->J * kC);

@@ -179,7 +179,7 @@ int gat_tiled_samples_per_wg(int J);
 int launch_gat_tiled(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* feat, void* stream, int B_total = 0, bool half16 = false);
 // gat_tail.hip
 size_t gat_tail_part_floats(int B, int J);
-int launch_gat_tail(gator_ctx* c, FusedState* f, const float* pose2d, const float* feat, int B, float* x_out, void* stream, bool joint, bool zero_ctr = true);
+int launch_gat_tail(gator_ctx* c, FusedState* f, const float* pose2d, const float* feat, int B, float* x_out, void* stream, bool zero_ctr = true);
 // upsample_bf16.hip
 size_t upsample_bf16_weight_elems();
 size_t upsample_bf16_vcp_elems(int B);

@@ -49,10 +49,7 @@ namespace gator {
 namespace {
 
 constexpr float kLog2e8 = 1.4426950408889634f;
-#ifndef GAT8_NT
-#define GAT8_NT 5
-#endif
-constexpr int kNT = GAT8_NT;                            // weight tiles in flight per product wave.  6 (one dummy tile per block, +28 VGPRs) was measured:
+constexpr int kNT = 5;                                  // weight tiles in flight per product wave.  6 (one dummy tile per block, +28 VGPRs) was measured:
                                                         // no change (188 - 192 us either way on one box), so the stream is not short of bytes in flight
 constexpr int kUseTiles = 65;                           // q k v h0 h1 proj lin0 (4 each) + lin1 (1) + back (4) + fc1 (16) + fc2 (16)
 constexpr int kPadTiles = (kNT - kUseTiles % kNT) % kNT;       // dummy tiles behind a block so that every block starts at slot 0
@@ -79,7 +76,6 @@ struct Gat8Tail {
     int ctr_B;                              //           ... of a forward of ctr_B samples (mdr_ctr_words)
     const float *jf5, *jf_h3, *jf_b, *posj_T;      // get_joint_feature: columns 0..4 as [5][64], columns 5..132 as H3 tiles [2][4], bias; pos_j tiles
     const float *j_n1w[3], *j_n1b[3], *j_wk_h3[3], *j_wv_h3[3];      // per LBF layer: norm1, wk / wv as H3 tiles [2][2] (the MDR layers' own weight image)
-    const float *jf_p, *j_wk_p[3], *j_wv_p[3];     // the same weights as packed fp32 tiles (GAT8_TAIL_F32: fp32-input MFMA forms of the two linears)
     float jf_inv, kv_inv;                          // 1 / (16 x 2^weight shift) of the two H3 weight sets (x3_common.h: four-product linears)
 #ifdef GATOR_DIAG
     unsigned long long* tstamps;                   // [8 waves][8] s_memtime stamps of workgroup B/2's epilogue (GATOR_GAT_STAMPS)
@@ -608,7 +604,7 @@ __device__ __forceinline__ void skip_pad(WT (&W)[kNT], const float* __restrict__
 //                six waves, their weight tiles requested behind the last lifter rows (same operand tiles out as k_gat_joint: two fp16
 //                planes of 16 x value).  These token-wise linears run as every other one of the
 //                default arithmetic does -- weights exact on three fp16 planes, activations on two, four partial products -- instead of
-//                k_gat_joint's fp32-input MFMAs: measured with the MFMAs cut out (GAT8_TAIL_CUT), the 32-MFMA fp32 chains of the K / V jobs
+//                k_gat_joint's fp32-input MFMAs: measured with the MFMAs cut out, the 32-MFMA fp32 chains of the K / V jobs
 //                alone were 6.5 us of the epilogue's 15.
 // LDS: the operand tiles A | Bq are dead after barrier 20 of the last block.
 constexpr int kTP = kA;                                 // the joint tokens without their pose3d columns (2 channel blocks, token on the lane)
@@ -618,12 +614,6 @@ constexpr int kTXO = kTVJ + 768;                        // pose3d of the sample 
 enum { TVJ_JFB = 0, TVJ_JF5 = 64, TVJ_N1W = 384, TVJ_N1B = 576, TVJ_TOTAL = 768 };      // jf bias | jf columns 0..4 [5][64] | norm1 w / b [3 layers][64]
 static_assert(kTXO + 64 <= kR, "the epilogue's LDS lives in the dead operand tiles");
 
-#ifndef GAT8_TAIL_F32
-#define GAT8_TAIL_F32 0              // 1: joint-token linear on the fp32-input MFMA (exact products), 2: the K / V jobs too  (A/B of the epilogue's arithmetic)
-#endif
-#ifndef GAT8_TAIL_CUT
-#define GAT8_TAIL_CUT 0              // timing experiments only (tools/build_variant.py ... -DGAT8_TAIL_CUT=n): 1 no lifter loads, 2 no joint-token MFMAs, 4 no K / V MFMAs, 8 lifter only, 16 no L2 warm-up of the lifter weight
-#endif
 __device__ __forceinline__ float dpp_add(float s, int ctrl_tag) {
     const int u = __builtin_bit_cast(int, s);
     int m;
@@ -648,7 +638,7 @@ template <int NI>
 __device__ __forceinline__ void lift_load(LiftRow<NI>& r, const float* __restrict__ wrow, int lane, bool live) {
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < NI; ++i) r.w[i] = (!(GAT8_TAIL_CUT & 1) && live && (i < NI - 1 || lane < 32)) ? *reinterpret_cast<const f32x4*>(wrow + 256 * i + 4 * lane) : z;
+    for (int i = 0; i < NI; ++i) r.w[i] = (live && (i < NI - 1 || lane < 32)) ? *reinterpret_cast<const f32x4*>(wrow + 256 * i + 4 * lane) : z;
 }
 template <int NI>
 __device__ __forceinline__ float lift_dot(const LiftRow<NI>& r, const f32x4 (&f)[NI]) {
@@ -678,7 +668,7 @@ __device__ __forceinline__ void gat8_tail(const Gat8Tail& tl, const float* pose2
     float* P = lds + kTP;
     const float* VJ = lds + kTVJ;
     float* XO = lds + kTXO;
-    const bool joint = tl.jkv != nullptr && !(GAT8_TAIL_CUT & 8);
+    const bool joint = tl.jkv != nullptr;
     // who does what besides its lifter rows: product waves 0 / 1 the feat columns of the joint-token linear (channel block w, all of K = 128);
     // the other six waves two K / V jobs each
     const bool jf_wave = !HELPER && w < 2 && joint;
@@ -760,21 +750,13 @@ __device__ __forceinline__ void gat8_tail(const Gat8Tail& tl, const float* pose2
         // jf without its pose3d columns: bias + pos_j + feat columns (GATOR.py:19, MDR.py:130-134), channel block w, token on the lane
         f32x16 acc = zero16(), acs = zero16();
         const f32x16 init = chanvec_lds(VJ, TVJ_JFB + 32 * w, h) + load_block(lds + kTPosj + w * kTile, lane);
-        if constexpr ((GAT8_TAIL_F32 & 1) != 0) {
-            mma2_T(load_wtile(tl.jf_p, w * 4 + 0, lane), load_block(X, lane), acc, load_wtile(tl.jf_p, w * 4 + 1, lane), load_block(X + kTile, lane), acs);
-            mma2_T(load_wtile(tl.jf_p, w * 4 + 2, lane), load_block(X + 2 * kTile, lane), acc, load_wtile(tl.jf_p, w * 4 + 3, lane), load_block(X + 3 * kTile, lane), acs);
-            store_block(P + w * kTile, lane, (acc + acs) + init);
-        } else {
-            if (!(GAT8_TAIL_CUT & 2)) {
 #pragma unroll
-                for (int kb = 0; kb < 4; ++kb) {
-                    const X2 fx2 = x2_split(load_block(X + kb * kTile, lane) * 16.0f);
-                    acs = h3_mma_wa_small(wt[kb], fx2, acs);
-                    acc = h3_mma_wa_main(wt[kb], fx2, acc);
-                }
-            }
-            store_block(P + w * kTile, lane, fma16(acc + acs, tl.jf_inv, init));
+        for (int kb = 0; kb < 4; ++kb) {
+            const X2 fx2 = x2_split(load_block(X + kb * kTile, lane) * 16.0f);
+            acs = h3_mma_wa_small(wt[kb], fx2, acs);
+            acc = h3_mma_wa_main(wt[kb], fx2, acc);
         }
+        store_block(P + w * kTile, lane, fma16(acc + acs, tl.jf_inv, init));
         wt[0] = job_tile(job0, 0);                             // (its own K / V job's tiles, in flight across the barrier)
         wt[1] = job_tile(job0, 1);
     }
@@ -814,34 +796,14 @@ __device__ __forceinline__ void gat8_tail(const Gat8Tail& tl, const float* pose2
         float* out = tl.jkv + (((size_t)b * 3 + li) * 4 + kv * 2 + nb) * kTile;
         const H3 &k0 = wt[2 * q], &k1 = wt[2 * q + 1];
         f32x16 r0 = zero16(), r1 = zero16();                   // r1: the cross products of both k blocks, r0: the hi x hi ones (x3_common.h on the order)
-        if constexpr ((GAT8_TAIL_F32 & 2) != 0) {
-            const float* wp32 = kv ? tl.j_wv_p[li] : tl.j_wk_p[li];
-            const WTile t0 = load_wtile(wp32, nb * 2, lane), t1 = load_wtile(wp32, nb * 2 + 1, lane);
-            if (kv == 0) {
-                mma2_T(t0, fz0, r0, t1, fz1, r1);
-                r0 += r1;
-                if (tok >= J) r0 = zero16();
-            } else {
-                mma2_C(t0, fz0, r0, t1, fz1, r1);
-                r0 += r1;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) r0[r] = (kap(r) + 4 * h < J) ? r0[r] : 0.f;
-            }
-            x2_store(out, lane, x2_split(r0 * 16.0f));
-            continue;
-        }
         if (kv == 0) {
-            if (!(GAT8_TAIL_CUT & 4)) {
-                r1 = h3_mma_wa_small(k1, z1, h3_mma_wa_small(k0, z0, r1));
-                r0 = h3_mma_wa_main(k1, z1, h3_mma_wa_main(k0, z0, r0));
-            }
+            r1 = h3_mma_wa_small(k1, z1, h3_mma_wa_small(k0, z0, r1));
+            r0 = h3_mma_wa_main(k1, z1, h3_mma_wa_main(k0, z0, r0));
             r0 += r1;
             if (tok >= J) r0 = zero16();                       // joints >= J: zero rows (masked in the softmax anyway)
         } else {
-            if (!(GAT8_TAIL_CUT & 4)) {
-                r1 = h3_mma_aw_small(z1, k1, h3_mma_aw_small(z0, k0, r1));
-                r0 = h3_mma_aw_main(z1, k1, h3_mma_aw_main(z0, k0, r0));
-            }
+            r1 = h3_mma_aw_small(z1, k1, h3_mma_aw_small(z0, k0, r1));
+            r0 = h3_mma_aw_main(z1, k1, h3_mma_aw_main(z0, k0, r0));
             r0 += r1;
 #pragma unroll
             for (int r = 0; r < 16; ++r) r0[r] = (kap(r) + 4 * h < J) ? r0[r] : 0.f;
@@ -1105,7 +1067,7 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
             // The epilogue's weights are HBM-cold like the streams (the lifter's 444 KB at J = 17, the joint-token linear's and the three
             // layers' wk / wv H3 tiles): every workgroup of the XCD would miss on them together.  One block ahead -- the last block has no
             // next block to warm -- this helper pulls its share of each region into the XCD's L2, one dword per 128-byte line.
-            if (!(GAT8_TAIL_CUT & 16) && bi + 1 == kDepth && a.tl.warm_n > 0) {
+            if (bi + 1 == kDepth && a.tl.warm_n > 0) {
                 const int idx = ((b >> 3) % a.tl.warm_n) * 4 + w, parts = a.tl.warm_n * 4;
                 auto touch = [&](const float* base, int bytes) {
                     const int share = ((bytes / parts + 127) / 128) * 128;
@@ -1561,8 +1523,6 @@ int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* 
         Gat8Tail& tl = a.tl;
         tl.lifter_w = w.lifter_w; tl.lifter_b = w.lifter_b; tl.x_out = tail_x_out; tl.jkv = tail_jkv;
         if (ctr_B > 0 && f->opt.mdr_persist != 0) { tl.mdr_ctr = f->ws->mdr_ctr; tl.ctr_B = ctr_B; f->ws->mdr_ctr_clean = true; }
-        tl.jf_p = f->jfeat128_p;
-        for (int i = 0; i < 3; ++i) { tl.j_wk_p[i] = f->lay[i].wk; tl.j_wv_p[i] = f->lay[i].wv; }
         tl.jf5 = f->jfeat5; tl.jf_h3 = f->jf128_h3; tl.jf_b = w.jfeat_b; tl.posj_T = f->posj_T;
         auto h3_of = [&](const float* t) { return f->wxbuf + (size_t)(t - f->lay[0].wq) / kTile * kTileX3; };      // the MDR layers' H3 image mirrors wbuf tile for tile
         for (int i = 0; i < 3; ++i) { tl.j_n1w[i] = w.lay[i].n1w; tl.j_n1b[i] = w.lay[i].n1b; tl.j_wk_h3[i] = h3_of(f->lay[i].wk); tl.j_wv_h3[i] = h3_of(f->lay[i].wv); }

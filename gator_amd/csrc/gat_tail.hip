@@ -46,7 +46,7 @@ __global__ __launch_bounds__(128) void k_gat_lifter(const LifterArgs a) {
 
 struct JointTailArgs {
     const float *pose2d, *feat, *part, *lifter_b;
-    float *x_out, *jkv;           // jkv == nullptr: lifter only (stand-alone GAT entry point)
+    float *x_out, *jkv;           // (launch_gat_tail always sets jkv; the kernel still skips the joint tokens where it is null)
     unsigned* mdr_ctr;            // non-null: zero k_mdr_persist's tickets and completion counts for the launch that follows (mdr_fused.hip)
     const float *jf5, *jf_p, *jf_b, *posj_T;       // get_joint_feature: columns 0..4 as [5][64], columns 5..132 packed [2][4], bias
     const float *j_n1w[3], *j_n1b[3], *j_wk_p[3], *j_wv_p[3];
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void k_gat_joint(const JointTailArgs a) {
 
 size_t gat_tail_part_floats(int B, int J) { return (size_t)((B + 31) / 32) * J * 2 * kTile; }
 
-int launch_gat_tail(gator_ctx* c, FusedState* f, const float* pose2d, const float* feat, int B, float* x_out, void* stream, bool joint, bool zero_ctr) {
+int launch_gat_tail(gator_ctx* c, FusedState* f, const float* pose2d, const float* feat, int B, float* x_out, void* stream, bool zero_ctr) {
     const Weights& w = c->w;
     const int J = c->J, MT = (B + 31) / 32;
     hipStream_t st = (hipStream_t)stream;
@@ -182,14 +182,11 @@ int launch_gat_tail(gator_ctx* c, FusedState* f, const float* pose2d, const floa
     k_gat_lifter<<<MT * J, 128, 0, st>>>(la);
     JointTailArgs a{};
     a.pose2d = pose2d; a.feat = feat; a.part = f->ws->lpart; a.lifter_b = w.lifter_b; a.x_out = x_out; a.B = B; a.J = J;
-    a.jkv = nullptr;
     a.mdr_ctr = nullptr;
     a.x2 = f->opt.mdr_x3 == 2;
-    if (joint) {
-        if (f->opt.mdr_persist != 0 && zero_ctr) { a.mdr_ctr = f->ws->mdr_ctr; f->ws->mdr_ctr_clean = true; }      // (!zero_ctr: k_gat8's fused tail zeroes them for the whole forward)
-        a.jkv = f->ws->jkv; a.jf5 = f->jfeat5; a.jf_p = f->jfeat128_p; a.jf_b = w.jfeat_b; a.posj_T = f->posj_T;
-        for (int i = 0; i < 3; ++i) { a.j_n1w[i] = w.lay[i].n1w; a.j_n1b[i] = w.lay[i].n1b; a.j_wk_p[i] = f->lay[i].wk; a.j_wv_p[i] = f->lay[i].wv; }
-    }
+    if (f->opt.mdr_persist != 0 && zero_ctr) { a.mdr_ctr = f->ws->mdr_ctr; f->ws->mdr_ctr_clean = true; }      // (!zero_ctr: k_gat8's fused tail zeroes them for the whole forward)
+    a.jkv = f->ws->jkv; a.jf5 = f->jfeat5; a.jf_p = f->jfeat128_p; a.jf_b = w.jfeat_b; a.posj_T = f->posj_T;
+    for (int i = 0; i < 3; ++i) { a.j_n1w[i] = w.lay[i].n1w; a.j_n1b[i] = w.lay[i].n1b; a.j_wk_p[i] = f->lay[i].wk; a.j_wv_p[i] = f->lay[i].wv; }
     k_gat_joint<<<B, 256, 0, st>>>(a);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;

@@ -29,9 +29,6 @@ namespace gator {
 namespace {
 
 constexpr float kLog2e = 1.4426950408889634f;
-#ifndef MDR_X1_PIPE
-#define MDR_X1_PIPE 1      // the one-plane form's attention and Mlp loops software-pipelined inside the wave (0: the plain loops, A/B)
-#endif
 
 // Diagnostic library only (GATOR_MDR_CUT, time-only experiments: results are meaningless): bit 0 = every weight load of a matrix reads its
 // tile 0, bit 1 = every K / V load of the 431-key attention reads key tile 0 -- the loads stay, their L2 -> L1 traffic goes (L1 hits).
@@ -361,154 +358,19 @@ __device__ __forceinline__ f32x16 self_attention_head_x2(const float* __restrict
 }
 
 
-// ---- the same loop, software-pipelined by one key tile inside the wave (round 5; MDR_ATTN_PIPE=1, tools/microbench/attn_pipe.hip) ------
-//     block A:  lo plane of P[kt-1] (deferred), O += V[kt-1] P[kt-1] (hi.hi first: it needs no lo plane)  ||  row maximum of S[kt]
-//     rescale (rare, wave-uniform)
-//     block B:  S[kt+1] = K[kt+1] Q  ||  exp2, row sum, hi plane of P[kt]
-// so that every MFMA is followed IN THE WAVE'S OWN STREAM by independent vector work.  Same arithmetic, same order of every
-// accumulation: bitwise the results of self_attention_head_x2.  Alone the loop takes 16 % fewer cycles (776 -> 649 per key tile
-// and SIMD) -- and the chip gives most of it back as clock on real data (profiles/r05_microbench_attn_pipe.txt).
-#ifndef MDR_ATTN_PIPE
-#define MDR_ATTN_PIPE 0
-#endif
-template <bool kActScale16>
-__device__ __forceinline__ f32x16 self_attention_head_x2_pipe(const float* __restrict__ qt, const float* __restrict__ kbase,
-                                                              const float* __restrict__ vbase, int lane) {
-    const int h = lane >> 5;
-    const X2 qx = x2_load(qt, lane);
-    f32x16 O = zero16(), O2 = zero16();
-    float m = -1e30f, l = 0.f;
-    X2 kb0 = x2_load(kbase, lane), kb1 = x2_load(kbase + (size_t)MDR_KVIDX(1) * 2 * kTile, lane);
-    X2 vb0 = x2_load(vbase, lane), vb1 = x2_load(vbase + (size_t)MDR_KVIDX(1) * 2 * kTile, lane);
-    f32x16 S0 = x2_mma(kb0, qx, zero16()), S1 = zero16();          // S[0]; "P[-1]" = 0 in fp32 and in its hi plane
-    kb0 = x2_load(kbase + (size_t)MDR_KVIDX(2) * 2 * kTile, lane);
-    f16x8 ph[2] = {f16x8(0), f16x8(0)};
-    auto step = [&](auto last_, const int kt, f32x16& Sc, f32x16& Sp, X2& Vp, X2& Kn) {
-        constexpr bool LAST = decltype(last_)::value;
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (LAST) {                                      // keys 431..447 do not exist
-#pragma unroll
-            for (int r = 0; r < 16; ++r) if (kap(r) + 4 * h >= kV - 32 * (kVT - 1)) Sc[r] = -1e30f;
-        }
-        f16x8 plo[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) plo[s][j] = (_Float16)(Sp[8 * s + j] - (float)ph[s][j]);
-        O = GATOR_MFMA_F16(Vp.p[0][0], ph[0], O);
-        O = GATOR_MFMA_F16(Vp.p[0][1], ph[1], O);
-        O2 = GATOR_MFMA_F16(Vp.p[1][0], ph[0], O2);
-        O2 = GATOR_MFMA_F16(Vp.p[0][0], plo[0], O2);
-        O2 = GATOR_MFMA_F16(Vp.p[1][1], ph[1], O2);
-        O2 = GATOR_MFMA_F16(Vp.p[0][1], plo[1], O2);
-        float bm = -1e30f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) bm = fmaxf(bm, Sc[r]);
-        bm = fmaxf(bm, xhalf(bm));
-        const bool calm = __all(bm <= m + 2048.0f);
-        __builtin_amdgcn_sched_barrier(0);
-        Vp = x2_load(vbase + (size_t)MDR_KVIDX(kt + 1 < kVT ? kt + 1 : kVT - 1) * 2 * kTile, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!calm) {
-            const float mn = fmaxf(m, bm);
-            const float al = __builtin_amdgcn_exp2f((m - mn) * 0.00390625f);
-            O = O * al;
-            O2 = O2 * al;
-            l *= al;
-            m = mn;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        Sp = x2_mma(Kn, qx, zero16());
-        const float off = 6.0f - m * 0.00390625f;
-        float ps = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float pe = __builtin_amdgcn_exp2f(fmaf(Sc[r], 0.00390625f, off));
-            Sc[r] = pe;
-            ps += pe;
-        }
-        l += ps;
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ph[s][j] = (_Float16)Sc[8 * s + j];
-        __builtin_amdgcn_sched_barrier(0);
-        Kn = x2_load(kbase + (size_t)MDR_KVIDX(kt + 3 < kVT ? kt + 3 : kVT - 1) * 2 * kTile, lane);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-#pragma unroll 1
-    for (int kt = 0; kt < kVT - 2; kt += 2) {
-        step(std::false_type(), kt, S0, S1, vb1, kb1);
-        step(std::false_type(), kt + 1, S1, S0, vb0, kb0);
-    }
-    step(std::false_type(), kVT - 2, S0, S1, vb1, kb1);
-    step(std::true_type(), kVT - 1, S1, S0, vb0, kb0);
-    {   // P[13] V[13]: fp32 probabilities in S1, V[13] in vb1
-        f16x8 plo[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) plo[s][j] = (_Float16)(S1[8 * s + j] - (float)ph[s][j]);
-        O = GATOR_MFMA_F16(vb1.p[0][0], ph[0], O);
-        O = GATOR_MFMA_F16(vb1.p[0][1], ph[1], O);
-        O2 = GATOR_MFMA_F16(vb1.p[1][0], ph[0], O2);
-        O2 = GATOR_MFMA_F16(vb1.p[0][0], plo[0], O2);
-        O2 = GATOR_MFMA_F16(vb1.p[1][1], ph[1], O2);
-        O2 = GATOR_MFMA_F16(vb1.p[0][1], plo[1], O2);
-    }
-    l += xhalf(l);
-    return (O + O2) * (((kActScale16 ? 16.0f : 1.0f) / kX2V) / l);
-}
-
 // ---- ONE fp16 plane ("X1", BASELINE config 3: the MDR layers in 16-bit operand mode, XA == 3) --------------------------------------------
 // Activations, Q, K, V and the probabilities are ONE fp16 plane of 16 x value (64 x for P): no split, 2 KiB tiles, 2 MFMAs per 32-deep
 // product in the attention cores (against 6) and 4 per token-wise product (weights on their two leading fp16 planes, 22 bits: against
 // 8); accumulation, softmax, norms, GELU and the residual stream stay fp32.  What that costs in accuracy is the activation rounding
 // (2^-12 relative per operand element): tools/emulate_16bit.py, profiles/r05_emulate_16bit.txt (sub-millimetre vertices).
 constexpr int kTileX1 = kTile / 2;
-// One key tile.  The VALU work per tile is what bounds this form (4 MFMAs against ~50 vector instructions), so the softmax is cut to
-// exp2 + row sum + one conversion per pair:
+// One key tile (the step of self_attention_head_x1).  The VALU work per tile is what bounds this form (4 MFMAs against ~50 vector
+// instructions), so the softmax is cut to exp2 + row sum + one conversion per pair:
 //   * Q arrives scaled by log2(e) / sqrt(d_k) and K unscaled, so the MFMA delivers the score in the exp2 domain, and the running
-//     reference rides on the accumulator's initial value (Ci = 6 - m in every register: the 2^6 keeps P's fp16 image normal), so the
-//     exponent is S itself -- no scale / offset instruction per value;
+//     reference is one add per value (ci = 6 - m: the 2^6 keeps P's fp16 image normal);
 //   * no row maximum: the probabilities are non-negative, so "the lane's row sum < 2^15" proves every one of them is inside fp16's range;
 //     where that fails (first tile, a tile whose scores jump by 2^9, anything non-finite) the tile is redone the long way: raw scores,
 //     maximum, rescale of O and l, new reference.  Wave-uniform and rare.
-#define ATTN_TILE_X1(KT, KB, VB)                                                                            \
-    {                                                                                                       \
-        f32x16 S = x1_mma(KB, qx, Ci);        /* S^T[key][query] - m + 6, exp2 domain */                    \
-        if ((KT) == kVT - 1) {                                                                              \
-            _Pragma("unroll") for (int r = 0; r < 16; ++r)                                                  \
-                if (kap(r) + 4 * h >= kV - 32 * (kVT - 1)) S[r] = -1e30f;   /* keys 431..447 do not exist */ \
-        }                                                                                                   \
-        float ps = 0.f;                                                                                     \
-        _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                    \
-            S[r] = __builtin_amdgcn_exp2f(S[r]);                                                            \
-            ps += S[r];                                                                                     \
-        }                                                                                                   \
-        if (!__all(ps < 32768.0f)) {                                                                        \
-            f32x16 R = x1_mma(KB, qx, zero16());                                                            \
-            float bm = -1e30f;                                                                              \
-            _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                \
-                if ((KT) == kVT - 1 && kap(r) + 4 * h >= kV - 32 * (kVT - 1)) R[r] = -1e30f;                \
-                bm = fmaxf(bm, R[r]);                                                                       \
-            }                                                                                               \
-            bm = fmaxf(bm, xhalf(bm));                                                                      \
-            const float mn = fmaxf(m, bm);                                                                  \
-            const float al = __builtin_amdgcn_exp2f(m - mn);                                                \
-            O = O * al;                                                                                     \
-            l *= al;                                                                                        \
-            m = mn;                                                                                         \
-            Ci = f32x16(6.0f - m);                                                                          \
-            ps = 0.f;                                                                                       \
-            _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                \
-                S[r] = __builtin_amdgcn_exp2f(R[r] + Ci[r]);                                                \
-                ps += S[r];                                                                                 \
-            }                                                                                               \
-        }                                                                                                   \
-        l += ps;                                                                                            \
-        O = x1_mma(VB, x1_cvt(S), O);                                                                       \
-    }
 template <bool kActScale16>
 __device__ __forceinline__ f32x16 self_attention_head_x1(const float* __restrict__ qt, const float* __restrict__ kbase,
                                                          const float* __restrict__ vbase, int lane) {
@@ -516,14 +378,10 @@ __device__ __forceinline__ f32x16 self_attention_head_x1(const float* __restrict
     const X1 qx = x1_load(qt, lane);
     f32x16 O = zero16();
     float m = -1e30f, l = 0.f;
-#if !MDR_X1_PIPE
-    f32x16 Ci = f32x16(1e30f);                 // "6 - m" of an empty history: the first tile overflows its row sums and takes the long way
-#endif
-#if MDR_X1_PIPE
     // Software-pipelined by one key tile (unrolled by two: fixed register names): the RAW scores of tile kt + 1 are issued before the
-    // exponentials of tile kt, so the MFMAs run under the vector work of the same wave.  (Here the reference is added per value -- one
-    // v_add more than the accumulator-initial-value form below, which needs a 16-register tile per head on top of the two score tiles
-    // and spills; this form is bound by latency, not by its vector instruction count.)
+    // exponentials of tile kt, so the MFMAs run under the vector work of the same wave.  (The reference is added per value -- one
+    // v_add more than carrying it on the accumulator's initial value, which needs a 16-register tile per head on top of the two score
+    // tiles and spills; this form is bound by latency, not by its vector instruction count.)
     X1 kA = x1_load(kbase, lane), vA = x1_load(vbase, lane);
     X1 kB = x1_load(kbase + (size_t)MDR_KVIDX(1) * 2 * kTileX1, lane), vB = x1_load(vbase + (size_t)MDR_KVIDX(1) * 2 * kTileX1, lane);
     f32x16 SA = x1_mma(kA, qx, zero16()), SB;
@@ -575,22 +433,6 @@ __device__ __forceinline__ f32x16 self_attention_head_x1(const float* __restrict
     }
     step(std::integral_constant<int, 0>(), kVT - 2, SA, SB, kA, kB, vA);
     step(std::integral_constant<int, kVT - 1>(), kVT - 1, SB, SA, kB, kA, vB);
-#else
-    X1 kb = x1_load(kbase, lane), vb = x1_load(vbase, lane);
-#pragma unroll 1
-    for (int kt = 0; kt < kVT - 2; kt += 2) {
-        X1 kn = x1_load(kbase + (size_t)MDR_KVIDX(kt + 1) * 2 * kTileX1, lane), vn = x1_load(vbase + (size_t)MDR_KVIDX(kt + 1) * 2 * kTileX1, lane);
-        ATTN_TILE_X1(0, kb, vb)
-        kb = x1_load(kbase + (size_t)MDR_KVIDX(kt + 2) * 2 * kTileX1, lane);
-        vb = x1_load(vbase + (size_t)MDR_KVIDX(kt + 2) * 2 * kTileX1, lane);
-        ATTN_TILE_X1(0, kn, vn)
-    }
-    {
-        X1 kn = x1_load(kbase + (size_t)MDR_KVIDX(kVT - 1) * 2 * kTileX1, lane), vn = x1_load(vbase + (size_t)MDR_KVIDX(kVT - 1) * 2 * kTileX1, lane);
-        ATTN_TILE_X1(kVT - 2, kb, vb)
-        ATTN_TILE_X1(kVT - 1, kn, vn)
-    }
-#endif
     l += xhalf(l);
     return O * (((kActScale16 ? 16.0f : 1.0f) / kX2V) / l);
 }
@@ -790,10 +632,6 @@ template <int XA> __device__ __forceinline__ typename TokOp<XA>::A mk(const f32x
 // from an LDS table instead: 3 072 (value, forward difference) pairs on [-6, 6) in steps of 1 / 256, linear interpolation -- error of Phi
 // below 4.6e-7 (h^2 / 8 max|Phi''|), against 2.4e-4 |x| for the fp16 rounding that follows; |x| >= 6 clamps to Phi = 0 / 1 (exact to 1e-9).
 // Seven vector instructions and one ds_read_b64 per value instead of ~14 issue slots.  The fp32 configuration keeps the polynomial.
-#ifndef MDR_X1_GELU_TABLE
-#define MDR_X1_GELU_TABLE 1
-#endif
-constexpr bool kX1GeluTable = MDR_X1_GELU_TABLE != 0;
 constexpr int kGeluTab = 3072;
 __device__ __forceinline__ void gelu_table_fill(float* GT) {      // cooperative (256 threads); the caller puts a barrier behind it
     for (int e = threadIdx.x; e < kGeluTab; e += 256) {
@@ -1021,17 +859,10 @@ __device__ __forceinline__ void mdr_tile(const MdrArgs& a, const int id, const f
             att[1] = self_attention_head_x1<true>(a.q_in + (tile + 1) * TQ, a.k_in + ((size_t)b * kVT * 2 + 1) * TQ,
                                     a.v_in + ((size_t)b * kVT * 2 + 1) * TQ, lane);
         } else if constexpr (XA == 2) {
-#if MDR_ATTN_PIPE
-            att[0] = self_attention_head_x2_pipe<true>(a.q_in + (tile + 0) * TQ, a.k_in + ((size_t)b * kVT * 2 + 0) * TQ,
-                                    a.v_in + ((size_t)b * kVT * 2 + 0) * TQ, lane);
-            att[1] = self_attention_head_x2_pipe<true>(a.q_in + (tile + 1) * TQ, a.k_in + ((size_t)b * kVT * 2 + 1) * TQ,
-                                    a.v_in + ((size_t)b * kVT * 2 + 1) * TQ, lane);
-#else
             att[0] = self_attention_head_x2<true>(a.q_in + (tile + 0) * TQ, a.k_in + ((size_t)b * kVT * 2 + 0) * TQ,
                                     a.v_in + ((size_t)b * kVT * 2 + 0) * TQ, lane);
             att[1] = self_attention_head_x2<true>(a.q_in + (tile + 1) * TQ, a.k_in + ((size_t)b * kVT * 2 + 1) * TQ,
                                     a.v_in + ((size_t)b * kVT * 2 + 1) * TQ, lane);
-#endif
         } else if constexpr (XA == 1) {
             att[0] = self_attention_head_x3(a.q_in + (tile + 0) * TQ, a.k_in + ((size_t)b * kVT * 2 + 0) * TQ,
                                             a.v_in + ((size_t)b * kVT * 2 + 0) * TQ, lane);
@@ -1172,7 +1003,7 @@ __device__ __forceinline__ void mdr_tile(const MdrArgs& a, const int id, const f
         // XA 3 is a latency-bound kernel (waves parked or issue-stalled 64 % of their time, profiles/r05_pmc_config3_B256.txt): its loop is
         // software-pipelined by one chunk inside the wave -- fc1 of chunk c + 1 is issued BEFORE the bias + GELU + conversion of chunk c, so
         // the eight dependent MFMAs run under that vector work instead of in front of it, and fc2's two chains are interleaved.
-        if constexpr (XA == 3 && MDR_X1_PIPE) {
+        if constexpr (XA == 3) {
             f32x16 hn = lin2_T(A, y2, zero16());                                        // fc1, chunk 0
             A = ldw<XA>(w.fc1, 2, 3, lane);
             MDR_PIN();
@@ -1181,7 +1012,7 @@ __device__ __forceinline__ void mdr_tile(const MdrArgs& a, const int id, const f
                 f32x16 hdn = hn;
                 if (c < 7) hn = lin2_T(A, y2, zero16());                               // fc1, chunk c + 1: independent of everything below
                 hdn += chanvec_lds(VT, VO_FC1B + 32 * c, h);
-                if constexpr (kX1GeluTable) gelu_tile_table(hdn, inv, GT); else gelu_tile_scaled(hdn, inv);
+                gelu_tile_table(hdn, inv, GT);
                 const X1 hx = mk<XA>(hdn, inv);
                 __builtin_amdgcn_sched_barrier(0);
                 if (c < 6) A = ldw<XA>(w.fc1, 2 * (c + 2), 2 * (c + 2) + 1, lane); else if (c == 6) A = ldw<XA>(w.sa0, 0, 1, lane);
@@ -1213,12 +1044,8 @@ __device__ __forceinline__ void mdr_tile(const MdrArgs& a, const int id, const f
                 if (c < 7) A = ldw<XA>(w.fc1, 2 * (c + 1), 2 * (c + 1) + 1, lane); else A = ldw<XA>(w.sa0, 0, 1, lane);
                 MDR_PIN();
             }
-            if constexpr (XA == 3 && kX1GeluTable) gelu_tile_table(hdn, inv, GT); else if constexpr (H) gelu_tile_scaled(hdn, inv); else gelu_tile(hdn);
-            if constexpr (XA == 3) {
-                const X1 hx = mk<XA>(hdn, inv);
-                acc2[0][0] = g2_mma_wa(B.t[0], hx, acc2[0][0]);
-                acc2[1][0] = g2_mma_wa(B.t[1], hx, acc2[1][0]);
-            } else if constexpr (H) {
+            if constexpr (H) gelu_tile_scaled(hdn, inv); else gelu_tile(hdn);
+            if constexpr (H) {
                 const X2 hx = mk<XA>(hdn, inv);
                 acc2[0][0] = h3_mma_wa(B.t[0], hx, acc2[0][0]);
                 acc2[1][0] = h3_mma_wa(B.t[1], hx, acc2[1][0]);
@@ -1310,8 +1137,8 @@ template <int MODE, int XA>
 __global__ __launch_bounds__(256, 2) void k_mdr_layer(const MdrArgs a, int nwg) {
     __shared__ f32x4 park[XA != 0 ? kParkF4 : 1];
     __shared__ __attribute__((aligned(16))) float VT[VO_TOTAL];
-    __shared__ __attribute__((aligned(16))) float GT[XA == 3 && MODE < 2 && kX1GeluTable ? 2 * kGeluTab : 2];
-    if constexpr (XA == 3 && MODE < 2 && kX1GeluTable) gelu_table_fill(GT);
+    __shared__ __attribute__((aligned(16))) float GT[XA == 3 && MODE < 2 ? 2 * kGeluTab : 2];
+    if constexpr (XA == 3 && MODE < 2) gelu_table_fill(GT);
     mdr_stage_vectors<MODE, XA>(a, VT);
     __syncthreads();
     mdr_tile<MODE, XA>(a, xcd_remap(blockIdx.x, nwg) * 4 + (threadIdx.x >> 6), VT, park, GT,
@@ -1487,9 +1314,9 @@ template <int XA>
 __global__ __launch_bounds__(256, 2) void k_mdr_persist(const MdrPersistArgs p) {
     __shared__ f32x4 park[XA != 0 ? kParkF4 : 1];
     __shared__ __attribute__((aligned(16))) float VT[VO_TOTAL];
-    __shared__ __attribute__((aligned(16))) float GT[XA == 3 && kX1GeluTable ? 2 * kGeluTab : 2];
+    __shared__ __attribute__((aligned(16))) float GT[XA == 3 ? 2 * kGeluTab : 2];
     __shared__ int s_unit;
-    if constexpr (XA == 3 && kX1GeluTable) gelu_table_fill(GT);      // published by the first ticket's barriers
+    if constexpr (XA == 3) gelu_table_fill(GT);      // published by the first ticket's barriers
     const int B = p.st[0].B, lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     unsigned xcc;                                                // the XCD this workgroup REALLY runs on picks its queue
@@ -1672,9 +1499,6 @@ __device__ __forceinline__ double wave_sum64_f64(double s) {
 // weights, its token's 32 head features -- is issued before the first phase, and the phases run on registers and LDS only
 // (16 / 13 us).  That costs 196 VGPRs, one workgroup per CU: batches of more than two workgroups per CU take the rolled form
 // (same arithmetic in the same order, 2 workgroups per CU), which is the faster one there.
-#ifndef MDR_HEAD_CUT
-#define MDR_HEAD_CUT 0      // timing experiments only (tools/build_variant.py ... -DMDR_HEAD_CUT=n): 1 no conv FMAs, 2 no wave reductions, 4 no softmax-mix, 8 no conv-weight loads
-#endif
 template <int NT, bool HOIST>
 __global__ __launch_bounds__(NT, HOIST ? 2 : 4) void k_mdr_head(const HeadArgs a) {
     static_assert(NT >= kV, "one token per thread");
@@ -1700,7 +1524,6 @@ __global__ __launch_bounds__(NT, HOIST ? 2 : 4) void k_mdr_head(const HeadArgs a
     // Conv1d(431->20,k3,p1) weight of row m = wave + 8 q at e = lane + 64 it
     auto conv_w = [&](int q, int it) {
         const int e = lane + 64 * it, m = wave + NW * q;
-        if (MDR_HEAD_CUT & 8) return 0.5f;
         return e < kV * 3 ? a.bconv_w[(m < 20 ? m : 0) * (kV * 3) + e] : 0.f;
     };
     float wreg[3][HOIST ? NIT : 1];
@@ -1730,14 +1553,14 @@ __global__ __launch_bounds__(NT, HOIST ? 2 : 4) void k_mdr_head(const HeadArgs a
         float acc[3][3];
 #pragma unroll
         for (int q = 0; q < 3; ++q) acc[q][0] = acc[q][1] = acc[q][2] = 0.f;
-        // Round 6 (the conv loop was 6.5 of the launch's 17 us, the nine double-precision butterflies through LDS 2.6: MDR_HEAD_CUT): the walk
+        // Round 6 (the conv loop was 6.5 of the launch's 17 us, the nine double-precision butterflies through LDS 2.6, by timing cuts): the walk
         // e = lane + 64 it advances (channel c, tap k) by (21, +1) instead of dividing; the padding is stored zeros, not conditions; the
         // products are fused multiply-adds; the wave sums run on DPP row operations (still in double: bc feeds every coarse vertex).
         int cch = lane / 3, ktap = lane - 3 * cch;
 #pragma unroll(HOIST ? NIT : 1)
         for (int it = 0; it < NIT; ++it) {
             const int e = lane + 64 * it;
-            if (!(MDR_HEAD_CUT & 1) && e < kV * 3) {
+            if (e < kV * 3) {
                 // tap k of channel c meets input position l + k - 1 (zero padding outside 0..2 = the stored zeros)
                 const float in0 = bn[cch][ktap], in1 = bn[cch][ktap + 1], in2 = bn[cch][ktap + 2];
 #pragma unroll
@@ -1755,7 +1578,7 @@ __global__ __launch_bounds__(NT, HOIST ? 2 : 4) void k_mdr_head(const HeadArgs a
         for (int q = 0; q < 3; ++q)
 #pragma unroll
             for (int l = 0; l < 3; ++l) {
-                const double s = (MDR_HEAD_CUT & 2) ? (double)acc[q][l] : wave_sum64_f64((double)acc[q][l]);
+                const double s = wave_sum64_f64((double)acc[q][l]);
                 const int m = wave + NW * q;
                 if (lane == 0 && m < 20) bc[m][l] = (float)(s + (double)a.bconv_b[m]);
             }
@@ -1781,7 +1604,7 @@ __global__ __launch_bounds__(NT, HOIST ? 2 : 4) void k_mdr_head(const HeadArgs a
         float mx = -1e30f, p[20], l = 0.f;
         for (int m = 0; m < 20; ++m) mx = fmaxf(mx, av[m]);
         for (int m = 0; m < 20; ++m) {
-            p[m] = (MDR_HEAD_CUT & 4) ? av[m] : __builtin_amdgcn_exp2f((av[m] - mx) * kLog2e);
+            p[m] = __builtin_amdgcn_exp2f((av[m] - mx) * kLog2e);
             l += p[m];
         }
         const float il = 1.0f / l;

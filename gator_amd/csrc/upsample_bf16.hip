@@ -6,16 +6,10 @@
 // Same tap-sharing formulation as upsample_fused.hip (7 MFMAs per loaded k-step, padding taps never multiplied) with
 // K = 16 coarse vertices per MFMA.  At 16x the fp32 MFMA rate the kernel is bound by operand traffic, so one wave owns TWO
 // 32-sample tiles per weight fragment (64 samples x 32 vertices x 3 coords).
-#include "fused_common.h"
-#include "fused_state.h"
+#include "upsample_common.h"
 
 namespace gator {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int kS16 = 28;      // 16-wide k steps over the 431 (->448) coarse vertices
-
-#define GATOR_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
 // dst[tap][ob][s][lane][j] = bf16( w[32ob + (lane&31)][16s + 8(lane>>5) + j][tap] )
 __global__ void k_pack_up_bf16(const float* __restrict__ w, __bf16* __restrict__ dst, int64_t total) {
@@ -42,8 +36,6 @@ __global__ void k_pack_vc_bf16(const float* __restrict__ vc, int B, __bf16* __re
     const int smp = 32 * mt + (lane & 31), c = 16 * s + 8 * (lane >> 5) + j;
     vcp[e] = (smp < B && c < kV) ? (__bf16)vc[((int64_t)smp * kV + c) * 3 + lp] : (__bf16)0.f;
 }
-
-struct __attribute__((packed)) F3 { float x, y, z; };
 
 __global__ __launch_bounds__(256) void k_upsample_bf16(const __bf16* __restrict__ vcp, const __bf16* __restrict__ wp,
                                                        const float* __restrict__ bias, const float* __restrict__ tpl,

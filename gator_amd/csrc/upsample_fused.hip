@@ -7,8 +7,7 @@
 // the 35.6 MB weight is streamed once per 128 samples.  A = packed vert431 (rows = samples), B = packed weights
 // (cols = output vertices)  ->  accumulator: vertex on the lane, samples in registers, so each lane stores the 3
 // contiguous floats out[b][o][0..2] and a wave row covers 384 contiguous bytes.
-#include "fused_common.h"
-#include "fused_state.h"
+#include "upsample_common.h"
 
 namespace gator {
 namespace {
@@ -25,8 +24,6 @@ __global__ void k_pack_vc(const float* __restrict__ vc, int B, float* __restrict
     const int s = 32 * mt + (lane & 31), c = 32 * cb + 8 * g + 4 * (lane >> 5) + j;
     vcp[e] = (s < B && c < kV) ? vc[((int64_t)s * kV + c) * 3 + lp] : 0.f;
 }
-
-struct __attribute__((packed)) F3 { float x, y, z; };
 
 // NT = 32-sample tiles per wave that share each weight fragment.  NT = 2 (64 samples x 32 vertices x 3 coords) halves the
 // weight traffic and, at B=256, gives 864 waves - at most one per SIMD, so no co-resident partner competes for the MFMA pipe

@@ -19,17 +19,13 @@
 #include <cmath>
 #include <cstring>
 
-#include "fused_common.h"
-#include "fused_state.h"
+#include "upsample_common.h"
 
 namespace gator {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-constexpr int kS16 = 28;                            // 16-deep k-steps over the 431 (-> 448) coarse vertices
 constexpr int kNBuf = 4, kStageFrags = 36;          // 1 KiB fragments per stage: [mt 4][lp 3][plane 2] then [ob 2][tap 3][plane 2]
 constexpr int kActShift = 4;                        // activations x 2^4
-#define GATOR_MFMA_F16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ void split2(float x, _Float16& h, _Float16& l) {
     h = (_Float16)x;
@@ -95,24 +91,14 @@ __device__ __forceinline__ void dma_frag(const void* base, unsigned lane_off, un
 }
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-struct __attribute__((packed)) F3 { float x, y, z; };
-
-// Joint-regression epilogue: see upsample_x3.hip (same tables, same order of operations on the finished vertex).
-struct JregEpi2 {
-    const int2* blk;
-    const int2* ent;
-    const float* w;
-    float* P;
-    int nnz;
-};
-
+// Joint-regression epilogue: upsample_common.h (JregEpi; the same order of operations on the finished vertex as upsample_x3.hip).
 // WLO = false (BASELINE config 3, the 16-bit operand mode): the weights' lo plane is not used -- weights on ONE fp16 plane, coarse vertices on two:
 // two MFMAs per product instead of three (0.35 mm max / 0.06 mm rms by the emulation: profiles/r05_emulate_16bit.txt)
 template <bool WLO = true>
 __global__ __launch_bounds__(512, 1) void k_upsample_x2(const _Float16* __restrict__ ap, const _Float16* __restrict__ wp,
                                                         const float* __restrict__ bias, const float* __restrict__ tpl,
                                                         float* __restrict__ out, int B, int MT, int MG, int nwg, float unscale,
-                                                        const JregEpi2 jr) {
+                                                        const JregEpi jr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     f16x8 (*st)[kStageFrags][64] = reinterpret_cast<f16x8 (*)[kStageFrags][64]>(lds_raw);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -282,8 +268,7 @@ int launch_pack_vc_x2(const float* vc, int B, void* vcp2, void* stream) {
 // verts == nullptr: vertices are not stored (joint regression only); with_joints: also fill f->jr_P for launch_jreg_reduce
 int launch_upsample_x2(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints, bool w1) {
     const int MT = (B + 31) / 32, MG = (MT + 3) / 4;
-    JregEpi2 jr{};
-    if (with_joints) { jr.blk = (const int2*)f->jr_blk.get(); jr.ent = (const int2*)f->jr_ent.get(); jr.w = f->jr_w.get(); jr.P = f->jr_P.get(); jr.nnz = f->jr_nnz; }
+    const JregEpi jr = jreg_epi(f, with_joints);
     const int nwg = (kOB / 2) * MG;
     if (w1) k_upsample_x2<false><<<nwg, 512, kX2Lds, (hipStream_t)stream>>>((const _Float16*)f->ws->vcp3, (const _Float16*)f->up_w2.get(), c->w.up_b, c->w.v6890,
                                                                            verts, B, MT, MG, nwg, f->up_w2_unscale, jr);

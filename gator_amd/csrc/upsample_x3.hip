@@ -5,15 +5,10 @@
 // (hi*hi | hi*mid, mid*hi | mid*mid, hi*lo, lo*hi) are computed on v_mfma_f32_32x32x16_bf16 -- 6 x 32 cycles per 16-deep
 // k-step against 8 x 64 cycles for the fp32-input MFMA (2.7x) -- and the dropped terms are below 2^-23 of the product.
 // hi*hi goes to one accumulator, the five small-magnitude terms to another, so they are not rounded away against the big sum.
-#include "fused_common.h"
-#include "fused_state.h"
+#include "upsample_common.h"
 
 namespace gator {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int kS16 = 28;
-#define GATOR_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
     h = (__bf16)x;
@@ -53,24 +48,12 @@ __global__ void k_pack_vc_x3(const float* __restrict__ vc, int B, __bf16* __rest
     vcp[e] = h; vcp[plane_elems + e] = m; vcp[2 * plane_elems + e] = l;
 }
 
-struct __attribute__((packed)) F3 { float x, y, z; };
-
 // One workgroup = one 32-vertex output tile x up to 8 sample tiles (one per compute wave) + ONE LOADER WAVE.
 // The 9 weight fragments of a k-step (3 taps x 3 planes, 9 KiB; the 54 MB weight stream comes from HBM) are fetched by
 // the loader wave four k-steps ahead into a register ring and handed to the compute waves through a double-buffered LDS
 // stage: its vmcnt queue is its own, so the compute waves' (L2-resident) activation prefetch never queues behind an
 // HBM miss (vmcnt retires in order).  Each compute wave register-prefetches its 9 activation fragments one step ahead.
-// Joint-regression epilogue (lib/core/base.py:221, demo/run.py:142: joints = J_regressor @ mesh, a 107-nnz matrix): a wave that
-// has just formed vertex v of its samples also writes w_e * v for every regressor entry e = (joint, v, w_e) of its 32-vertex
-// block into P[sample][e][xyz]; k_jreg_reduce sums each joint's entries in a fixed order.  No atomics, no second pass over the
-// 82 kB/mesh of vertices -- and with `out` == nullptr the vertices are never written at all (evaluation needs the joints only).
-struct JregEpi {
-    const int2* blk;            // [kOB] (first entry, entry count) of every 32-vertex block, entries sorted by vertex
-    const int2* ent;            // (vertex, slot in P) per entry
-    const float* w;             // weight per entry
-    float* P;                   // [B][nnz][3]
-    int nnz;
-};
+// Joint-regression epilogue: upsample_common.h (JregEpi).
 constexpr int kX3Waves = 8, kX3Ring = 4;
 __global__ __launch_bounds__(64 * (kX3Waves + 1), 1) void k_upsample_x3(const __bf16* __restrict__ vcp, const __bf16* __restrict__ wp,
                                                                        const float* __restrict__ bias, const float* __restrict__ tpl,
@@ -251,8 +234,7 @@ int launch_jreg_reduce(const FusedState* f, int B, float* joints, void* stream) 
 // verts == nullptr: vertices are not stored (joint regression only); with_joints: also fill f->jr_P for launch_jreg_reduce
 int launch_upsample_x3(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints) {
     const int MT = (B + 31) / 32;
-    JregEpi jr{};
-    if (with_joints) { jr.blk = (const int2*)f->jr_blk.get(); jr.ent = (const int2*)f->jr_ent.get(); jr.w = f->jr_w.get(); jr.P = f->jr_P.get(); jr.nnz = f->jr_nnz; }
+    const JregEpi jr = jreg_epi(f, with_joints);
     const int64_t w_plane = (int64_t)upsample_x3_weight_elems() / 3, a_plane = (int64_t)upsample_x3_vcp_elems(f->ws->cap) / 3;
     const int nwg = kOB * ((MT + kX3Waves - 1) / kX3Waves);
     k_upsample_x3<<<nwg, 64 * (kX3Waves + 1), 0, (hipStream_t)stream>>>((const __bf16*)f->ws->vcp3, (const __bf16*)f->up_w3.get(), c->w.up_b,
