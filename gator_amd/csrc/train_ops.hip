@@ -57,6 +57,27 @@ __device__ __forceinline__ int64_t dot4(const uint32_t (&c)[4], const Str4& s) {
     return (int64_t)c[0] * s.s[0] + (int64_t)c[1] * s.s[1] + (int64_t)c[2] * s.s[2] + (int64_t)c[3] * s.s[3];
 }
 
+// the C ABI's shape[4] / stride[4] as kernel arguments (a missing stride array: all 0, every index reads element 0)
+int64_t load_shape(const int64_t* shape, Idx4& n) {
+    int64_t total = 1;
+    for (int d = 0; d < 4; ++d) total *= (n.n[d] = shape[d]);
+    return total;
+}
+Str4 load_stride(const int64_t* stride) {
+    Str4 s;
+    for (int d = 0; d < 4; ++d) s.s[d] = stride ? stride[d] : 0;
+    return s;
+}
+// the strides of a contiguous tensor of shape n (a dim of extent 1 may carry any stride)
+bool dense(const Idx4& n, const Str4& s) {
+    int64_t e = 1;
+    for (int d = 3; d >= 0; --d) {
+        if (n.n[d] != 1 && s.s[d] != e) return false;
+        e *= n.n[d];
+    }
+    return true;
+}
+
 __device__ __forceinline__ float binary_apply(int op, float x, float y) {
     switch (op) {
         case 0: return x + y;
@@ -103,17 +124,8 @@ __global__ __launch_bounds__(kThreads) void k_t_binary32(int op, const float* __
 
 __global__ __launch_bounds__(kThreads) void k_t_binary(int op, const float* __restrict__ a, Str4 sa, const float* __restrict__ b, Str4 sb,
                                                        float* __restrict__ o, Str4 so, Idx4 n, int64_t total) {
-    for (int64_t i = blockIdx.x * (int64_t)kThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kThreads) {
-        const float x = a[offset4(i, n, sa)], y = b[offset4(i, n, sb)];
-        float r;
-        switch (op) {
-            case 0: r = x + y; break;
-            case 1: r = x - y; break;
-            case 2: r = x * y; break;
-            default: r = x / y; break;
-        }
-        o[offset4(i, n, so)] = r;
-    }
+    for (int64_t i = blockIdx.x * (int64_t)kThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kThreads)
+        o[offset4(i, n, so)] = binary_apply(op, a[offset4(i, n, sa)], b[offset4(i, n, sb)]);
 }
 
 __device__ __forceinline__ float unary_apply(int op, float x, float p0, float p1) {
@@ -184,18 +196,7 @@ __global__ __launch_bounds__(kThreads) void k_t_reduce(const float* __restrict__
     __shared__ double sh[4];
     const int64_t o = blockIdx.x;
     const int sp = blockIdx.y;
-    Idx4 kn = keep;
-    int64_t base;
-    {
-        int64_t i = o;
-        const int64_t i3 = i % kn.n[3];
-        i /= kn.n[3];
-        const int64_t i2 = i % kn.n[2];
-        i /= kn.n[2];
-        const int64_t i1 = i % kn.n[1];
-        const int64_t i0 = i / kn.n[1];
-        base = i0 * sx.s[0] + i1 * sx.s[1] + i2 * sx.s[2] + i3 * sx.s[3];
-    }
+    const int64_t base = offset4(o, keep, sx);
     const int64_t per = (R + nsplit - 1) / nsplit, r0 = sp * per, r1 = r0 + per < R ? r0 + per : R;
     double acc = 0.0;
     for (int64_t r = r0 + threadIdx.x; r < r1; r += kThreads) acc += (double)x[base + offset4(r, red, sx)];
@@ -424,6 +425,14 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, float (&As)[2][kGem
     }
 }
 
+// The layout of a product and of its split-K workspace, for the host entry points and the kernels alike: 64x64 output tiles; the
+// workspace holds the ksplit slices of C ([ksplit][M][N], dense) and behind them those of the row sums ([ksplit][M]); the finish
+// launch gives every 64 consecutive elements of C a workgroup and, behind those, every 64 row sums.
+__host__ __device__ __forceinline__ int gemm_tiles(int M, int N) { return ((M + 63) / 64) * ((N + 63) / 64); }
+__host__ __device__ __forceinline__ int64_t splitk_rowsum_off(int ksplit, int M, int N) { return (int64_t)ksplit * M * N; }
+__host__ __device__ __forceinline__ int64_t splitk_ws_floats(int ksplit, int M, int N) { return splitk_rowsum_off(ksplit, M, N) + (int64_t)ksplit * M; }
+__host__ __device__ __forceinline__ int64_t splitk_finish_wgs(int M, int N, bool rowsum) { return ((int64_t)M * N + 63) / 64 + (rowsum ? (M + 63) / 64 : 0); }
+
 __global__ __launch_bounds__(kThreads) void k_t_gemm(GemmArgs g) {
     __shared__ float As[2][kGemmBK][65], Bs[2][kGemmBK][65];
     gemm_tile(g, As, Bs, blockIdx.x, blockIdx.y, blockIdx.z);
@@ -431,20 +440,8 @@ __global__ __launch_bounds__(kThreads) void k_t_gemm(GemmArgs g) {
 
 // Grouped form: ONE launch runs a list of independent unbatched products (the weight gradients of a whole backward pass, which
 // nothing consumes before the optimiser).  Workgroup -> (problem, tile, K slice) through the table's running workgroup count.
-struct GroupedProblem {
-    const float *A, *B;
-    float *C, *rowsum;                 // final destinations
-    int M, N, K, ksplit;
-    int64_t am, ak, bk, bn, cm, cn;
-    float alpha;
-    int accumulate;
-    int wg_begin, fin_begin;           // first workgroup of this problem in the product launch / in the finish launch
-    int64_t ws_off;                    // floats into the shared split-K workspace
-    int total_wgs, total_fin;          // (entry 0: launch sizes; keeps the layout of gator_gemm_problem)
-    const float* bias;                 // optional [N], added to every row (forward linears run as a group)
-};
-
-__device__ __forceinline__ int find_problem(const GroupedProblem* __restrict__ tab, int n, int wg, bool fin) {
+// The table is the ABI's gator_gemm_problem (include/gator_train.h), as gator_t_gemm_grouped_prepare completed it.
+__device__ __forceinline__ int find_problem(const gator_gemm_problem* __restrict__ tab, int n, int wg, bool fin) {
     int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -453,22 +450,22 @@ __device__ __forceinline__ int find_problem(const GroupedProblem* __restrict__ t
     return lo;
 }
 
-__global__ __launch_bounds__(kThreads) void k_t_gemm_grouped(const GroupedProblem* __restrict__ tab, int n, float* __restrict__ ws) {
+__global__ __launch_bounds__(kThreads) void k_t_gemm_grouped(const gator_gemm_problem* __restrict__ tab, int n, float* __restrict__ ws) {
     __shared__ float As[2][kGemmBK][65], Bs[2][kGemmBK][65];
     const int pi = find_problem(tab, n, blockIdx.x, false);
-    const GroupedProblem p = tab[pi];
-    const int local = blockIdx.x - p.wg_begin, tiles = ((p.M + 63) / 64) * ((p.N + 63) / 64);
+    const gator_gemm_problem p = tab[pi];
+    const int local = blockIdx.x - p.wg_begin, tiles = ((p.M + 63) / 64) * ((p.N + 63) / 64);        // keep in step with gemm_tiles()
     GemmArgs g;
     g.A = p.A; g.B = p.B; g.bias = p.bias;
     g.M = p.M; g.N = p.N; g.K = p.K; g.nb2 = 1; g.ksplit = p.ksplit;
-    g.am = p.am; g.ak = p.ak; g.bk = p.bk; g.bn = p.bn;
+    g.am = p.stride_a[0]; g.ak = p.stride_a[1]; g.bk = p.stride_b[0]; g.bn = p.stride_b[1];
     g.a1 = g.a2 = g.b1 = g.b2 = g.c1 = g.c2 = 0;
     if (p.ksplit > 1) {
         g.C = ws + p.ws_off; g.cm = p.N; g.cn = 1; g.alpha = 1.f; g.accumulate = 0;
-        g.rowsum = p.rowsum ? ws + p.ws_off + (int64_t)p.ksplit * p.M * p.N : nullptr;
+        g.rowsum = p.a_rowsum ? ws + p.ws_off + splitk_rowsum_off(p.ksplit, p.M, p.N) : nullptr;
     } else {
-        g.C = p.C; g.cm = p.cm; g.cn = p.cn; g.alpha = p.alpha; g.accumulate = p.accumulate;
-        g.rowsum = p.rowsum;
+        g.C = p.C; g.cm = p.stride_c[0]; g.cn = p.stride_c[1]; g.alpha = p.alpha; g.accumulate = p.accumulate;
+        g.rowsum = p.a_rowsum;
     }
     g.a_kfast = (g.ak == 1 || g.am != 1) ? 1 : 0;
     g.b_nfast = (g.bn == 1 || g.bk != 1) ? 1 : 0;
@@ -481,7 +478,7 @@ __device__ __forceinline__ void splitk_finish_block(float (&sh)[4][64], int64_t 
                                                     int accumulate, const float* __restrict__ ws_rowsum, float* __restrict__ rowsum) {
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int64_t MN = (int64_t)M * N;
-    const int64_t blocks_c = (MN + 63) / 64;
+    const int64_t blocks_c = (MN + 63) / 64;                      // keep in step with splitk_finish_wgs()
     const bool is_rs = block >= blocks_c;                         // trailing workgroups finish the row sums
     const int64_t i = (is_rs ? block - blocks_c : block) * 64 + tx;
     const int64_t total = is_rs ? M : MN;
@@ -521,14 +518,14 @@ __global__ __launch_bounds__(kThreads) void k_t_splitk_finish(const float* __res
     splitk_finish_block(sh, blockIdx.x, ws, ksplit, M, N, C, cm, cn, bias, alpha, accumulate, ws_rowsum, rowsum);
 }
 
-__global__ __launch_bounds__(kThreads) void k_t_splitk_finish_grouped(const GroupedProblem* __restrict__ tab, int n, const float* __restrict__ ws) {
+__global__ __launch_bounds__(kThreads) void k_t_splitk_finish_grouped(const gator_gemm_problem* __restrict__ tab, int n, const float* __restrict__ ws) {
     __shared__ float sh[4][64];
     const int pi = find_problem(tab, n, blockIdx.x, true);
-    const GroupedProblem p = tab[pi];
+    const gator_gemm_problem p = tab[pi];
     if (p.ksplit <= 1) return;                                   // (problems without split-K own no finish workgroups; defensive)
     const float* w = ws + p.ws_off;
-    splitk_finish_block(sh, blockIdx.x - p.fin_begin, w, p.ksplit, p.M, p.N, p.C, p.cm, p.cn, p.bias, p.alpha, p.accumulate,
-                        p.rowsum ? w + (int64_t)p.ksplit * p.M * p.N : nullptr, p.rowsum);
+    splitk_finish_block(sh, blockIdx.x - p.fin_begin, w, p.ksplit, p.M, p.N, p.C, p.stride_c[0], p.stride_c[1], p.bias, p.alpha, p.accumulate,
+                        p.a_rowsum ? w + splitk_rowsum_off(p.ksplit, p.M, p.N) : nullptr, p.a_rowsum);
 }
 
 // ------------------------------------------------------------------------------------------------------------ row kernels
@@ -635,12 +632,18 @@ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2])
     k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
 }
 
-__device__ __forceinline__ bool philox_keep_raw(uint64_t seed, uint64_t offset, int64_t idx, uint32_t thresh) {
-    const int64_t q = idx >> 2;
-    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
+// one Philox4x32 block: the counter c becomes the block's four words under the key `seed`
+__device__ __forceinline__ void philox_block(uint32_t (&c)[4], uint64_t seed) {
     uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
 #pragma unroll
     for (int r = 0; r < GATOR_PHILOX_ROUNDS; ++r) philox_round(c, k);
+}
+
+// keep decision of element `idx` of a tensor, exactly as k_t_dropout draws it (quad idx/4, lane idx%4 of one Philox block)
+__device__ __forceinline__ bool philox_keep(uint64_t seed, uint64_t offset, int64_t idx, uint32_t thresh) {
+    const int64_t q = idx >> 2;
+    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
+    philox_block(c, seed);
     return c[idx & 3] >= thresh;
 }
 
@@ -651,9 +654,7 @@ __global__ __launch_bounds__(kThreads) void k_t_dropout(const float* __restrict_
     if (q * 4 >= n) return;
     if (step_counter) offset += step_counter[0] << 32;
     uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
-    uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-    for (int r = 0; r < GATOR_PHILOX_ROUNDS; ++r) philox_round(c, k);
+    philox_block(c, seed);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int64_t i = q * 4 + j;
@@ -676,7 +677,7 @@ __global__ __launch_bounds__(kThreads) void k_t_drop_fused(const float* __restri
     if (q * 4 >= n) return;
     const uint64_t hi = step_counter ? (step_counter[0] << 32) : 0ull;
     uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)(offset + hi), (uint32_t)((offset + hi) >> 32)};
-    if (drop_on) {
+    if (drop_on) {                                  // keep in step with philox_block()
         uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
 #pragma unroll
         for (int r = 0; r < GATOR_PHILOX_ROUNDS; ++r) philox_round(c, k);
@@ -698,7 +699,7 @@ __global__ __launch_bounds__(kThreads) void k_t_drop_fused(const float* __restri
             const int64_t b = i / per_sample;
             if (b != sb) {                              // (one generator call per thread unless its quad straddles two samples)
                 sb = b;
-                f = philox_keep_raw(seed, poffset + hi, b, pthresh) ? pscale : 0.f;
+                f = philox_keep(seed, poffset + hi, b, pthresh) ? pscale : 0.f;
             }
             if (i == b * per_sample) fac[b] = f;
             v *= f;
@@ -876,6 +877,12 @@ int grid_for(int64_t total) {
     return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
 }
 
+// a 32-bit Philox word is KEPT when it is >= this: the dropped share of [0, 2^32) is `rate`
+uint32_t rate_thresh(float rate) {
+    const double t = (double)rate * 4294967296.0;
+    return t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
+}
+
 int check_launch(const char* what) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail((int)e, "%s: %s", what, hipGetErrorString(e));
@@ -900,16 +907,6 @@ int face_loss(bool normal, const float* pred, const float* target, const int32_t
     return check_launch(normal ? "gator_t_normal_loss" : "gator_t_edge_loss");
 }
 
-// keep decision of element `idx` of a tensor, exactly as k_t_dropout draws it (quad idx/4, lane idx%4 of one Philox block)
-__device__ __forceinline__ bool philox_keep(unsigned long long seed, unsigned long long offset, int64_t idx, uint32_t thresh) {
-    const int64_t q = idx >> 2;
-    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
-    uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-    for (int r = 0; r < GATOR_PHILOX_ROUNDS; ++r) philox_round(c, k);
-    return c[idx & 3] >= thresh;
-}
-
 #include "train_attn.inc"
 
 }  // namespace
@@ -923,26 +920,11 @@ int gator_t_binary(int op, const float* a, const int64_t* sa, const float* b, co
                    const int64_t* shape, gator_stream stream) {
     if (!a || !b || !out || op < 0 || op > 3) return fail(1, "gator_t_binary: bad argument");
     Idx4 n;
-    Str4 A, Bs, O;
-    int64_t total = 1;
-    for (int d = 0; d < 4; ++d) {
-        n.n[d] = shape[d];
-        A.s[d] = sa[d];
-        Bs.s[d] = sb[d];
-        O.s[d] = so[d];
-        total *= shape[d];
-    }
+    const int64_t total = load_shape(shape, n);
+    const Str4 A = load_stride(sa), Bs = load_stride(sb), O = load_stride(so);
     if (total == 0) return 0;
-    auto dense = [&](const Str4& s) {
-        int64_t e = 1;
-        for (int d = 3; d >= 0; --d) {
-            if (n.n[d] != 1 && s.s[d] != e) return false;
-            e *= n.n[d];
-        }
-        return true;
-    };
     const bool aligned = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0;
-    if (dense(A) && dense(Bs) && dense(O) && aligned)
+    if (dense(n, A) && dense(n, Bs) && dense(n, O) && aligned)
         hipLaunchKernelGGL(k_t_binary_flat, dim3(grid_for((total + 3) / 4)), dim3(kThreads), 0, (hipStream_t)stream, op, a, b, out, total);
     else if (total < 0x7fffffffLL)
         hipLaunchKernelGGL(k_t_binary32, dim3(grid_for(total)), dim3(kThreads), 0, (hipStream_t)stream, op, a, A, b, Bs, out, O, n, (uint32_t)total);
@@ -962,24 +944,10 @@ int gator_t_unary(int op, const float* x, const int64_t* sx, float* out, const i
                   gator_stream stream) {
     if (!x || !out || op < 0 || op > 11) return fail(1, "gator_t_unary: bad argument");
     Idx4 n;
-    Str4 X, O;
-    int64_t total = 1;
-    for (int d = 0; d < 4; ++d) {
-        n.n[d] = shape[d];
-        X.s[d] = sx[d];
-        O.s[d] = so[d];
-        total *= shape[d];
-    }
+    const int64_t total = load_shape(shape, n);
+    const Str4 X = load_stride(sx), O = load_stride(so);
     if (total == 0) return 0;
-    auto dense = [&](const Str4& s) {
-        int64_t e = 1;
-        for (int d = 3; d >= 0; --d) {
-            if (n.n[d] != 1 && s.s[d] != e) return false;
-            e *= n.n[d];
-        }
-        return true;
-    };
-    if (dense(X) && dense(O) && (((uintptr_t)x | (uintptr_t)out) & 15) == 0)
+    if (dense(n, X) && dense(n, O) && (((uintptr_t)x | (uintptr_t)out) & 15) == 0)
         hipLaunchKernelGGL(k_t_unary_flat, dim3(grid_for((total + 3) / 4)), dim3(kThreads), 0, (hipStream_t)stream, op, x, out, total, p0, p1);
     else if (total < 0x7fffffffLL)
         hipLaunchKernelGGL(k_t_unary32, dim3(grid_for(total)), dim3(kThreads), 0, (hipStream_t)stream, op, x, X, out, O, n, (uint32_t)total, p0, p1);
@@ -1032,15 +1000,14 @@ int gator_t_gemm(const float* A, const float* B, float* C, int M, int N, int K, 
     g.a1 = ba[0]; g.a2 = ba[1]; g.b1 = bb[0]; g.b2 = bb[1]; g.c1 = bc[0]; g.c2 = bc[1];
     g.alpha = ksplit > 1 ? 1.f : alpha;
     g.accumulate = ksplit > 1 ? 0 : accumulate;
-    g.rowsum = a_rowsum ? (ksplit > 1 ? ws + (int64_t)ksplit * M * N : a_rowsum) : nullptr;
+    g.rowsum = a_rowsum ? (ksplit > 1 ? ws + splitk_rowsum_off(ksplit, M, N) : a_rowsum) : nullptr;
     g.a_kfast = (g.ak == 1 || g.am != 1) ? 1 : 0;       // lanes run along whichever index is contiguous in memory
     g.b_nfast = (g.bn == 1 || g.bk != 1) ? 1 : 0;
-    const unsigned tiles = (unsigned)(((M + 63) / 64) * ((N + 63) / 64));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_t_gemm, dim3(tiles, nb1 * nb2, ksplit), dim3(kThreads), 0, st, g);
+    hipLaunchKernelGGL(k_t_gemm, dim3((unsigned)gemm_tiles(M, N), nb1 * nb2, ksplit), dim3(kThreads), 0, st, g);
     if (ksplit > 1)
-        hipLaunchKernelGGL(k_t_splitk_finish, dim3((unsigned)(((int64_t)M * N + 63) / 64 + (a_rowsum ? (M + 63) / 64 : 0))), dim3(kThreads), 0, st, ws, ksplit, M, N, C,
-                           sc[0], sc[1], bias, alpha, accumulate, a_rowsum ? ws + (int64_t)ksplit * M * N : nullptr, a_rowsum);
+        hipLaunchKernelGGL(k_t_splitk_finish, dim3((unsigned)splitk_finish_wgs(M, N, a_rowsum != nullptr)), dim3(kThreads), 0, st, ws, ksplit, M, N, C,
+                           sc[0], sc[1], bias, alpha, accumulate, a_rowsum ? ws + splitk_rowsum_off(ksplit, M, N) : nullptr, a_rowsum);
     return check_launch("gator_t_gemm");
 }
 
@@ -1051,14 +1018,13 @@ int64_t gator_t_gemm_grouped_prepare(gator_gemm_problem* pr, int n) {
     for (int i = 0; i < n; ++i) {
         gator_gemm_problem& p = pr[i];
         if (p.M <= 0 || p.N <= 0 || p.K < 0 || p.ksplit < 1) return -1;
-        const int tiles = ((p.M + 63) / 64) * ((p.N + 63) / 64);
         p.wg_begin = wg;
         p.fin_begin = fin;
         p.ws_off = ws;
-        wg += tiles * p.ksplit;
+        wg += gemm_tiles(p.M, p.N) * p.ksplit;
         if (p.ksplit > 1) {
-            fin += (int)(((int64_t)p.M * p.N + 63) / 64) + (p.a_rowsum ? (p.M + 63) / 64 : 0);
-            ws += (int64_t)p.ksplit * ((int64_t)p.M * p.N + p.M);
+            fin += (int)splitk_finish_wgs(p.M, p.N, p.a_rowsum != nullptr);
+            ws += splitk_ws_floats(p.ksplit, p.M, p.N);
         }
     }
     pr[0].total_wgs = wg;
@@ -1068,16 +1034,15 @@ int64_t gator_t_gemm_grouped_prepare(gator_gemm_problem* pr, int n) {
 
 int gator_t_gemm_grouped(const gator_gemm_problem* table_host, int n, void* table_dev, float* ws, gator_stream stream) {
     if (!table_host || !table_dev || n <= 0) return fail(1, "gator_t_gemm_grouped: bad argument");
-    static_assert(sizeof(gator_gemm_problem) == sizeof(GroupedProblem) && offsetof(gator_gemm_problem, ws_off) == offsetof(GroupedProblem, ws_off), "host / device problem layouts");
     hipStream_t st = (hipStream_t)stream;
     const int wgs = table_host[0].total_wgs, fin = table_host[0].total_fin;
     if (wgs <= 0) return fail(1, "gator_t_gemm_grouped: call gator_t_gemm_grouped_prepare first");
     if (fin > 0 && !ws) return fail(1, "gator_t_gemm_grouped: split-K problems need the workspace");
     const hipError_t e = hipMemcpyAsync(table_dev, table_host, (size_t)n * sizeof(gator_gemm_problem), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail((int)e, "gator_t_gemm_grouped: table upload: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_t_gemm_grouped, dim3(wgs), dim3(kThreads), 0, st, static_cast<const GroupedProblem*>(table_dev), n, ws);
+    hipLaunchKernelGGL(k_t_gemm_grouped, dim3(wgs), dim3(kThreads), 0, st, static_cast<const gator_gemm_problem*>(table_dev), n, ws);
     if (fin > 0)
-        hipLaunchKernelGGL(k_t_splitk_finish_grouped, dim3(fin), dim3(kThreads), 0, st, static_cast<const GroupedProblem*>(table_dev), n, ws);
+        hipLaunchKernelGGL(k_t_splitk_finish_grouped, dim3(fin), dim3(kThreads), 0, st, static_cast<const gator_gemm_problem*>(table_dev), n, ws);
     return check_launch("gator_t_gemm_grouped");
 }
 
@@ -1122,17 +1087,10 @@ int gator_t_dropout(const float* x, int64_t n, float rate, uint64_t seed, uint64
                     gator_stream stream) {
     if (!out || !mask || rate < 0.f || rate >= 1.f) return fail(1, "gator_t_dropout: bad argument");
     if (n == 0) return 0;
-    const double t = (double)rate * 4294967296.0;
-    const uint32_t thresh = t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
     const int64_t quads = (n + 3) / 4;
-    hipLaunchKernelGGL(k_t_dropout, dim3((unsigned)((quads + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, x, n, thresh,
+    hipLaunchKernelGGL(k_t_dropout, dim3((unsigned)((quads + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, x, n, rate_thresh(rate),
                        1.0f / (1.0f - rate), seed, offset, step_counter, out, mask);
     return check_launch("gator_t_dropout");
-}
-
-static uint32_t rate_thresh(float rate) {
-    const double t = (double)rate * 4294967296.0;
-    return t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
 }
 
 int gator_t_drop_fused(const float* x, const float* res, int64_t n, int64_t per_sample, int gelu, float rate, uint64_t seed, uint64_t offset,
@@ -1289,13 +1247,8 @@ int gator_t_coord_loss(const float* pred, const float* target, const float* vali
                        float* loss_out, float* grad, void* ws, gator_stream stream) {
     if (!pred || !target || !loss_out || !ws) return fail(1, "gator_t_coord_loss: null argument");
     Idx4 n;
-    Str4 S;
-    int64_t total = 1;
-    for (int d = 0; d < 4; ++d) {
-        n.n[d] = shape[d];
-        S.s[d] = (valid && sv) ? sv[d] : 0;
-        total *= shape[d];
-    }
+    const int64_t total = load_shape(shape, n);
+    const Str4 S = load_stride(valid ? sv : nullptr);
     if (total == 0) return fail(1, "gator_t_coord_loss: empty input");
     const int blocks = (int)std::min<int64_t>(kLossBlocks, (total + kThreads - 1) / kThreads);
     hipStream_t st = (hipStream_t)stream;

@@ -43,7 +43,7 @@ class _LossFn(torch.autograd.Function):
         out = torch.empty(1, device=p.device, dtype=torch.float32)
         need = ctx.needs_input_grad[0]
         grad = ops.zeros(p.shape, p.device) if need else None
-        st = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
+        st = ops.stream_of(p)
         lib = _lib.load()
         if kind == 'coord':
             n4 = [1] * (4 - p.dim()) + list(p.shape)

@@ -43,8 +43,6 @@ class Consts:
         self.J, self.alpha = int(J), bool(alpha)
         sp = np.asarray(sp).astype(np.int64)
         self.A = f(graph_adj)
-        self.E = f(np.eye(J))
-        self.notE = f(1.0 - np.eye(J))
         self.m1 = f(sp <= 1)                                                  # modules.py:163-170
         self.m2 = f(sp == 2)
         deg = np.asarray(graph_adj).astype(np.int64).sum(1)                   # GAT.py:143
@@ -100,11 +98,7 @@ def conv1d_k3(x, w, b):
     """F.conv1d(x [B,C,3], w [O,C,3], b, padding=1) -> [B,O,3]"""
     B, C, _ = x.shape
     u = _Unfold3.apply(x).reshape(B, 3, C * 3)
-    wr = w.reshape(w.shape[0], C * 3)
-    slot = getattr(w, '_gslot', None)                                # (forwarded, not consumed: ops.linear below is the one writer)
-    if slot is not None:
-        wr._gslot = slot.reshape(w.shape[0], C * 3)                  # the view keeps its slice of the flat gradient buffer
-    y = ops.linear(u, wr, b)                                         # [B,3,O]
+    y = ops.linear(u, ops.slot_view(w, (w.shape[0], C * 3)), b)      # [B,3,O]
     return y.transpose(1, 2)
 
 
@@ -120,41 +114,30 @@ def hop_path_bias(P, c, p='pose_lifter.get_hop_path_encoding.'):
     return ops.add(spb, ops.mul(eb, c.inv_spatial))
 
 
-import os
-
-# GATOR_TRAIN_FUSED_ATTN=0: attention cores and the MGCN aggregation composed from the primitives (the cross-check form) instead of
-# their one-launch kernels
-FUSED_SELF_ATTENTION = os.environ.get('GATOR_TRAIN_FUSED_ATTN', '1') != '0'
+def mlp_tail(y, res, g, p, rate, path_rate, gen, training):
+    """res + DropPath(dropout(fc2(dropout(gelu(fc1(y)))))): timm's Mlp behind a pre-norm skip (modules.py:188-196, MDR.py:64-69).
+    GELU + dropout, and dropout + DropPath + residual, are one launch each."""
+    hdn = ops.drop_fused(ops.linear(y, g(p + 'fc1.weight'), g(p + 'fc1.bias')), None, True, rate, 0.0, gen, training)
+    return ops.drop_fused(ops.linear(hdn, g(p + 'fc2.weight'), g(p + 'fc2.bias')), res, False, rate, path_rate, gen, training)
 
 
 def gat_block(P, c, x, bias, i, gen, rates, training=True, p='pose_lifter.'):
     """GATBlock.forward (lib/models/GAT.py:33-43) composed from the primitives: x [B,J,128] -> [B,J,128]."""
     g = lambda k: P[p + k]
-    B, J, H, C = x.shape[0], c.J, NUM_HEADS, EMBED
+    H, C = NUM_HEADS, EMBED
     scale = (C // H) ** -0.5
     b = 'blocks.%d.' % i
     y, res = ops.layernorm_skip(x, g(b + 'norm1.weight'), g(b + 'norm1.bias'), 1e-5, 0)
     y, y0, y1 = ops.fork(y, 3)
     # Attention (modules.py:121-138)
     qkv = ops.linear(y, g(b + 'attn.qkv.weight'), g(b + 'attn.qkv.bias'))
-    if FUSED_SELF_ATTENTION:            # one launch per direction, one wave per (sample, head) (csrc/train_attn.inc)
-        a = ops.attention_small(qkv, bias, H, scale, rates.gat_attn, gen, training)
-    else:
-        q, k, v = [ops.reshape(t, B, J, H, C // H).permute(0, 2, 1, 3) for t in ops.split(qkv.reshape(B, J, 3, C), 2, (1, 1, 1))]
-        att = ops.add(ops.matmul(q, k.transpose(-2, -1), scale), bias)
-        att = ops.dropout(ops.softmax(att), rates.gat_attn, gen, training)
-        a = ops.contiguous(ops.matmul(att, v).transpose(1, 2)).reshape(B, J, C)
+    a = ops.attention_small(qkv, bias, H, scale, rates.gat_attn, gen, training)   # one launch per direction, one wave per (sample, head) (csrc/train_attn.inc)
     a = ops.dropout(ops.linear(a, g(b + 'attn.proj.weight'), g(b + 'attn.proj.bias')), rates.gat_proj, gen, training)
     # MGCN (modules.py:243-255)
     h0 = ops.xw(y0, g(b + 'gcn.W'), 0)
     h1 = ops.xw(y1, g(b + 'gcn.W'), 1)
-    if FUSED_SELF_ATTENTION:            # diag / off-diagonal aggregation, modulation and bias in one launch per direction
-        gout = ops.mgcn(h0, h1, sym_adjacency(c, g(b + 'gcn.adj2')), g(b + 'gcn.M'), g(b + 'gcn.bias'))
-    else:
-        adj_d, adj_o = ops.fork(sym_adjacency(c, g(b + 'gcn.adj2')))
-        M0, M1 = ops.fork(g(b + 'gcn.M'))
-        gout = ops.add(ops.add(ops.matmul(ops.mul(adj_d, c.E), ops.mul(M0, h0)), ops.matmul(ops.mul(adj_o, c.notE), ops.mul(M1, h1))),
-                       g(b + 'gcn.bias').reshape(1, 1, -1))
+    # diag / off-diagonal aggregation, modulation and bias in one launch per direction
+    gout = ops.mgcn(h0, h1, sym_adjacency(c, g(b + 'gcn.adj2')), g(b + 'gcn.M'), g(b + 'gcn.bias'))
     s = ops.drop_path(ops.add(a, gout), rates.gat_path[i], gen, training)
     # X_Feat (modules.py:158-177)
     s0, s1 = ops.fork(s)
@@ -165,12 +148,7 @@ def gat_block(P, c, x, bias, i, gen, rates, training=True, p='pose_lifter.'):
     x = ops.add(res, xf)
     # MLP (modules.py:188-196)
     y2, res = ops.layernorm_skip(x, g(b + 'norm2.weight'), g(b + 'norm2.bias'), 1e-5, 0)
-    if FUSED_SELF_ATTENTION:            # GELU + dropout, and dropout + DropPath + residual, one launch each
-        hdn = ops.drop_fused(ops.linear(y2, g(b + 'mlp.fc1.weight'), g(b + 'mlp.fc1.bias')), None, True, rates.gat_mlp, 0.0, gen, training)
-        return ops.drop_fused(ops.linear(hdn, g(b + 'mlp.fc2.weight'), g(b + 'mlp.fc2.bias')), res, False, rates.gat_mlp, rates.gat_path[i], gen, training)
-    hdn = ops.dropout(ops.gelu(ops.linear(y2, g(b + 'mlp.fc1.weight'), g(b + 'mlp.fc1.bias'))), rates.gat_mlp, gen, training)
-    m = ops.dropout(ops.linear(hdn, g(b + 'mlp.fc2.weight'), g(b + 'mlp.fc2.bias')), rates.gat_mlp, gen, training)
-    return ops.add(res, ops.drop_path(m, rates.gat_path[i], gen, training))
+    return mlp_tail(y2, res, g, b + 'mlp.', rates.gat_mlp, rates.gat_path[i], gen, training)
 
 
 def sym_adjacency(c, adj2):
@@ -201,26 +179,6 @@ def gat_forward(P, c, pose2d, gen, rates, training=True, p='pose_lifter.'):
     return x_out, feat
 
 
-def _batchnorm_train(x, w, b, run_mean, run_var, momentum=0.1, eps=1e-5):
-    """nn.BatchNorm1d(431) in training mode on x [B,431,3] (channels = the vertex axis, MDR.py:119,159): batch statistics over
-    (B, xyz), biased variance for the normalisation, running statistics updated with the unbiased one."""
-    n = x.shape[0] * x.shape[2]
-    x, x2 = ops.fork(x)
-    mu = ops.mean(x2, [0, 2], keepdim=True)
-    mu, mu_s = ops.fork(mu)
-    xc = ops.sub(x, mu)
-    xc, xc2 = ops.fork(xc)
-    var = ops.mean(ops.square(xc2), [0, 2], keepdim=True)
-    var, var_s = ops.fork(var)
-    y = ops.mul(xc, ops.rsqrt(ops.affine(var, 1.0, eps)))
-    if run_mean is not None:                                  # running = (1-m) running + m batch  (no gradient)
-        rm, rv = run_mean.reshape(1, -1, 1), run_var.reshape(1, -1, 1)
-        ops.raw_binary(ops.ADD, ops.raw_unary(ops.U_AFFINE, rm, 1.0 - momentum, 0.0), ops.raw_unary(ops.U_AFFINE, mu_s.detach(), momentum, 0.0), out=rm)
-        ops.raw_binary(ops.ADD, ops.raw_unary(ops.U_AFFINE, rv, 1.0 - momentum, 0.0),
-                       ops.raw_unary(ops.U_AFFINE, var_s.detach(), momentum * n / max(n - 1, 1), 0.0), out=rv)
-    return ops.add(ops.mul(y, w.reshape(1, -1, 1)), b.reshape(1, -1, 1))
-
-
 def mdr_forward(P, c, pc, gen, rates, training=True, buffers=None, p='pose2mesh.'):
     """MDR.forward (lib/models/MDR.py:124-170) in training mode.  pc [B,J,2+3+128] -> vertices [B,6890,3] (metres)."""
     g = lambda k: P[p + k]
@@ -242,38 +200,19 @@ def mdr_forward(P, c, pc, gen, rates, training=True, buffers=None, p='pose2mesh.
         fq, fj = ops.split(fz, 1, (V, J))
         fk, fv = ops.fork(ops.contiguous(fj))
         q, k, v = ops.linear_group([(fq, g(e + 'attn.wq.weight'), None), (fk, g(e + 'attn.wk.weight'), None), (fv, g(e + 'attn.wv.weight'), None)])
-        if FUSED_SELF_ATTENTION:        # vertex queries on joint keys through the same fused core (Tk = J)
-            o = ops.attention(q, k, v, Hh, d ** -0.5, rates.mdr_attn, gen, training)
-        else:
-            qh, kh, vh = [ops.reshape(t, B, t.shape[1], Hh, d).permute(0, 2, 1, 3) for t in (q, k, v)]
-            att = ops.dropout(ops.softmax(ops.matmul(qh, kh.transpose(-2, -1), d ** -0.5)), rates.mdr_attn, gen, training)
-            o = ops.contiguous(ops.matmul(att, vh).transpose(1, 2)).reshape(B, V, E)
+        o = ops.attention(q, k, v, Hh, d ** -0.5, rates.mdr_attn, gen, training)              # vertex queries on joint keys (Tk = J)
         o = ops.linear(o, g(e + 'attn.proj.weight'), g(e + 'attn.proj.bias'))
-        if FUSED_SELF_ATTENTION:
-            vf = ops.drop_fused(o, res, False, rates.mdr_drop, rates.mdr_path, gen, training)           # MDR.py:66
-        else:
-            vf = ops.add(res, ops.drop_path(ops.dropout(o, rates.mdr_drop, gen, training), rates.mdr_path, gen, training))
+        vf = ops.drop_fused(o, res, False, rates.mdr_drop, rates.mdr_path, gen, training)      # MDR.py:66
         y, res = ops.layernorm_skip(vf, g(e + 'norm2.weight'), g(e + 'norm2.bias'), 1e-5, 0)
-        if FUSED_SELF_ATTENTION:                                                                         # timm Mlp
-            h = ops.drop_fused(ops.linear(y, g(e + 'mlp.fc1.weight'), g(e + 'mlp.fc1.bias')), None, True, rates.mdr_drop, 0.0, gen, training)
-            vf = ops.drop_fused(ops.linear(h, g(e + 'mlp.fc2.weight'), g(e + 'mlp.fc2.bias')), res, False, rates.mdr_drop, rates.mdr_path, gen, training)
-        else:
-            h = ops.dropout(ops.gelu(ops.linear(y, g(e + 'mlp.fc1.weight'), g(e + 'mlp.fc1.bias'))), rates.mdr_drop, gen, training)
-            h = ops.dropout(ops.linear(h, g(e + 'mlp.fc2.weight'), g(e + 'mlp.fc2.bias')), rates.mdr_drop, gen, training)
-            vf = ops.add(res, ops.drop_path(h, rates.mdr_path, gen, training))
+        vf = mlp_tail(y, res, g, e + 'mlp.', rates.mdr_drop, rates.mdr_path, gen, training)
         vf = ops.layernorm(vf, g('norm%s.a_2' % sfx), g('norm%s.b_2' % sfx), 1e-6, 1)          # vanilla_transformer_encoder.py:31-34
         sa = 'selfatt%s.linears.' % sfx
         vf, res, xq, xk = ops.fork(vf, 4)
         qq, kk, vv = ops.linear_group([(t, g(sa + '%d.weight' % n), g(sa + '%d.bias' % n)) for n, t in enumerate((vf, xq, xk))])   # [B,431,64] each, one launch
-        if FUSED_SELF_ATTENTION:        # one launch forward / three backward, no [B,2,431,431] tensor (csrc/train_attn.inc)
-            xo = ops.attention(qq, kk, vv, Hh, 1.0 / math.sqrt(d), rates.mdr_self, gen, training)
-        else:                           # the same core composed from the primitives (the cross-check of tests/test_gpu_train_fused.py)
-            qh, kh, vh = [ops.reshape(t, B, V, Hh, d).transpose(1, 2) for t in (qq, kk, vv)]
-            pa = ops.dropout(ops.softmax(ops.matmul(qh, kh.transpose(-2, -1), 1.0 / math.sqrt(d))), rates.mdr_self, gen, training)
-            xo = ops.contiguous(ops.matmul(pa, vh).transpose(1, 2)).reshape(B, V, E)
+        # one launch forward / three backward, no [B,2,431,431] tensor (csrc/train_attn.inc)
+        xo = ops.attention(qq, kk, vv, Hh, 1.0 / math.sqrt(d), rates.mdr_self, gen, training)
         xo = ops.linear(xo, g(sa + '3.weight'), g(sa + '3.bias'))
-        vf = ops.drop_fused(xo, res, False, rates.mdr_self, 0.0, gen, training) if FUSED_SELF_ATTENTION else \
-            ops.add(res, ops.dropout(xo, rates.mdr_self, gen, training))                         # MDR.py:143
+        vf = ops.drop_fused(xo, res, False, rates.mdr_self, 0.0, gen, training)                # MDR.py:143
     # MDR head (MDR.py:156-168)
     va, vb, vs = ops.fork(vf, 3)
     ac = ops.linear(va, g('motion_linear.weight'), g('motion_linear.bias'))
@@ -284,10 +223,7 @@ def mdr_forward(P, c, pc, gen, rates, training=True, buffers=None, p='pose2mesh.
     elif training:
         rm = buffers.get(p + 'bias_norm.running_mean') if buffers is not None else None
         rv = buffers.get(p + 'bias_norm.running_var') if buffers is not None else None
-        if FUSED_SELF_ATTENTION:        # one launch per direction, one workgroup per vertex channel
-            mat_b = ops.batchnorm_train(mat_b, g('bias_norm.weight'), g('bias_norm.bias'), rm, rv)
-        else:
-            mat_b = _batchnorm_train(mat_b, g('bias_norm.weight'), g('bias_norm.bias'), rm, rv)
+        mat_b = ops.batchnorm_train(mat_b, g('bias_norm.weight'), g('bias_norm.bias'), rm, rv)      # one launch per direction, one workgroup per vertex channel
     else:
         rm, rv = buffers[p + 'bias_norm.running_mean'].reshape(1, -1, 1), buffers[p + 'bias_norm.running_var'].reshape(1, -1, 1)
         xh = ops.mul(ops.sub(mat_b, rm), ops.raw_unary(ops.U_RSQRT, ops.raw_unary(ops.U_AFFINE, rv, 1.0, 1e-5)))

@@ -5,6 +5,7 @@ torch is the plumbing here: tensors own device memory, views (reshape / permute 
 libgator_hip.so; nothing in this module calls an aten compute op on the data path, and there is no CPU path: inputs must live on
 a HIP device.  The reference gets the same operations from aten through autograd (lib/core/base.py:135-153)."""
 import ctypes
+import math
 
 import torch
 
@@ -17,7 +18,8 @@ ADD, SUB, MUL, DIV = 0, 1, 2, 3
 U_AFFINE, U_GELU, U_DGELU, U_EXP, U_RSQRT, U_SQRT, U_RECIP, U_ABS, U_SIGN, U_POWBASE, U_SQUARE, U_GT = range(12)
 
 
-def _stream(t):
+def stream_of(t):
+    """The current stream of t's device, as the C ABI's gator_stream."""
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
@@ -50,7 +52,7 @@ def raw_binary(op, a, b, out=None):
     n4, sa = _v4(ae)
     _, sb = _v4(be)
     _, so = _v4(out)
-    _call('gator_t_binary', op, ae.data_ptr(), _I64x4(*sa), be.data_ptr(), _I64x4(*sb), out.data_ptr(), _I64x4(*so), _I64x4(*n4), _stream(a))
+    _call('gator_t_binary', op, ae.data_ptr(), _I64x4(*sa), be.data_ptr(), _I64x4(*sb), out.data_ptr(), _I64x4(*so), _I64x4(*n4), stream_of(a))
     return out
 
 
@@ -59,7 +61,7 @@ def raw_unary(op, x, p0=0.0, p1=0.0, out=None):
         out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
     n4, sx = _v4(x)
     _, so = _v4(out)
-    _call('gator_t_unary', op, x.data_ptr(), _I64x4(*sx), out.data_ptr(), _I64x4(*so), _I64x4(*n4), float(p0), float(p1), _stream(x))
+    _call('gator_t_unary', op, x.data_ptr(), _I64x4(*sx), out.data_ptr(), _I64x4(*so), _I64x4(*n4), float(p0), float(p1), stream_of(x))
     return out
 
 
@@ -84,7 +86,7 @@ def raw_sum(x, dims, keepdim=False, out=None, accumulate=False):
     lib = _lib.load()
     nbytes = int(lib.gator_t_reduce_ws_bytes(_I64x4(*n4), _I32x4(*red)))
     ws = torch.empty(max(nbytes, 8), device=x.device, dtype=torch.uint8)
-    _call('gator_t_reduce_sum', x.data_ptr(), _I64x4(*sx), _I64x4(*n4), _I32x4(*red), out.data_ptr(), int(accumulate), ws.data_ptr(), _stream(x))
+    _call('gator_t_reduce_sum', x.data_ptr(), _I64x4(*sx), _I64x4(*n4), _I32x4(*red), out.data_ptr(), int(accumulate), ws.data_ptr(), stream_of(x))
     if not keepdim:
         out = out.reshape([x.shape[i] for i in range(x.dim()) if i not in dims])
     return out
@@ -102,6 +104,12 @@ def sum_to(g, shape):
     return raw_sum(g, dims, keepdim=True).reshape(shape)
 
 
+def _ksplit(M, N, K):
+    """K slices of an unbatched M x N product.  Few output tiles, long K: slices of >= 128 fill the chip."""
+    tiles = ((M + 63) // 64) * ((N + 63) // 64)
+    return max(1, min(64, K // 128, 1024 // tiles)) if (K >= 512 and tiles < 256) else 1
+
+
 def raw_gemm(a, b, out=None, bias=None, alpha=1.0, accumulate=False, a_rowsum=None):
     """a [n1,n2,M,K] x b [n1,n2,K,N] (any strides, stride 0 = broadcast) -> out [n1,n2,M,N].  a_rowsum [M]: also alpha * a.sum(K)."""
     n1, n2, M, K = a.shape
@@ -109,15 +117,11 @@ def raw_gemm(a, b, out=None, bias=None, alpha=1.0, accumulate=False, a_rowsum=No
     if out is None:
         out = torch.empty((n1, n2, M, N), device=a.device, dtype=torch.float32)
     sa, sb, so = a.stride(), b.stride(), out.stride()
-    ksplit, ws = 1, None
-    tiles = ((M + 63) // 64) * ((N + 63) // 64)
-    if n1 * n2 == 1 and K >= 512 and tiles < 256:          # few output tiles, long K: slices of >= 128 fill the chip
-        ksplit = max(1, min(64, K // 128, 1024 // tiles))
-        if ksplit > 1:
-            ws = torch.empty(ksplit * (M * N + M), device=a.device, dtype=torch.float32)
+    ksplit = _ksplit(M, N, K) if n1 * n2 == 1 else 1
+    ws = torch.empty(ksplit * (M * N + M), device=a.device, dtype=torch.float32) if ksplit > 1 else None
     _call('gator_t_gemm', a.data_ptr(), b.data_ptr(), out.data_ptr(), M, N, K, _I64x2(sa[2], sa[3]), _I64x2(sb[2], sb[3]), _I64x2(so[2], so[3]),
           n1, n2, _I64x2(sa[0], sa[1]), _I64x2(sb[0], sb[1]), _I64x2(so[0], so[1]), bias.data_ptr() if bias is not None else None, float(alpha),
-          int(accumulate), ksplit, ws.data_ptr() if ws is not None else None, a_rowsum.data_ptr() if a_rowsum is not None else None, _stream(a))
+          int(accumulate), ksplit, ws.data_ptr() if ws is not None else None, a_rowsum.data_ptr() if a_rowsum is not None else None, stream_of(a))
     return out
 
 
@@ -139,6 +143,16 @@ def grad_slot(p, part=None):
     return sl
 
 
+def slot_view(p, shape):
+    """p.reshape(shape) for a parameter view p; the result keeps p's slice of the flat gradient buffer.  The slot is forwarded, not
+    consumed: the slot-aware op that the result feeds is the one writer."""
+    v = p.reshape(shape)
+    slot = getattr(p, '_gslot', None)
+    if slot is not None:
+        v._gslot = slot.reshape(shape)
+    return v
+
+
 def raw_copy(x):
     """Contiguous copy through the library's strided copy kernel."""
     if x.dim() > 4:
@@ -148,6 +162,11 @@ def raw_copy(x):
 
 def _contig(x):
     return x if x.is_contiguous() else raw_copy(x)
+
+
+def _rows(x):
+    """[..., C] -> the flattened rows [1, 1, R, C] (contiguous), the operand form of raw_gemm"""
+    return _contig(x).reshape(1, 1, -1, x.shape[-1])
 
 
 # ------------------------------------------------------------------------------------------------ deferred weight gradients
@@ -167,7 +186,6 @@ class Deferred:
     them here instead of launching each between two links of the dependent activation-gradient chain, and `flush()` - called by
     the last backward node, the parameter scatter - runs the whole list as ONE grouped GEMM launch (+ one split-K finish):
     ~70 small products that fill the chip together instead of ~230 latency-bound launches on the critical path."""
-    enabled = True
     queue = []
     retired = []
     pool = None        # pinned host memory for the problem tables of CAPTURED steps (a replayed graph re-reads its table); allocated
@@ -208,12 +226,11 @@ def run_group(problems, dev):
         arr = (_lib.GemmProblem * n)()                 # pageable: the upload is staged before the call returns
     for p, (a4, b4, out4, rowsum, bias) in zip(arr, problems):
         M, K, N = a4.shape[2], a4.shape[3], b4.shape[3]
-        tiles = ((M + 63) // 64) * ((N + 63) // 64)
         p.A, p.B, p.C = a4.data_ptr(), b4.data_ptr(), out4.data_ptr()
         p.a_rowsum = rowsum.data_ptr() if rowsum is not None else None
         p.bias = bias.data_ptr() if bias is not None else None
         p.M, p.N, p.K = M, N, K
-        p.ksplit = max(1, min(64, K // 128, 1024 // tiles)) if (K >= 512 and tiles < 256) else 1
+        p.ksplit = _ksplit(M, N, K)
         p.stride_a[0], p.stride_a[1] = a4.stride(2), a4.stride(3)
         p.stride_b[0], p.stride_b[1] = b4.stride(2), b4.stride(3)
         p.stride_c[0], p.stride_c[1] = out4.stride(2), out4.stride(3)
@@ -224,7 +241,35 @@ def run_group(problems, dev):
         raise RuntimeError('gator_t_gemm_grouped_prepare rejected the problem list')
     ws = torch.empty(max(ws_floats, 1), device=dev, dtype=torch.float32)
     table = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    _call('gator_t_gemm_grouped', arr, n, table.data_ptr(), ws.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    _call('gator_t_gemm_grouped', arr, n, table.data_ptr(), ws.data_ptr(), stream_of(table))
+
+
+def _grad_product(a4, b4, slot, need_rowsum=False, rowsum_slot=None, out=None):
+    """Where the parameter gradient a4 [1,1,M,K] . b4 [1,1,K,N] goes (and, with need_rowsum, the row sums of a4: the bias gradient of a
+    linear).  A parameter with a slot has the product queued on Deferred, into the slot; the row sums ride on that product only when
+    they have a slot too (or are not needed).  Everything else runs now: into the slot if there is one, else into `out` ([M, N] of
+    the caller's) or a fresh tensor.  -> (what holds the product, what holds the row sums or None), for the backward to hand on."""
+    M, N = a4.shape[2], b4.shape[3]
+    rowsum = None
+    if need_rowsum:
+        rowsum = rowsum_slot if rowsum_slot is not None else torch.empty(M, device=a4.device, dtype=torch.float32)
+    dest = slot if slot is not None else out
+    dest4 = dest.view(1, 1, M, N) if dest is not None else None
+    if slot is not None and (rowsum is None or rowsum_slot is not None):
+        Deferred.add(a4, b4, dest4, rowsum)              # lands in the flat gradient buffer: grouped launch
+        return slot, rowsum
+    res = raw_gemm(a4, b4, out=dest4, a_rowsum=rowsum)
+    return (dest if dest is not None else res.reshape(M, N)), rowsum
+
+
+def _grad_colsum(x, slot):
+    """Where the parameter gradient x [R, ...].sum(0) goes (x contiguous): with a slot, queued on Deferred as the product
+    ones [1, R] . x [R, n] into the slot; without one, a reduction now into a fresh tensor."""
+    if slot is None:
+        return raw_sum(x, [0])
+    R, n = x.shape[0], x.numel() // x.shape[0]
+    Deferred.add(_one(x.device).as_strided((1, 1, 1, R), (0, 0, 0, 0)), x.view(1, 1, R, n), slot.view(1, 1, 1, n), None)
+    return slot
 
 
 # ------------------------------------------------------------------------------------------------ differentiable ops
@@ -285,7 +330,6 @@ class _Unary(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        import math
         op = ctx.op
         x, y = ctx.saved_tensors
         if op == U_AFFINE:
@@ -420,7 +464,7 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b):
         _need_device(x, w, b)
-        x2 = _contig(x).reshape(1, 1, -1, x.shape[-1])
+        x2 = _rows(x)
         w4 = w.reshape(1, 1, w.shape[0], w.shape[1])
         ctx.save_for_backward(x2, w4)
         ctx.xshape, ctx.has_b = x.shape, b is not None
@@ -431,19 +475,13 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x2, w4 = ctx.saved_tensors
-        g2 = _contig(g).reshape(1, 1, -1, g.shape[-1])
+        g2 = _rows(g)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = raw_gemm(g2, w4).reshape(ctx.xshape)
         need_b = ctx.has_b and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:                      # dW = dY^T X; the bias gradient (row sums of dY^T) rides on the same launch
-            gb = (ctx.bslot if ctx.bslot is not None else torch.empty(w4.shape[2], device=g.device, dtype=torch.float32)) if need_b else None
-            if Deferred.enabled and ctx.wslot is not None and (gb is None or ctx.bslot is not None):
-                Deferred.add(g2.transpose(2, 3), x2, ctx.wslot.view(w4.shape), gb)       # lands in the flat gradient buffer: grouped launch
-                gw = ctx.wslot
-            else:
-                gw = raw_gemm(g2.transpose(2, 3), x2, a_rowsum=gb, out=ctx.wslot.view(w4.shape) if ctx.wslot is not None else None)
-                gw = ctx.wslot if ctx.wslot is not None else gw.reshape(w4.shape[2], w4.shape[3])
+            gw, gb = _grad_product(g2.transpose(2, 3), x2, ctx.wslot, need_b, ctx.bslot)
         elif need_b:
             gb = raw_sum(g2.reshape(-1, g2.shape[-1]), [0])
         return gx, gw, gb
@@ -461,7 +499,7 @@ class _LinearGroup(torch.autograd.Function):
     def forward(ctx, n, *args):                           # args = x_0, w_0, b_0, x_1, w_1, b_1, ...
         xs, ws, bs = args[0::3], args[1::3], args[2::3]
         _need_device(*xs)
-        x2s = [_contig(x).reshape(1, 1, -1, x.shape[-1]) for x in xs]
+        x2s = [_rows(x) for x in xs]
         w4s = [w.reshape(1, 1, w.shape[0], w.shape[1]) for w in ws]
         outs = [torch.empty((1, 1, x2.shape[2], w4.shape[2]), device=x2.device, dtype=torch.float32) for x2, w4 in zip(x2s, w4s)]
         run_group([(x2, w4.transpose(2, 3), o, None, b) for x2, w4, o, b in zip(x2s, w4s, outs, bs)], x2s[0].device)
@@ -475,7 +513,7 @@ class _LinearGroup(torch.autograd.Function):
     def backward(ctx, *gs):
         n = ctx.n
         x2s, w4s = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
-        g2s = [_contig(g).reshape(1, 1, -1, g.shape[-1]) for g in gs]
+        g2s = [_rows(g) for g in gs]
         grads = [None] * (3 * n)
         gxs = [torch.empty(x2.shape, device=x2.device, dtype=torch.float32) if ctx.needs_input_grad[1 + 3 * i] else None for i, x2 in enumerate(x2s)]
         probs = [(g2s[i], w4s[i], gxs[i], None, None) for i in range(n) if gxs[i] is not None]
@@ -484,16 +522,9 @@ class _LinearGroup(torch.autograd.Function):
         for i in range(n):
             if gxs[i] is not None:
                 grads[3 * i] = gxs[i].reshape(ctx.xshapes[i])
-            w4 = w4s[i]
             need_b = ctx.has_b[i] and ctx.needs_input_grad[3 + 3 * i]
             if ctx.needs_input_grad[2 + 3 * i]:
-                gb = (ctx.bslots[i] if ctx.bslots[i] is not None else torch.empty(w4.shape[2], device=w4.device, dtype=torch.float32)) if need_b else None
-                if Deferred.enabled and ctx.wslots[i] is not None and (gb is None or ctx.bslots[i] is not None):
-                    Deferred.add(g2s[i].transpose(2, 3), x2s[i], ctx.wslots[i].view(w4.shape), gb)
-                    grads[3 * i + 1] = ctx.wslots[i]
-                else:
-                    grads[3 * i + 1] = raw_gemm(g2s[i].transpose(2, 3), x2s[i], a_rowsum=gb).reshape(w4.shape[2], w4.shape[3])
-                grads[3 * i + 2] = gb
+                grads[3 * i + 1], grads[3 * i + 2] = _grad_product(g2s[i].transpose(2, 3), x2s[i], ctx.wslots[i], need_b, ctx.bslots[i])
             elif need_b:
                 grads[3 * i + 2] = raw_sum(g2s[i].reshape(-1, g2s[i].shape[-1]), [0])
         return (None,) + tuple(grads)
@@ -515,7 +546,7 @@ class _XW(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, k):
         _need_device(x, W)
-        x2 = _contig(x).reshape(1, 1, -1, x.shape[-1])
+        x2 = _rows(x)
         wk = W.narrow(0, k, 1).reshape(1, 1, W.shape[1], W.shape[2])
         ctx.save_for_backward(x2, wk)
         ctx.xshape, ctx.k, ctx.wshape = x.shape, k, W.shape
@@ -527,18 +558,18 @@ class _XW(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x2, wk = ctx.saved_tensors
-        g2 = _contig(g).reshape(1, 1, -1, g.shape[-1])
+        g2 = _rows(g)
         gx = raw_gemm(g2, wk.transpose(2, 3)).reshape(ctx.xshape) if ctx.needs_input_grad[0] else None
         gW = None
         if ctx.needs_input_grad[1]:
-            if Deferred.enabled and ctx.wslot is not None:
-                Deferred.add(x2.transpose(2, 3), g2, ctx.wslot, None)
+            if ctx.wslot is not None:
                 # every slice writes into the SAME slot tensor: hand it to autograd once (slice 0), or the engine would add the
                 # tensor to itself for each further use of W
-                gW = ctx.full if ctx.k == 0 else None
+                gW, out = (ctx.full if ctx.k == 0 else None), None
             else:
                 gW = zeros(ctx.wshape, g.device)
-                raw_gemm(x2.transpose(2, 3), g2, out=gW.narrow(0, ctx.k, 1).view(1, 1, ctx.wshape[1], ctx.wshape[2]))
+                out = gW.narrow(0, ctx.k, 1)
+            _grad_product(x2.transpose(2, 3), g2, ctx.wslot, out=out)
         return gx, gW, None
 
 
@@ -553,7 +584,7 @@ class _Softmax(torch.autograd.Function):
         xc = _contig(x)
         p = torch.empty_like(xc)
         n = xc.shape[-1]
-        _call('gator_t_softmax_fwd', xc.data_ptr(), xc.numel() // n, n, p.data_ptr(), _stream(x))
+        _call('gator_t_softmax_fwd', xc.data_ptr(), xc.numel() // n, n, p.data_ptr(), stream_of(x))
         ctx.save_for_backward(p)
         return p
 
@@ -563,7 +594,7 @@ class _Softmax(torch.autograd.Function):
         gc = _contig(g)
         dx = torch.empty_like(p)
         n = p.shape[-1]
-        _call('gator_t_softmax_bwd', p.data_ptr(), gc.data_ptr(), p.numel() // n, n, dx.data_ptr(), _stream(p))
+        _call('gator_t_softmax_bwd', p.data_ptr(), gc.data_ptr(), p.numel() // n, n, dx.data_ptr(), stream_of(p))
         return dx
 
 
@@ -586,7 +617,7 @@ class _LayerNorm(torch.autograd.Function):
         mean = torch.empty(rows, device=x.device, dtype=torch.float32)
         rinv = torch.empty(rows, device=x.device, dtype=torch.float32)
         _call('gator_t_layernorm_fwd', xc.data_ptr(), rows, n, w.data_ptr() if w is not None else None, b.data_ptr() if b is not None else None,
-              float(eps), int(mode), y.data_ptr(), mean.data_ptr(), rinv.data_ptr(), _stream(x))
+              float(eps), int(mode), y.data_ptr(), mean.data_ptr(), rinv.data_ptr(), stream_of(x))
         ctx.save_for_backward(xc, mean, rinv, w)
         ctx.eps, ctx.mode, ctx.has_b = eps, mode, b is not None
         ctx.wslot, ctx.bslot = grad_slot(w) if w is not None else None, grad_slot(b) if b is not None else None
@@ -609,22 +640,9 @@ class _LayerNorm(torch.autograd.Function):
         need_w = w is not None and ctx.needs_input_grad[1]
         dyx = torch.empty_like(xc) if need_w else None
         _call('gator_t_layernorm_bwd', gc.data_ptr(), xc.data_ptr(), mean.data_ptr(), rinv.data_ptr(), w.data_ptr() if w is not None else None, rows, n,
-              float(ctx.eps), int(ctx.mode), dx.data_ptr(), dyx.data_ptr() if need_w else None, add.data_ptr() if add is not None else None, _stream(xc))
-        gw = gb = None
-        grouped = Deferred.enabled
-        ones = _one(xc.device).as_strided((1, 1, 1, rows), (0, 0, 0, 0)) if grouped else None      # column sums as 1 x rows products
-        if need_w:
-            if grouped and ctx.wslot is not None:
-                Deferred.add(ones, dyx.view(1, 1, rows, n), ctx.wslot.view(1, 1, 1, n), None)
-                gw = ctx.wslot
-            else:
-                gw = raw_sum(dyx.reshape(rows, n), [0], keepdim=True, out=ctx.wslot.view(1, n) if ctx.wslot is not None else None).reshape(n)
-        if ctx.has_b and ctx.needs_input_grad[2]:
-            if grouped and ctx.bslot is not None:
-                Deferred.add(ones, gc.view(1, 1, rows, n), ctx.bslot.view(1, 1, 1, n), None)
-                gb = ctx.bslot
-            else:
-                gb = raw_sum(gc.reshape(rows, n), [0], keepdim=True, out=ctx.bslot.view(1, n) if ctx.bslot is not None else None).reshape(n)
+              float(ctx.eps), int(ctx.mode), dx.data_ptr(), dyx.data_ptr() if need_w else None, add.data_ptr() if add is not None else None, stream_of(xc))
+        gw = _grad_colsum(dyx.view(rows, n), ctx.wslot) if need_w else None
+        gb = _grad_colsum(gc.view(rows, n), ctx.bslot) if ctx.has_b and ctx.needs_input_grad[2] else None
         return dx, gw, gb, None, None, None
 
 
@@ -654,14 +672,21 @@ class Generator:
     def begin_step(self):
         if self.counter is not None:
             self.offset = 0
-            _call('gator_t_step_advance', self.counter.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(self.counter.device).cuda_stream))
+            _call('gator_t_step_advance', self.counter.data_ptr(), stream_of(self.counter))
 
-    def next_offset(self):
-        self.offset += 1
-        return self.offset
-
-    def counter_ptr(self):
-        return self.counter.data_ptr() if self.counter is not None else None
+    @staticmethod
+    def draw(gen, *on):
+        """One mask of `gen` per flag, in order: (seed, offset_0, ..., pointer to the step counter or None).  A mask that is on takes
+        a fresh offset; one that is off gets offset 0 and takes none.  All off: (0, 0, ..., None), and gen may be None (an op that
+        was called without a generator)."""
+        offsets = []
+        for o in on:
+            if o:
+                gen.offset += 1
+            offsets.append(gen.offset if o else 0)
+        if not any(on):
+            return (0, *offsets, None)
+        return (gen.seed, *offsets, gen.counter.data_ptr() if gen.counter is not None else None)
 
 
 class _Dropout(torch.autograd.Function):
@@ -672,7 +697,7 @@ class _Dropout(torch.autograd.Function):
         out = torch.empty_like(xc)
         mask = torch.empty(xc.shape, device=x.device, dtype=torch.uint8)
         _call('gator_t_dropout', xc.data_ptr(), xc.numel(), float(rate), ctypes.c_uint64(seed), ctypes.c_uint64(offset), counter, out.data_ptr(),
-              mask.data_ptr(), _stream(x))
+              mask.data_ptr(), stream_of(x))
         ctx.save_for_backward(mask)
         ctx.scale = 1.0 / (1.0 - rate)
         return out
@@ -682,7 +707,7 @@ class _Dropout(torch.autograd.Function):
         mask, = ctx.saved_tensors
         gc = _contig(g)
         out = torch.empty_like(gc)
-        _call('gator_t_mask_scale', gc.data_ptr(), mask.data_ptr(), gc.numel(), float(ctx.scale), out.data_ptr(), _stream(gc))
+        _call('gator_t_mask_scale', gc.data_ptr(), mask.data_ptr(), gc.numel(), float(ctx.scale), out.data_ptr(), stream_of(gc))
         return out, None, None, None, None
 
 
@@ -690,7 +715,7 @@ def dropout(x, rate, gen, training=True):
     """nn.Dropout: identity when not training or rate == 0."""
     if not training or rate <= 0.0:
         return x
-    return _Dropout.apply(x, float(rate), gen.seed, gen.next_offset(), gen.counter_ptr())
+    return _Dropout.apply(x, float(rate), *Generator.draw(gen, True))
 
 
 def drop_path(x, rate, gen, training=True):
@@ -700,8 +725,8 @@ def drop_path(x, rate, gen, training=True):
     B = x.shape[0]
     factor = torch.empty(B, device=x.device, dtype=torch.float32)
     mask = torch.empty(B, device=x.device, dtype=torch.uint8)
-    _call('gator_t_dropout', None, B, float(rate), ctypes.c_uint64(gen.seed), ctypes.c_uint64(gen.next_offset()), gen.counter_ptr(), factor.data_ptr(),
-          mask.data_ptr(), _stream(x))
+    seed, offset, counter = Generator.draw(gen, True)
+    _call('gator_t_dropout', None, B, float(rate), ctypes.c_uint64(seed), ctypes.c_uint64(offset), counter, factor.data_ptr(), mask.data_ptr(), stream_of(x))
     return mul(x, factor.reshape([B] + [1] * (x.dim() - 1)))
 
 
@@ -717,7 +742,7 @@ class _Attention(torch.autograd.Function):
         o = torch.empty_like(q)
         lse = torch.empty((B, heads, T), device=q.device, dtype=torch.float32)
         _call('gator_t_attn_fwd', q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), B, heads, T, k.shape[1], HD // heads, float(scale),
-              float(rate), ctypes.c_uint64(seed), ctypes.c_uint64(offset), counter, _stream(q))
+              float(rate), ctypes.c_uint64(seed), ctypes.c_uint64(offset), counter, stream_of(q))
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.cfg = (heads, scale, rate, seed, offset, counter)
         return o
@@ -737,7 +762,7 @@ class _Attention(torch.autograd.Function):
         dsum = torch.empty_like(lse)
         _call('gator_t_attn_bwd', q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), gc.data_ptr(), dq.data_ptr(), dk.data_ptr(),
               dv.data_ptr(), dsum.data_ptr(), B, heads, T, Tk, HD // heads, float(scale), float(rate), ctypes.c_uint64(seed), ctypes.c_uint64(offset), counter,
-              qsplit, _stream(q))
+              qsplit, stream_of(q))
         if qsplit > 1:
             dk, dv = raw_sum(dk.view(qsplit, -1), [0]).view(k.shape), raw_sum(dv.view(qsplit, -1), [0]).view(v.shape)
         else:
@@ -748,8 +773,7 @@ class _Attention(torch.autograd.Function):
 def attention(q, k, v, heads, scale, rate=0.0, gen=None, training=True):
     """q [B, T, heads*32], k, v [B, Tk, heads*32] -> [B, T, heads*32]"""
     on = training and rate > 0.0
-    return _Attention.apply(q, k, v, int(heads), float(scale), float(rate) if on else 0.0, gen.seed if on else 0, gen.next_offset() if on else 0,
-                            gen.counter_ptr() if on else None)
+    return _Attention.apply(q, k, v, int(heads), float(scale), float(rate) if on else 0.0, *Generator.draw(gen, on))
 
 
 class _AttentionSmall(torch.autograd.Function):
@@ -764,7 +788,7 @@ class _AttentionSmall(torch.autograd.Function):
         o = torch.empty((B, J, C), device=qkv.device, dtype=torch.float32)
         P = torch.empty((B, heads, J, J), device=qkv.device, dtype=torch.float32)
         _call('gator_t_attn_small_fwd', qkv.data_ptr(), bias.data_ptr(), o.data_ptr(), P.data_ptr(), B, heads, J, C // heads, float(scale), float(rate),
-              ctypes.c_uint64(seed), ctypes.c_uint64(offset), counter, _stream(qkv))
+              ctypes.c_uint64(seed), ctypes.c_uint64(offset), counter, stream_of(qkv))
         ctx.save_for_backward(qkv, bias, P)
         ctx.cfg = (heads, scale, rate, seed, offset, counter)
         return o
@@ -778,7 +802,7 @@ class _AttentionSmall(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         dS = torch.empty_like(P)
         _call('gator_t_attn_small_bwd', qkv.data_ptr(), bias.data_ptr(), P.data_ptr(), gc.data_ptr(), dqkv.data_ptr(), dS.data_ptr(), B, heads, J,
-              C3 // 3 // heads, float(scale), float(rate), ctypes.c_uint64(seed), ctypes.c_uint64(offset), counter, _stream(qkv))
+              C3 // 3 // heads, float(scale), float(rate), ctypes.c_uint64(seed), ctypes.c_uint64(offset), counter, stream_of(qkv))
         dbias = raw_sum(dS, [0]) if ctx.needs_input_grad[1] else None
         return dqkv, dbias, None, None, None, None, None, None
 
@@ -786,8 +810,7 @@ class _AttentionSmall(torch.autograd.Function):
 def attention_small(qkv, bias, heads, scale, rate=0.0, gen=None, training=True):
     """qkv [B,J,3*heads*16] (the GAT in-projection's output), bias [heads,J,J] -> attention output [B,J,heads*16]"""
     on = training and rate > 0.0
-    return _AttentionSmall.apply(qkv, bias, int(heads), float(scale), float(rate) if on else 0.0, gen.seed if on else 0, gen.next_offset() if on else 0,
-                                 gen.counter_ptr() if on else None)
+    return _AttentionSmall.apply(qkv, bias, int(heads), float(scale), float(rate) if on else 0.0, *Generator.draw(gen, on))
 
 
 class _Mgcn(torch.autograd.Function):
@@ -799,7 +822,7 @@ class _Mgcn(torch.autograd.Function):
         h0, h1, adj, Mc, bc = _contig(h0), _contig(h1), _contig(adj), _contig(M), _contig(bias)
         B, J, C = h0.shape
         out = torch.empty_like(h0)
-        _call('gator_t_mgcn_fwd', h0.data_ptr(), h1.data_ptr(), adj.data_ptr(), Mc.data_ptr(), bc.data_ptr(), out.data_ptr(), B, J, C, _stream(h0))
+        _call('gator_t_mgcn_fwd', h0.data_ptr(), h1.data_ptr(), adj.data_ptr(), Mc.data_ptr(), bc.data_ptr(), out.data_ptr(), B, J, C, stream_of(h0))
         ctx.save_for_backward(h0, h1, adj, Mc)
         ctx.mslot, ctx.bslot = grad_slot(M), grad_slot(bias)
         return out
@@ -812,18 +835,9 @@ class _Mgcn(torch.autograd.Function):
         dh0, dh1, pm = torch.empty_like(h0), torch.empty_like(h0), torch.empty_like(h0)
         dadj = torch.empty((B, J, J), device=g.device, dtype=torch.float32)
         _call('gator_t_mgcn_bwd', h0.data_ptr(), h1.data_ptr(), adj.data_ptr(), M.data_ptr(), gc.data_ptr(), dh0.data_ptr(), dh1.data_ptr(), pm.data_ptr(),
-              dadj.data_ptr(), B, J, C, _stream(g))
-        ones = lambda n: _one(g.device).as_strided((1, 1, 1, n), (0, 0, 0, 0))
-        if Deferred.enabled and ctx.mslot is not None:
-            Deferred.add(ones(B), pm.view(1, 1, B, J * C), ctx.mslot.view(1, 1, 1, J * C), None)
-            gM = ctx.mslot
-        else:
-            gM = raw_sum(pm, [0])
-        if Deferred.enabled and ctx.bslot is not None:
-            Deferred.add(ones(B * J), gc.view(1, 1, B * J, C), ctx.bslot.view(1, 1, 1, C), None)
-            gb = ctx.bslot
-        else:
-            gb = raw_sum(gc.reshape(B * J, C), [0])
+              dadj.data_ptr(), B, J, C, stream_of(g))
+        gM = _grad_colsum(pm, ctx.mslot)
+        gb = _grad_colsum(gc.view(B * J, C), ctx.bslot)
         return dh0, dh1, raw_sum(dadj, [0]), gM, gb
 
 
@@ -845,7 +859,7 @@ class _DropFused(torch.autograd.Function):
         fac = torch.empty(xc.shape[0], device=x.device, dtype=torch.float32) if (path_rate > 0 and path_offset) else None
         _call('gator_t_drop_fused', xc.data_ptr(), rc.data_ptr() if rc is not None else None, n, per, int(gelu), float(rate), ctypes.c_uint64(seed),
               ctypes.c_uint64(offset), float(path_rate), ctypes.c_uint64(path_offset), counter, out.data_ptr(), mask.data_ptr() if mask is not None else None,
-              fac.data_ptr() if fac is not None else None, _stream(x))
+              fac.data_ptr() if fac is not None else None, stream_of(x))
         ctx.save_for_backward(xc if gelu else None, mask, fac)
         ctx.cfg = (gelu, rate, res is not None)
         return out
@@ -860,7 +874,7 @@ class _DropFused(torch.autograd.Function):
         else:
             dx = torch.empty_like(gc)
             _call('gator_t_drop_fused_bwd', gc.data_ptr(), x.data_ptr() if x is not None else None, mask.data_ptr() if mask is not None else None,
-                  fac.data_ptr() if fac is not None else None, gc.numel(), gc.numel() // gc.shape[0], int(gelu), float(rate), dx.data_ptr(), _stream(gc))
+                  fac.data_ptr() if fac is not None else None, gc.numel(), gc.numel() // gc.shape[0], int(gelu), float(rate), dx.data_ptr(), stream_of(gc))
         return dx, (gc if has_res else None), None, None, None, None, None, None, None
 
 
@@ -868,12 +882,10 @@ def drop_fused(x, res=None, gelu=False, rate=0.0, path_rate=0.0, gen=None, train
     """res + drop_path(dropout(gelu?(x), rate), path_rate) - offsets drawn in that order, as the composed chain draws them."""
     d_on = training and rate > 0.0
     p_on = training and path_rate > 0.0
-    off = gen.next_offset() if d_on else 0
-    poff = gen.next_offset() if p_on else 0
     if not gelu and not d_on and not p_on:
         return x if res is None else add(res, x)
-    return _DropFused.apply(x, res, bool(gelu), float(rate) if d_on else 0.0, gen.seed if (d_on or p_on) else 0, off, float(path_rate) if p_on else 0.0, poff,
-                            gen.counter_ptr() if (d_on or p_on) else None)
+    seed, off, poff, counter = Generator.draw(gen, d_on, p_on)
+    return _DropFused.apply(x, res, bool(gelu), float(rate) if d_on else 0.0, seed, off, float(path_rate) if p_on else 0.0, poff, counter)
 
 
 class _BatchNormTrain(torch.autograd.Function):
@@ -889,7 +901,7 @@ class _BatchNormTrain(torch.autograd.Function):
         rinv = torch.empty(C, device=x.device, dtype=torch.float32)
         _call('gator_t_batchnorm_fwd', xc.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(), rinv.data_ptr(),
               run_mean.data_ptr() if run_mean is not None else None, run_var.data_ptr() if run_var is not None else None, B, C, L, float(eps),
-              float(momentum), _stream(x))
+              float(momentum), stream_of(x))
         ctx.save_for_backward(xc, w, mean, rinv)
         ctx.wslot, ctx.bslot = grad_slot(w), grad_slot(b)
         return y
@@ -903,7 +915,7 @@ class _BatchNormTrain(torch.autograd.Function):
         dw = ctx.wslot if ctx.wslot is not None else torch.empty(C, device=g.device, dtype=torch.float32)
         db = ctx.bslot if ctx.bslot is not None else torch.empty(C, device=g.device, dtype=torch.float32)
         _call('gator_t_batchnorm_bwd', gc.data_ptr(), xc.data_ptr(), w.data_ptr(), mean.data_ptr(), rinv.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-              db.data_ptr(), B, C, L, _stream(g))
+              db.data_ptr(), B, C, L, stream_of(g))
         return dx, dw, db, None, None, None, None
 
 
@@ -1049,7 +1061,7 @@ class _Fork(torch.autograd.Function):
             if all(t.is_contiguous() and t.shape == acc.shape for t in take) and acc.is_contiguous():
                 out = torch.empty_like(acc)
                 ptr = [t.data_ptr() for t in take] + [None] * (3 - len(take))
-                _call('gator_t_add_n', acc.data_ptr(), ptr[0], ptr[1], ptr[2], out.data_ptr(), acc.numel(), _stream(acc))
+                _call('gator_t_add_n', acc.data_ptr(), ptr[0], ptr[1], ptr[2], out.data_ptr(), acc.numel(), stream_of(acc))
                 acc = out
             else:
                 for t in take:

@@ -1,7 +1,5 @@
 """Parameters in ONE flat device buffer + torch.optim.Adam's update as one kernel launch (lib/funcs_utils.py:91-95: Adam, lr
 only; MultiStepLR of :102-103).  The flat layout is also the data-parallel bucket: one all-reduce of `grad` per step."""
-import ctypes
-
 import numpy as np
 import torch
 
@@ -89,10 +87,9 @@ class Adam:
     def step(self, grad):
         self.step_count += 1
         f = self.p.flat
-        st = ctypes.c_void_p(torch.cuda.current_stream(f.device).cuda_stream)
         _lib.check(_lib.load().gator_t_adam(f.data_ptr(), grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.p.numel,
                                             float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_count,
-                                            self.device_step.data_ptr() if self.device_step is not None else None, st), 'gator_t_adam')
+                                            self.device_step.data_ptr() if self.device_step is not None else None, ops.stream_of(f)), 'gator_t_adam')
 
     # ---- checkpoint interchange with the reference (main/train.py:51-58 saves optimizer.state_dict(); base.py:73-77 loads it) ----
     def state_dict(self):
