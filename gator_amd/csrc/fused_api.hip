@@ -22,17 +22,9 @@ static void graphs_clear(FusedState* f) {
     for (auto& g : f->graphs) graph_slot_free(g);
     f->graphs.clear();
 }
-// The launchers read the workspace through FusedState::ws; a scope points it at set `i` and restores the previous set on exit.
-struct WsScope {
-    FusedState* f; FusedWs* prev;
-    WsScope(FusedState* f_, int i) : f(f_), prev(f_->ws) { f->ws = &f->sets[i]; }
-    ~WsScope() { f->ws = prev; }
-};
-
-// (Re-)allocates the set in use for a batch of B: one block, zeroed once, carved into its regions.
-int fused_ensure_ws(gator_ctx* c, int B) {
+// (Re-)allocates workspace set w for a batch of B: one block, zeroed once, carved into its regions.
+int fused_ensure_ws(gator_ctx* c, FusedWs& w, int B) {
     FusedState* f = c->fused;
-    FusedWs& w = *f->ws;
     if (w.base && B <= w.cap) return GATOR_OK;
     if (w.base) {
         GATOR_HIP_CHECK(hipDeviceSynchronize());
@@ -78,7 +70,7 @@ void fill_tile(float* dst, F tab) {
             for (int j = 0; j < 4; ++j) dst[(g * 64 + lane) * 4 + j] = tab(lane & 31, 8 * g + 4 * (lane >> 5) + j);
 }
 
-// Every environment switch of the fused path (fused_state.h: FusedOptions), read once per ctx, with the rules that depend only on
+// Every environment switch of the fused path (forward_plan.h: FusedOptions), read once per ctx, with the rules that depend only on
 // the switches and on gator_config.arithmetic.  Exact arithmetic (GATOR_ARITH_EXACT_SPLIT: no two-plane operand anywhere) wins over
 // the environment.
 int read_fused_options(const gator_ctx* c, FusedOptions* o) {
@@ -488,80 +480,76 @@ void fused_destroy(gator_ctx* c) {
     c->fused = nullptr;
 }
 
-int launch_upsample_any(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints, bool w1) {
-    if (f->opt.up_x3 == 0) return launch_upsample(f, c, B, verts, stream);
-    return f->opt.up_x3 == 2 ? launch_upsample_x2(f, c, B, verts, stream, with_joints, w1) : launch_upsample_x3(f, c, B, verts, stream, with_joints);
+int launch_upsample_any(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const RegressorPlan& r, int B, float* verts, void* stream) {
+    return r.form == Regressor::FP32 ? launch_upsample(f, c, ws, B, verts, stream) : r.form == Regressor::X2 ? launch_upsample_x2(f, c, ws, B, verts, stream, r.with_joints, r.w1) : launch_upsample_x3(f, c, ws, B, verts, stream, r.with_joints);
+}
+
+// The plan of one call on this ctx (forward_plan.h), or GATOR_EUNSUPPORTED with the planner's reason: before anything is queued
+static int fused_plan(const gator_ctx* c, int B, PlanEntry entry, bool bf16, bool with_joints, ForwardPlan* p) {
+    const FusedState* f = c->fused;
+    const char* why = plan_forward(f->opt, c->J, f->n_cu, B, entry, bf16, with_joints, f->gat_tiled, p);
+    return why ? fail(GATOR_EUNSUPPORTED, "%s", why) : GATOR_OK;
 }
 
 int fused_gat_forward(gator_ctx* c, const float* pose2d, int B, float* x_out, float* feat, void* stream) {
+    ForwardPlan p;
+    GATOR_TRY(fused_plan(c, B, PlanEntry::GAT, false, false, &p));
     StageTimer tm(c, "gat", stream);
-    return launch_gat(c, c->fused, pose2d, B, x_out, feat, stream);
-}
-
-static int fused_upsample_in(gator_ctx* c, const float* vert431, int B, float* verts, void* stream) {
-    int rc = fused_ensure_ws(c, B);
-    if (rc) return rc;
-    FusedState* f = c->fused;
-    rc = f->opt.up_x3 == 0 ? launch_pack_vc(vert431, B, f->ws->vcp, stream)
-         : f->opt.up_x3 == 2 ? launch_pack_vc_x2(vert431, B, f->ws->vcp3, stream) : launch_pack_vc_x3(vert431, B, f->ws->cap, f->ws->vcp3, stream);
-    if (rc) return rc;
-    StageTimer tm(c, "upsample", stream);
-    return launch_upsample_any(f, c, B, verts, stream);
+    return launch_gat(c, c->fused, p.gat, pose2d, B, x_out, feat, stream, B, 0);
 }
 
 int fused_upsample(gator_ctx* c, const float* vert431, int B, float* verts, void* stream) {
-    WsScope ws(c->fused, 0);
-    return fused_upsample_in(c, vert431, B, verts, stream);
+    FusedState* f = c->fused;
+    FusedWs& ws = f->sets[0];
+    GATOR_TRY(fused_ensure_ws(c, ws, B));
+    const RegressorPlan r = plan_regressor(f->opt, false, false);
+    int rc = r.form == Regressor::FP32 ? launch_pack_vc(vert431, B, ws.vcp, stream)
+         : r.form == Regressor::X2 ? launch_pack_vc_x2(vert431, B, ws.vcp3, stream) : launch_pack_vc_x3(vert431, B, ws.cap, ws.vcp3, stream);
+    if (rc) return rc;
+    StageTimer tm(c, "upsample", stream);
+    return launch_upsample_any(f, c, ws, r, B, verts, stream);
 }
 
-static int ensure_bf16(gator_ctx* c, int B, void* stream) {
+static int fused_upsample_bf16_in(gator_ctx* c, FusedWs& ws, const float* vert431, int B, float* verts, void* stream) {
+    GATOR_TRY(fused_ensure_ws(c, ws, B));
     FusedState* f = c->fused;
     if (!f->up_w16) {      // first bf16 call: pack the regressor weights once
         GATOR_TRY(f->up_w16.alloc(upsample_bf16_weight_elems() * 2));
-        int rc = pack_upsample_bf16(c->w.up_w, f->up_w16, stream);
-        if (rc) return rc;
+        GATOR_TRY(pack_upsample_bf16(c->w.up_w, f->up_w16, stream));
         // One-time: the pack must be COMPLETE before any other stream may read up_w16.  In sub-batch mode the second half
         // runs on a different (non-blocking) stream whose fork event was recorded before this pack was queued.
         GATOR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     }
-    if (B > f->ws->vcp16_cap) {
-        if (f->ws->vcp16) GATOR_HIP_CHECK(hipDeviceSynchronize());
-        GATOR_TRY(f->ws->vcp16.alloc(upsample_bf16_vcp_elems(B) * 2));
-        f->ws->vcp16_cap = B;
+    if (B > ws.vcp16_cap) {
+        if (ws.vcp16) GATOR_HIP_CHECK(hipDeviceSynchronize());
+        GATOR_TRY(ws.vcp16.alloc(upsample_bf16_vcp_elems(B) * 2));
+        ws.vcp16_cap = B;
     }
-    return GATOR_OK;
-}
-
-static int fused_upsample_bf16_in(gator_ctx* c, const float* vert431, int B, float* verts, void* stream) {
-    int rc = fused_ensure_ws(c, B);
-    if (rc == GATOR_OK) rc = ensure_bf16(c, B, stream);
-    if (rc) return rc;
     StageTimer tm(c, "upsample_bf16", stream);
-    return launch_upsample_bf16(c->fused, c, vert431, B, verts, stream);
+    return launch_upsample_bf16(f, c, ws, vert431, B, verts, stream);
 }
 
 int fused_upsample_bf16(gator_ctx* c, const float* vert431, int B, float* verts, void* stream) {
-    WsScope ws(c->fused, 0);
-    return fused_upsample_bf16_in(c, vert431, B, verts, stream);
+    return fused_upsample_bf16_in(c, c->fused->sets[0], vert431, B, verts, stream);
 }
 
-static int fused_mdr_forward_impl(gator_ctx* c, const float* pc, int B, float* verts, void* stream, bool bf16) {
-    int rc = fused_ensure_ws(c, B);
-    if (rc) return rc;
-    FusedState* f = c->fused;
-    rc = launch_mdr(c, f, pc, B, stream, nullptr, nullptr, bf16 && f->opt.c3_mdr);        // also writes the packed vertex-GEMM operand f->ws->vcp / f->ws->vcp3
-    if (rc) return rc;
-    if (bf16 && f->opt.c3_up_bf16) return fused_upsample_bf16_in(c, f->ws->vc, B, verts, stream);
+// The vertex regressor of a forward, in the form its plan names, on the coarse vertices launch_mdr left in ws
+static int fused_regress(gator_ctx* c, FusedWs& ws, const RegressorPlan& r, int B, float* verts, void* stream) {
+    if (r.form == Regressor::BF16) return fused_upsample_bf16_in(c, ws, ws.vc, B, verts, stream);
     StageTimer tm(c, "upsample", stream);
-    return launch_upsample_any(f, c, B, verts, stream);
+    return launch_upsample_any(c->fused, c, ws, r, B, verts, stream);
 }
 
 int fused_mdr_forward(gator_ctx* c, const float* pc, int B, float* verts, void* stream) {
-    WsScope ws(c->fused, 0);
-    return fused_mdr_forward_impl(c, pc, B, verts, stream, false);
+    FusedWs& ws = c->fused->sets[0];
+    ForwardPlan p;
+    GATOR_TRY(fused_plan(c, B, PlanEntry::MDR, false, false, &p));
+    GATOR_TRY(fused_ensure_ws(c, ws, B));
+    GATOR_TRY(launch_mdr(c, c->fused, ws, p, pc, B, stream, nullptr, nullptr));        // also writes the packed vertex-GEMM operand ws.vcp / ws.vcp3
+    return fused_regress(c, ws, p.up, B, verts, stream);
 }
 
-static int fused_forward_one(gator_ctx* c, const float* pose2d, int B, float* verts, float* pose3d, void* stream, bool bf16, float* joints = nullptr);
+static int fused_forward_one(gator_ctx* c, FusedWs& ws, const ForwardPlan& p, const float* pose2d, int B, float* verts, float* pose3d, void* stream, float* joints);
 
 int fused_set_graph_replay(gator_ctx* c, int on) {
     FusedState* f = c->fused;
@@ -573,14 +561,14 @@ int fused_set_graph_replay(gator_ctx* c, int on) {
     return (int)std::min<unsigned long long>(f->graph_launches, 0x7fffffffull);
 }
 
-// The forward of fused_forward_one replayed from a hipGraph (see FusedState::GraphSlot).  Runs inside a WsScope.
-static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* verts, float* pose3d, void* stream, bool bf16) {
+// The forward of fused_forward_one replayed from a hipGraph (see FusedState::GraphSlot)
+static int fused_forward_graph(gator_ctx* c, FusedWs& ws, const ForwardPlan& p, const float* pose2d, int B, float* verts, float* pose3d, void* stream) {
     FusedState* f = c->fused;
-    int rc = fused_ensure_ws(c, B);                      // may reallocate: before the key is formed, never inside a capture
+    int rc = fused_ensure_ws(c, ws, B);                  // may reallocate: before the key is formed, never inside a capture
     if (rc) return rc;
     FusedState::GraphSlot* slot = nullptr;
     for (auto& g : f->graphs)
-        if (g.B == B && g.in == pose2d && g.verts == verts && g.pose3d == pose3d && g.bf16 == bf16 && g.tiled == f->gat_tiled && g.persist == f->opt.mdr_persist && g.ws == f->ws->base.get()) { slot = &g; break; }
+        if (g.B == B && g.in == pose2d && g.verts == verts && g.pose3d == pose3d && g.ws == ws.base.get() && g.plan == p) { slot = &g; break; }
     if (!slot) {                                         // first sight: remember the key, run directly
         if ((int)f->graphs.size() >= FusedState::kGraphSlots) {
             // evict a key that was never captured if there is one (no replay can be in flight: no device-wide wait), else the least recently used
@@ -591,10 +579,10 @@ static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* 
             f->graphs.erase(lru);
         }
         FusedState::GraphSlot g;
-        g.B = B; g.in = pose2d; g.verts = verts; g.pose3d = pose3d; g.bf16 = bf16; g.tiled = f->gat_tiled; g.persist = f->opt.mdr_persist; g.ws = f->ws->base.get();
+        g.B = B; g.in = pose2d; g.verts = verts; g.pose3d = pose3d; g.plan = p; g.ws = ws.base.get();
         g.used = ++f->graph_clock;
         f->graphs.push_back(g);
-        return fused_forward_one(c, pose2d, B, verts, pose3d, stream, bf16);
+        return fused_forward_one(c, ws, p, pose2d, B, verts, pose3d, stream, nullptr);
     }
     slot->used = ++f->graph_clock;
     if (!slot->exec) {                                   // second sight: capture on the private stream
@@ -608,7 +596,7 @@ static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* 
         hipGraphExec_t ex = nullptr;
         bool ok = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) == hipSuccess;
         if (ok) {
-            rc = fused_forward_one(c, pose2d, B, verts, pose3d, cs, bf16);
+            rc = fused_forward_one(c, ws, p, pose2d, B, verts, pose3d, cs, nullptr);
             ok = hipStreamEndCapture(cs, &g) == hipSuccess && rc == GATOR_OK && g != nullptr;
             if (ok) ok = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess;
         }
@@ -618,14 +606,14 @@ static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* 
             if (g) (void)hipGraphDestroy(g);
             f->graph_replay = false;
             if (rc) return rc;
-            return fused_forward_one(c, pose2d, B, verts, pose3d, stream, bf16);
+            return fused_forward_one(c, ws, p, pose2d, B, verts, pose3d, stream, nullptr);
         }
         slot->graph = g; slot->exec = ex;
     }
     GATOR_HIP_CHECK(hipGraphLaunch((hipGraphExec_t)slot->exec, (hipStream_t)stream));
     ++f->graph_launches;
-    c->set_tap(TAP_FEAT, f->ws->feat, (int64_t)B * c->J * kC);      // the same taps a direct forward leaves (launch_mdr sets vert431 only while it runs)
-    c->set_tap(TAP_VERT431, f->ws->vc, (int64_t)B * kV * 3);
+    c->set_tap(TAP_FEAT, ws.feat, (int64_t)B * c->J * kC);      // the same taps a direct forward leaves (launch_mdr sets vert431 only while it runs)
+    c->set_tap(TAP_VERT431, ws.vc, (int64_t)B * kV * 3);
     return GATOR_OK;
 }
 
@@ -636,14 +624,15 @@ static int fused_forward_graph(gator_ctx* c, const float* pose2d, int B, float* 
 int fused_forward(gator_ctx* c, const float* pose2d, int B, float* verts, float* pose3d, void* stream, bool bf16) {
     FusedState* f = c->fused;
     const int want = c->subbatch_streams > 0 ? c->subbatch_streams : f->opt.subbatch_streams;
+    ForwardPlan p;
     if (want < 2 || B < 128) {
-        WsScope ws(f, 0);
+        GATOR_TRY(fused_plan(c, B, PlanEntry::FORWARD, bf16, false, &p));
         if (f->graph_replay && !c->profiling && !c->block_taps) {
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;      // a caller that is capturing the forward itself gets the plain launches
             if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-            if (cs == hipStreamCaptureStatusNone) return fused_forward_graph(c, pose2d, B, verts, pose3d, stream, bf16);
+            if (cs == hipStreamCaptureStatusNone) return fused_forward_graph(c, f->sets[0], p, pose2d, B, verts, pose3d, stream);
         }
-        return fused_forward_one(c, pose2d, B, verts, pose3d, stream, bf16);
+        return fused_forward_one(c, f->sets[0], p, pose2d, B, verts, pose3d, stream, nullptr);
     }
     if (!f->aux_stream) {
         hipStream_t s2; hipEvent_t e1, e2;
@@ -658,10 +647,10 @@ int fused_forward(gator_ctx* c, const float* pose2d, int B, float* verts, float*
     GATOR_HIP_CHECK(hipStreamWaitEvent((hipStream_t)f->aux_stream, (hipEvent_t)f->ev_fork, 0));
     int rc = GATOR_OK;
     for (int i = 0; i < 2 && rc == GATOR_OK; ++i) {
-        WsScope ws(f, i);
         const int off = i ? B0 : 0, n = i ? B1 : B0;
-        rc = fused_forward_one(c, pose2d + (size_t)off * J * 2, n, verts + (size_t)off * kNV * 3, pose3d + (size_t)off * J * 3,
-                               i ? f->aux_stream : stream, bf16);
+        rc = fused_plan(c, n, PlanEntry::FORWARD, bf16, false, &p);      // each half is a forward of its own
+        if (rc == GATOR_OK) rc = fused_forward_one(c, f->sets[i], p, pose2d + (size_t)off * J * 2, n, verts + (size_t)off * kNV * 3, pose3d + (size_t)off * J * 3,
+                               i ? f->aux_stream : stream, nullptr);
     }
     GATOR_HIP_CHECK(hipEventRecord((hipEvent_t)f->ev_join, (hipStream_t)f->aux_stream));
     GATOR_HIP_CHECK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)f->ev_join, 0));
@@ -669,75 +658,43 @@ int fused_forward(gator_ctx* c, const float* pose2d, int B, float* verts, float*
     return rc;
 }
 
-// How many samples of a batch of B the sample-tiled encoder takes under the ctx's current policy (the rest goes to the
-// one-sample-per-workgroup kernel); also behind gator_encoder_for_batch, so that a caller pinning the encoder asks the library
-// instead of repeating the rule.
-int fused_tiled_samples(const gator_ctx* c, int B, bool unpinned) {
+// gator_encoder_for_batch: under the ctx's own policy (pin = AUTO, whatever gator_set_encoder has pinned); a split batch counts as tiled
+int fused_encoder_for_batch(const gator_ctx* c, int B) {
     const FusedState* f = c->fused;
-    int n_tiled = 0;
-    const int policy = f ? (unpinned ? f->opt.gat_tiled : f->gat_tiled) : 0;
-    if (f && f->opt.gat_x3 && policy != 0) {
-        if (policy == 1) n_tiled = B;
-        else if (B >= f->opt.gat_tiled_min_batch) {
-            const int round = f->n_cu * gat_tiled_samples_per_wg(c->J);
-            n_tiled = (B / round) * round;
-            // the remainder: k_gat8 takes ~0.18 ms per n_cu samples (four partial products), a partial round of the tiled kernel ~0.85 ms
-            if (B - n_tiled > 4 * f->n_cu) n_tiled = B;
-        }
-    }
-    return n_tiled;
+    return f && plan_tiled_samples(f->opt, c->J, f->n_cu, B, f->opt.gat_tiled) > 0 ? GATOR_ENCODER_TILED : GATOR_ENCODER_SAMPLE;
 }
 
-static int fused_forward_one(gator_ctx* c, const float* pose2d, int B, float* verts, float* pose3d, void* stream, bool bf16, float* joints) {
-    int rc = fused_ensure_ws(c, B);
-    if (rc) return rc;
+// One forward as its plan says.  p is the plan of THIS call: of a batch of B, with_joints iff joints is given
+static int fused_forward_one(gator_ctx* c, FusedWs& ws, const ForwardPlan& p, const float* pose2d, int B, float* verts, float* pose3d, void* stream, float* joints) {
+    GATOR_TRY(fused_ensure_ws(c, ws, B));
     FusedState* f = c->fused;
-    // Encoder.  k_gat gives every sample a workgroup (one round of it = one sample per CU); the sample-tiled kernel packs S samples
-    // per workgroup (dense token tiles, weights fetched once per workgroup) and one round of it (n_cu workgroups) costs about as
-    // much as 3.8 rounds of k_gat but covers S = 7 (J=17) or 6 (J=19) times the samples.  So a large batch runs as many FULL
-    // tiled rounds as fit, and the remainder on whichever is cheaper: k_gat if it needs at most 3 rounds, the tiled kernel else.
-    // Within one kernel results are bit-identical whatever the batch; between the two they agree to fp32 rounding noise
-    // (tests/test_gpu_tiled.py), so above the threshold a sample's last bits depend on the batch size and its position in it.
-    // GATOR_GAT_TILED=0 keeps every batch on k_gat (bitwise batch invariance at any size), =1 forces the tiled kernel.
-    // The tail (lifter + MDR joint tokens): k_gat8 runs it for its own samples as its epilogue where the ctx has that form (round 6);
-    // the samples of the sample-tiled kernel, or all of them without it, get the two batched launches of gat_tail.hip.
-    const int n_tiled = fused_tiled_samples(c, B);
-    const bool enc16 = bf16 && f->opt.c3_encoder;      // config 3: both encoders' one-plane forms
-    const bool fused_tail = n_tiled < B && gat8_tail_supported(f, enc16);
+    int rc = GATOR_OK;
     {   // x_out [B,3J] IS pose3d [B,J,3]: the tail writes the caller's buffer and produces the MDR joint K/V
         StageTimer tm(c, "gat", stream);
-        if (n_tiled > 0) rc = launch_gat_tiled(c, f, pose2d, n_tiled, f->ws->feat, stream, B, enc16);
-        if (rc == GATOR_OK && n_tiled < B) {
-            const size_t o = (size_t)n_tiled * c->J;
-            float* tail_jkv = fused_tail ? f->ws->jkv + (size_t)n_tiled * 12 * kTile : nullptr;
-            rc = launch_gat(c, f, pose2d + o * 2, B - n_tiled, pose3d + o * 3, f->ws->feat + o * kC, stream, true, B, n_tiled, enc16, tail_jkv);
+        if (p.n_tiled > 0) rc = launch_gat_tiled(c, f, ws, p, pose2d, B, stream);
+        if (rc == GATOR_OK && p.sample == SampleEncoder::GAT8) rc = launch_gat8(c, f, ws, p, pose2d, B, pose3d, stream);
+        if (rc == GATOR_OK && p.sample == SampleEncoder::GAT) {
+            const size_t o = (size_t)p.n_tiled * c->J;
+            rc = launch_gat(c, f, p.gat, pose2d + o * 2, B - p.n_tiled, pose3d + o * 3, ws.feat + o * kC, stream, B, p.n_tiled);
         }
     }
     if (rc) return rc;
-    const int n_tail = fused_tail ? n_tiled : B;
-    if (n_tail > 0) {   // lifter + MDR joint tokens as two batched launches (gat_tail.hip)
+    if (p.n_tail > 0) {   // lifter + MDR joint tokens as two batched launches (gat_tail.hip)
         StageTimer tm(c, "gat_tail", stream);
-        rc = launch_gat_tail(c, f, pose2d, f->ws->feat, n_tail, pose3d, stream, !fused_tail);
-        if (rc) return rc;
+        GATOR_TRY(launch_gat_tail(c, f, ws, p, pose2d, pose3d, stream));
     }
-    c->set_tap(TAP_FEAT, f->ws->feat, (int64_t)B * c->J * kC);
-    rc = launch_mdr(c, f, nullptr, B, stream, pose3d, pose2d, bf16 && f->opt.c3_mdr);      // pose_combine is never materialised on this path
-    if (rc) return rc;
-    if (joints) {      // vertex GEMM with the joint-regression epilogue (verts may be null: nothing of 82 kB/mesh is stored)
-        if (f->opt.up_x3 == 0 || bf16) return fail(GATOR_EUNSUPPORTED, "gator_forward_joints_f32 needs the split-precision vertex regressor");
-        if (B > f->jr_cap) {
-            if (f->jr_P) GATOR_HIP_CHECK(hipDeviceSynchronize());
-            GATOR_TRY(f->jr_P.alloc((size_t)B * f->jr_nnz * 3 * sizeof(float)));
-            f->jr_cap = B;
-        }
-        { StageTimer tm(c, "upsample", stream); rc = launch_upsample_any(f, c, B, verts, stream, true); }
-        if (rc) return rc;
-        StageTimer tm(c, "jreg_reduce", stream);
-        return launch_jreg_reduce(f, B, joints, stream);
+    c->set_tap(TAP_FEAT, ws.feat, (int64_t)B * c->J * kC);
+    GATOR_TRY(launch_mdr(c, f, ws, p, nullptr, B, stream, pose3d, pose2d));      // pose_combine is never materialised on this path
+    if (!joints) return fused_regress(c, ws, p.up, B, verts, stream);
+    // vertex GEMM with the joint-regression epilogue (verts may be null: nothing of 82 kB/mesh is stored)
+    if (B > f->jr_cap) {
+        if (f->jr_P) GATOR_HIP_CHECK(hipDeviceSynchronize());
+        GATOR_TRY(f->jr_P.alloc((size_t)B * f->jr_nnz * 3 * sizeof(float)));
+        f->jr_cap = B;
     }
-    if (bf16 && f->opt.c3_up_bf16) return fused_upsample_bf16_in(c, f->ws->vc, B, verts, stream);
-    StageTimer tm(c, "upsample", stream);
-    return launch_upsample_any(f, c, B, verts, stream, false, bf16 && f->opt.c3_up_w1);
+    GATOR_TRY(fused_regress(c, ws, p.up, B, verts, stream));
+    StageTimer tm(c, "jreg_reduce", stream);
+    return launch_jreg_reduce(f, B, joints, stream);
 }
 
 // Register a sparse [nj, 6890] joint regressor (COO, host or device pointers are both read through hipMemcpy) for the fused epilogue
@@ -803,9 +760,9 @@ int fused_set_encoder(gator_ctx* c, int mode) {
 int fused_forward_joints(gator_ctx* c, const float* pose2d, int B, float* joints, float* pose3d, float* verts, void* stream) {
     FusedState* f = c->fused;
     if (!f || f->jr_nnz == 0) return fail(GATOR_EINVAL, "gator_forward_joints_f32: call gator_set_joint_regressor first");
-    if (f->opt.up_x3 == 0) return fail(GATOR_EUNSUPPORTED, "gator_forward_joints_f32 needs the split-precision vertex regressor");      // before anything is queued
-    WsScope ws(f, 0);
-    return fused_forward_one(c, pose2d, B, verts, pose3d, stream, false, joints);
+    ForwardPlan p;
+    GATOR_TRY(fused_plan(c, B, PlanEntry::FORWARD, false, true, &p));      // (refuses the fp32-input regressor: before anything is queued)
+    return fused_forward_one(c, f->sets[0], p, pose2d, B, verts, pose3d, stream, joints);
 }
 
 }  // namespace gator

@@ -1,15 +1,14 @@
 // State of the fused path: packed (MFMA-operand-order) weights and the per-batch workspace.
 #pragma once
 #include "internal.h"
+#include "forward_plan.h"
 #include <vector>
 
 namespace gator {
 
-constexpr int kVT = 14;                 // 32-token tiles per sample (431 -> 448)
 constexpr int kOB = 216;                // 32-vertex output blocks of the upsample GEMM (6890 -> 6912)
 constexpr int kCB = 14;                 // 32-wide k blocks over the 431 coarse vertices
 constexpr int kTile = 32 * 32;          // floats in one packed 32x32 tile ([4 g][64 lanes][4])
-constexpr int kMdrCtrChunks = 64;       // persistent MDR launches one forward may be cut into (launch_mdr: chunks of 256 .. 511 samples)
 // words of k_mdr_persist's counters for a forward of B samples: per launch a 32-word header (tickets, error flag) + 4 counts per sample
 __host__ __device__ inline size_t mdr_ctr_words(int B) { return (size_t)32 * kMdrCtrChunks + (size_t)4 * B; }
 
@@ -22,8 +21,8 @@ struct GatBlockPk {                     // packed tiles of one GATBlock
     const float *mc, *mdT, *aoffT, *f1b; // M (channel on lane), diag(A).M (TOKEN on lane), offdiag(A)^T B-operand tile, hop-2 bias term
 };
 
-// Per-sub-batch workspace: one block carved into regions (fused_api.hip: fused_ensure_ws).  FusedState holds two sets and a pointer to the
-// one in use (`f->ws->vf`); fused_forward points it at the second set for the second half-batch when it runs two halves on two streams.
+// Per-sub-batch workspace: one block carved into regions (fused_api.hip: fused_ensure_ws).  FusedState holds two sets; every launcher is
+// handed the one it works on: fused_forward gives half-batch i sets[i] when it runs two halves on two streams, everything else sets[0].
 struct FusedWs {
     DevBuf<float> base;                 // the block (per cap batch); everything below but vcp16 points into it
     int cap = 0;
@@ -38,54 +37,9 @@ struct FusedWs {
     float *feat = nullptr;              // [B][J][128] encoder output
     float* hpart = nullptr;             // [cap][14][64] DOUBLES: the head conv's per-tile partial sums (mdr_fused.hip: head_conv_partial)
     float *lpart = nullptr;             // [MT][J][2][kTile] lifter partial tiles (gat_tail.hip)
-    bool mdr_ctr_clean = false;         // the joint-token kernel queued before launch_mdr has zeroed mdr_ctr for it
-    unsigned* mdr_ctr = nullptr;        // k_mdr_persist: the counter blocks of a forward's launches, mdr_ctr_words(cap) words (mdr_fused.hip: MdrChunkPlan)
+    unsigned* mdr_ctr = nullptr;        // k_mdr_persist: the counter blocks of a forward's launches, mdr_ctr_words(cap) words (forward_plan.h: MdrChunkPlan; ForwardPlan::ctr_zero names the launch that zeroes them)
     DevBuf<void> vcp16;                 // bf16 packed vert431 for the bf16 vertex GEMM (cap-sized)
     int vcp16_cap = 0;
-};
-
-// The fused path's environment switches: read once per ctx, at gator_create (fused_api.hip: read_fused_options), which also applies
-// the rules that combine them and gator_config.arithmetic.  What only the weights or the device can tell (the config-3 guard, the
-// byte-lo round trip, the residual checks of the fp16 x 3 weight images) narrows them later by clearing a flag.  Launchers read
-// FusedState::opt and nothing else.
-struct FusedOptions {
-    // encoder
-    bool gat_x3 = true;                 // GATOR_GAT_X3 (default 1): GAT linears on split-precision bf16 MFMA; =0: fp32-input MFMA (k_gat only)
-    bool gat8 = true;                   // GATOR_GAT8 (default 1): the one-sample-per-workgroup encoder is the two-role kernel k_gat8; =0: k_gat.  Needs gat_x3
-    bool gat8_h4 = true;                // GATOR_GAT8_H4 (default 1): k_gat8's token-wise products on four partial products (x3_common.h); =0: the exact six.  Off under exact arithmetic
-    bool gat8_lobyte = true;            // GATOR_GAT8_LOBYTE (default 1): k_gat8 streams the byte-lo image of its weights (H3B, gat_roles.hip); =0: the three fp16 planes.
-                                        // Needs gat8 and gat8_h4; cleared unless every lo value survives the byte round trip (always, for finite weights)
-    bool gat8_tail = true;              // GATOR_GAT8_TAIL (default 1): k_gat8 runs its samples' lifter and MDR joint tokens as its epilogue (round 6); =0: the two
-                                        // launches of gat_tail.hip.  Needs gat8, gat8_h4 and mdr_x3 = 2; cleared if jf128_h3 cannot hold the joint-feature weights;
-                                        // outside config 3 it also needs gat8_lobyte (gat8_tail_supported)
-    bool gat_tiled_h4 = true;           // GATOR_GAT_TILED_H4 (default 1): the sample-tiled encoder's token-wise products on four partial products; =0: the exact six.  Off under exact arithmetic
-    int gat_tiled = -1;                 // GATOR_GAT_TILED: -1 (default) by batch size (fused_tiled_samples), 0 never the sample-tiled encoder, 1 always; what GATOR_ENCODER_AUTO restores
-    int gat_tiled_min_batch = 1024;     // GATOR_GAT_TILED_MIN_BATCH (default 1024; values <= 0 ignored): smallest batch the by-batch-size policy gives the sample-tiled encoder
-    // MDR layers and vertex regressor
-    int mdr_x3 = 2;                     // GATOR_MDR_X3: 0 fp32-input MFMA; 1 exact bf16 x 3 split everywhere; 2 (default) that + the 431x431 attention on two fp16 planes.  1 under exact arithmetic
-    int up_x3 = 2;                      // GATOR_UPSAMPLE_X3: 0 the fp32-input MFMA vertex regressor; 1 the exact three bf16 planes; 2 (default) two scaled fp16 planes.  1 under exact arithmetic
-    int mdr_persist = -1;               // GATOR_MDR_PERSIST: the four MDR stages as persistent launches (k_mdr_persist): -1 (default) by batch size (launch_mdr), 0 never, 1 always.
-                                        // A persistent launch that did not complete sets it to 0 (fused_disable_persist)
-    int mdr_persist_chunk = 0;          // GATOR_MDR_PERSIST_CHUNK: most samples per persistent launch (0, default: floor(B / 256) launches, ceil(B / 384) in config 3)
-    int mdr_persist_grid = 0;           // GATOR_MDR_PERSIST_GRID: workgroups of the persistent launch (0, default: two per CU; tests: a grid that leaves XCDs without one)
-    bool mdr_head_partials = true;      // GATOR_MDR_HEAD_PARTIALS (default 1): the tiles' head-conv partial sums + k_mdr_head_finish; =0: the whole head in k_mdr_head (A/B)
-    // gator_forward_bf16 (BASELINE config 3): which stages run on ONE 16-bit operand plane
-    bool c3_mdr = true;                 // GATOR_C3_MDR (default 1): the MDR layers on one fp16 activation plane; =0: the fp32 configuration's form.  Needs mdr_x3 = 2; cleared by the guard
-    bool c3_encoder = true;             // GATOR_C3_ENCODER (default 1): the encoder's token-wise products on one fp16 activation plane as well; =0: the fp32 configuration's.
-                                        // Needs gat8 and both encoders' four-product forms; cleared by the guard
-    bool c3_up_w1 = true;               // GATOR_C3_UPSAMPLE_W1 (default 1): the vertex regressor's weights on ONE fp16 plane, coarse vertices on two; =0: weights on two
-    bool c3_up_bf16 = false;            // GATOR_C3_UPSAMPLE_BF16 (default 0): the vertex regressor on one bf16 plane instead of its two fp16 planes.  Set unless up_x3 = 2
-    bool c3_guard = true;               // GATOR_C3_GUARD (default 1): clear c3_mdr and c3_encoder if the weights bound the attention logits above 2^10 (fused_create); =0: never
-    // forward
-    bool graph = false;                 // GATOR_GRAPH (default 0): =1 starts the ctx with hipGraph replay of repeated forwards on (gator_set_graph_replay)
-    int subbatch_streams = 0;           // GATOR_SUBBATCH_STREAMS: 2 runs batches >= 128 as two half-batches on two streams, if gator_config.subbatch_streams is 0 (fused_forward)
-    // diagnostic library only (-DGATOR_DIAG; not read otherwise)
-    int gat8_dbg = 0;                   // GATOR_GAT8_DBG: k_gat8's debug mode (1: the helper waves reduced to their barriers)
-    bool gat_stamps = false;            // GATOR_GAT_STAMPS (set): k_gat / k_gat8 record and print in-kernel cycle stamps
-    int mdr_cut = 0;                    // GATOR_MDR_CUT: bit 0 makes every MDR weight load read its tile 0, bit 1 every K / V load (L2 -> CU traffic probe)
-    bool mdr_stamps = false;            // GATOR_MDR_STAMPS (set): k_mdr_layer<1> records and prints stamps (four launches only)
-    bool mdr_solo = false;              // GATOR_MDR_SOLO (set): the MDR layer launches hold one workgroup per CU (one wave per SIMD)
-    bool mdr_ends = false;              // GATOR_MDR_ENDS (set): the last persistent launch prints when its workgroups started and ended
 };
 
 struct FusedState {
@@ -129,12 +83,12 @@ struct FusedState {
     const float* tok_base = nullptr;    // [14][2][4][64][4]  v431 part of get_verts_feature + bias + pos_v  (T-layout tiles)
     const float* tok_w3 = nullptr;      // [3][64]            pose3d part of get_verts_feature (columns 3..5), row-major [i][ch]
     // hipGraph replay of the full forward (gator_set_graph_replay / GATOR_GRAPH=1).  A forward is identified by (batch, the three
-    // caller pointers, precision, encoder pin, persistent-launch state, workspace): the first time a key is seen the forward runs
+    // caller pointers, its ForwardPlan -- everything that decides the launch sequence --, workspace): the first time a key is seen the forward runs
     // directly (lazy allocations happen there), the second time it is captured on a private stream, from then on one hipGraphLaunch
     // on the caller's stream replaces the six launches.  Keys are kept LRU (kGraphSlots); anything unexpected switches the feature off.
     struct GraphSlot {
-        int B = 0; const void *in = nullptr, *verts = nullptr, *pose3d = nullptr; bool bf16 = false;
-        int tiled = 0, persist = 0; const void* ws = nullptr;
+        int B = 0; const void *in = nullptr, *verts = nullptr, *pose3d = nullptr;
+        ForwardPlan plan; const void* ws = nullptr;
         void *graph = nullptr, *exec = nullptr;
         unsigned long long used = 0;
     };
@@ -145,7 +99,6 @@ struct FusedState {
     unsigned long long graph_clock = 0, graph_launches = 0;
     // sub-batch pipelining (two half-batches on two streams: one half's kernel tails are filled by the other's work)
     FusedWs sets[2];                    // set 0 is the normal workspace, set 1 the second half-batch's
-    FusedWs* ws = &sets[0];             // the set in use (fused_api.hip: WsScope)
     void* aux_stream = nullptr;
     void *ev_fork = nullptr, *ev_join = nullptr;
     const float* jfeat_p = nullptr;     // get_joint_feature.weight packed [2 nb][5 kb]
@@ -157,40 +110,35 @@ struct FusedState {
 // fused_pack.hip
 int fused_pack_linear(const float* W, int64_t wsn, int64_t wsk, int N, int K, float* dst, void* stream);   // -> [NB][KB] tiles
 inline int nblk32(int n) { return (n + 31) / 32; }
+// The launchers execute their part of a ForwardPlan (forward_plan.h) on the workspace set they are handed; none reads a switch to choose a kernel.
 // upsample_fused.hip
 int launch_pack_vc(const float* vc, int B, float* vcp, void* stream);
-int launch_upsample(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream);
+int launch_upsample(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream);
 // gat_fused.hip
 int gat_prepare_device();
 int gat_ensure_blk_tap(gator_ctx* c, FusedState* f, int B);
-// split_tail (the full forward): the lifter and the MDR joint tokens are left to gat_tail.hip's batched launches, or to k_gat8's
-// epilogue for its samples (tail_jkv); false (gator_gat_forward_f32): k_gat runs the lifter itself
-int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x_out, float* feat, void* stream, bool split_tail = false,
-               int B_total = 0, int tap_row0 = 0, bool half16 = false, float* tail_jkv = nullptr);      // half16: the one-plane form of the two-role kernel (config 3); other forms ignore it
+int launch_gat(gator_ctx* c, FusedState* f, const GatForm& form, const float* pose2d, int B, float* x_out, float* feat, void* stream, int B_total, int tap_row0);      // B samples: rows tap_row0 .. of a batch of B_total
 // gat_roles.hip
 int gat8_prepare_device();
 int gat8_build_stream(FusedState* f, void* stream);
-int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* feat, void* stream, int B_total = 0, int tap_row0 = 0, bool half16 = false,
-                float* tail_x_out = nullptr, float* tail_jkv = nullptr, int ctr_B = 0);
-bool gat8_tail_supported(const FusedState* f, bool half16);
+int launch_gat8(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pose2d, int B, float* pose3d, void* stream);      // k_gat8<p.gat8> on samples p.n_tiled .. B of the whole batch's pose2d / pose3d
 // gat_tiled.hip
 int gat_tiled_prepare_device();
-int gat_tiled_samples_per_wg(int J);
-int launch_gat_tiled(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* feat, void* stream, int B_total = 0, bool half16 = false);
+int launch_gat_tiled(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pose2d, int B, void* stream);      // k_gat_tiled<p.tiled> on samples 0 .. p.n_tiled
 // gat_tail.hip
 size_t gat_tail_part_floats(int B, int J);
-int launch_gat_tail(gator_ctx* c, FusedState* f, const float* pose2d, const float* feat, int B, float* x_out, void* stream, bool zero_ctr = true);
+int launch_gat_tail(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pose2d, float* x_out, void* stream);  // lifter + MDR joint tokens of samples 0 .. p.n_tail
 // upsample_bf16.hip
 size_t upsample_bf16_weight_elems();
 size_t upsample_bf16_vcp_elems(int B);
 int pack_upsample_bf16(const float* up_w, void* dst, void* stream);
-int launch_upsample_bf16(const FusedState* f, const gator_ctx* c, const float* vc, int B, float* verts, void* stream);
+int launch_upsample_bf16(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const float* vc, int B, float* verts, void* stream);
 // upsample_x3.hip
 size_t upsample_x3_weight_elems();
 size_t upsample_x3_vcp_elems(int B);
 int pack_upsample_x3(const float* up_w, void* dst, void* stream);
 int launch_pack_vc_x3(const float* vc, int B, int cap, void* vcp3, void* stream);
-int launch_upsample_x3(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints = false);
+int launch_upsample_x3(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream, bool with_joints);
 int launch_jreg_reduce(const FusedState* f, int B, float* joints, void* stream);
 // upsample_x2.hip
 size_t upsample_x2_weight_elems();
@@ -198,10 +146,9 @@ size_t upsample_x2_vcp_elems(int B);
 int upsample_x2_prepare_device();
 int pack_upsample_x2(const float* up_w, void* dst, float* unscale, void* stream);
 int launch_pack_vc_x2(const float* vc, int B, void* vcp2, void* stream);
-int launch_upsample_x2(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints = false, bool w1 = false);
-// the vertex regressor the ctx was created with (fp32-input MFMA | bf16 x 3 | fp16 x 2)
-int launch_upsample_any(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints = false, bool w1 = false);
-// mdr_fused.hip
-int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream, const float* x_out = nullptr, const float* pose2d = nullptr, bool half16 = false);
+int launch_upsample_x2(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream, bool with_joints, bool w1);
+int launch_upsample_any(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const RegressorPlan& r, int B, float* verts, void* stream);      // fp32-input MFMA | bf16 x 3 | fp16 x 2 (the bf16 kernel: fused_api.hip)
+// mdr_fused.hip: the joint tokens (pc, the MDR entry point; else x_out and pose2d of the whole forward), the layers and the head, as p says
+int launch_mdr(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pc, int B, void* stream, const float* x_out, const float* pose2d);
 
 }  // namespace gator

@@ -568,13 +568,17 @@ __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
 constexpr size_t kGatLds = (20 * kTile + 2048) * sizeof(float);                   // 88 KB
 constexpr size_t kGatLdsX3 = (kGatLdsFloatsX3 + 1024) * sizeof(float);            // 120 KB + the 4 KB landing window of the L2 warm-up
 
+// The four forms of k_gat with their dynamic LDS, named once: the opt-in and the launch both read this table
+using GatKernel = void (*)(const GatArgs);
+const struct { GatForm form; GatKernel kernel; size_t lds; } kGatKernels[] = {
+    {{false, true}, k_gat<false, true>, kGatLds}, {{true, true}, k_gat<true, true>, kGatLdsX3},
+    {{false, false}, k_gat<false, false>, kGatLds}, {{true, false}, k_gat<true, false>, kGatLdsX3}};
+
 // Dynamic-LDS opt-in of the kernels, per DEVICE: called from fused_create_gat with the ctx's device current (a function
 // attribute set on one device does not carry to another, and a process may hold contexts on several).
 int gat_prepare_device() {
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGatLds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGatLdsX3));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGatLds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGatLdsX3));
+    for (const auto& e : kGatKernels)
+        GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)e.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.lds));
     return GATOR_OK;
 }
 
@@ -589,9 +593,12 @@ int gat_ensure_blk_tap(gator_ctx* c, FusedState* f, int B) {
     return GATOR_OK;
 }
 
-int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x_out, float* feat, void* stream, bool split_tail,
-               int B_total, int tap_row0, bool half16, float* tail_jkv) {
-    const bool x3 = f->opt.gat_x3;
+int launch_gat(gator_ctx* c, FusedState* f, const GatForm& form, const float* pose2d, int B, float* x_out, float* feat, void* stream, int B_total, int tap_row0) {
+    GatKernel kernel = nullptr;
+    for (const auto& e : kGatKernels)
+        if (e.form == form) kernel = e.kernel;
+    if (!kernel) return fail(GATOR_EINVAL, "k_gat: no such form");
+    const bool x3 = form.x3k;
     GatArgs a;
     const Weights& w = c->w;
     a.J = c->J; a.pose2d = pose2d;
@@ -618,12 +625,9 @@ int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x
     }
     a.blk_tap = nullptr;
     a.tapB = B;
-    if (c->block_taps) {
-        const int Bt = B_total > 0 ? B_total : B;
-        int rc = gat_ensure_blk_tap(c, f, Bt);
-        if (rc) return rc;
-        a.blk_tap = f->blk_tap + (size_t)tap_row0 * c->J * kC;      // this launch's samples start at row tap_row0 of the batch
-        a.tapB = Bt;
+    if (c->block_taps) {      // this launch's samples start at row tap_row0 of the batch
+        GATOR_TRY(gat_ensure_blk_tap(c, f, B_total));
+        a.blk_tap = f->blk_tap + (size_t)tap_row0 * c->J * kC; a.tapB = B_total;
     }
 #ifdef GATOR_DIAG
     a.stamps = nullptr;
@@ -633,22 +637,8 @@ int launch_gat(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* x
         a.stamps = d_st.get();
     }
 #endif
-    if (split_tail && f->opt.gat8) {                                                      // the two-role form (gat_roles.hip)
-#ifdef GATOR_DIAG
-        d_st.reset();                                                                     // (it prints its own stamps)
-#endif
-        // tail_jkv: k_gat8 runs the lifter + joint tokens of ITS samples as its epilogue (and zeroes the MDR counters of the whole forward)
-        return launch_gat8(c, f, pose2d, B, feat, stream, B_total, tap_row0, half16, tail_jkv ? x_out : nullptr, tail_jkv, tail_jkv ? (B_total > 0 ? B_total : B) : 0);
-    }
-    if (split_tail) {
-        if (x3) k_gat<true, false><<<B, 256, kGatLdsX3, (hipStream_t)stream>>>(a);
-        else k_gat<false, false><<<B, 256, kGatLds, (hipStream_t)stream>>>(a);
-    } else {
-        if (x3) k_gat<true, true><<<B, 256, kGatLdsX3, (hipStream_t)stream>>>(a);
-        else k_gat<false, true><<<B, 256, kGatLds, (hipStream_t)stream>>>(a);
-    }
+    kernel<<<B, 256, x3 ? kGatLdsX3 : kGatLds, (hipStream_t)stream>>>(a);
     GATOR_HIP_CHECK(hipGetLastError());
-
 #ifdef GATOR_DIAG
     if (d_st) {     // diagnostic build: synchronous read-back
         unsigned long long hst[20];

@@ -1417,18 +1417,18 @@ __global__ void k_h3_to_h3b(const float* __restrict__ src, float* __restrict__ d
 
 constexpr size_t kGat8Lds = (size_t)(kGat8LdsFloats + kDiagLdsFloats) * sizeof(float);
 
+// The eleven forms of k_gat8, named once: the dynamic-LDS opt-in and the launch both read this table
+using Gat8Kernel = void (*)(const Gat8Args);
+const struct { Gat8Form form; Gat8Kernel kernel; } kGat8Kernels[] = {
+    {{false, 16, false, false, false}, k_gat8<false, 16>}, {{true, 10, false, false, false}, k_gat8<true, 10>}, {{true, 12, false, false, false}, k_gat8<true, 12>},
+    {{true, 10, true, false, false}, k_gat8<true, 10, true>}, {{true, 12, true, false, false}, k_gat8<true, 12, true>},
+    {{true, 10, false, true, false}, k_gat8<true, 10, false, true>}, {{true, 12, false, true, false}, k_gat8<true, 12, false, true>},
+    {{true, 10, true, false, true}, k_gat8<true, 10, true, false, true>}, {{true, 12, true, false, true}, k_gat8<true, 12, true, false, true>},
+    {{true, 10, false, true, true}, k_gat8<true, 10, false, true, true>}, {{true, 12, false, true, true}, k_gat8<true, 12, false, true, true>}};
+
 int gat8_prepare_device() {
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<true, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<true, 12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<true, 10, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<true, 12, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<true, 10, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<true, 12, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<true, 10, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<true, 12, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<true, 10, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat8<true, 12, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
+    for (const auto& e : kGat8Kernels)
+        GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)e.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGat8Lds));
     return GATOR_OK;
 }
 
@@ -1493,99 +1493,32 @@ int gat8_build_stream(FusedState* f, void* stream) {
     return GATOR_OK;
 }
 
-// feat only (the lifter and the MDR joint tokens are the batched launches of gat_tail.hip)
-// tail_x_out != nullptr: the lifter (-> tail_x_out [B][3J]) and, with tail_jkv, the MDR joint tokens / K / V tiles run as the kernel's epilogue
-// (gat8_tail_supported); ctr_B > 0: the kernel also zeroes the persistent MDR launch's counters of a forward of ctr_B samples
-bool gat8_tail_supported(const FusedState* f, bool half16) {
-    // (the three-plane stream's kernel has no registers left for the epilogue: outside config 3, GATOR_GAT8_LOBYTE=0 keeps the two launches)
-    return f->opt.gat8_tail && (half16 || f->opt.gat8_lobyte);
-}
-
-int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* feat, void* stream, int B_total, int tap_row0, bool half16,
-                float* tail_x_out, float* tail_jkv, int ctr_B) {
-    if (tail_x_out && !gat8_tail_supported(f, half16)) return fail(GATOR_EUNSUPPORTED, "k_gat8: the fused tail needs the four-product forms and 17 or 19 joints");
-    if (half16 && !f->opt.gat8_h4) return fail(GATOR_EUNSUPPORTED, "the 16-bit encoder needs the four-product weight stream (GATOR_GAT8_H4=1, the default)");
-    Gat8Args a;
-    const Weights& w = c->w;
-    a.B = B; a.J = c->J; a.pose2d = pose2d;
-    a.gl0_W = w.gl0_W; a.gl0_b = w.gl0_b; a.gn_w = w.gn_w; a.gn_b = w.gn_b; a.gl3_p = f->g_gl3; a.gl3_b = w.gl3_b; a.posT = f->g_posT;
-    a.biasT = f->g_biasT; a.m1T = f->g_m1T; a.m2T = f->g_m2T;
-    a.norm_w = w.norm_w; a.norm_b = w.norm_b;
-    a.wstream = f->g8stream;
-    for (int i = 0; i < kDepth; ++i) {
-        const GatBlockPk& p = f->gblk[i];
-        a.blk[i] = Gat8Blk{p.back, p.mc, p.mdT, p.aoffT, p.f1b, f->g_vecs + (size_t)i * 2048};
-    }
-    a.feat = feat;
-    a.tl = Gat8Tail{};
-    const bool tail = tail_x_out != nullptr;
-    if (tail) {
-        Gat8Tail& tl = a.tl;
-        tl.lifter_w = w.lifter_w; tl.lifter_b = w.lifter_b; tl.x_out = tail_x_out; tl.jkv = tail_jkv;
-        if (ctr_B > 0 && f->opt.mdr_persist != 0) { tl.mdr_ctr = f->ws->mdr_ctr; tl.ctr_B = ctr_B; f->ws->mdr_ctr_clean = true; }
-        tl.jf5 = f->jfeat5; tl.jf_h3 = f->jf128_h3; tl.jf_b = w.jfeat_b; tl.posj_T = f->posj_T;
-        auto h3_of = [&](const float* t) { return f->wxbuf + (size_t)(t - f->lay[0].wq) / kTile * kTileX3; };      // the MDR layers' H3 image mirrors wbuf tile for tile
-        for (int i = 0; i < 3; ++i) { tl.j_n1w[i] = w.lay[i].n1w; tl.j_n1b[i] = w.lay[i].n1b; tl.j_wk_h3[i] = h3_of(f->lay[i].wk); tl.j_wv_h3[i] = h3_of(f->lay[i].wv); }
-        tl.jf_inv = std::ldexp(1.0f, -(4 + f->jf128_wshift));
-        tl.kv_inv = std::ldexp(1.0f, -(4 + f->mdr_wshift));
-    }
-    a.blk_tap = nullptr;
-    a.tapB = B;
-    if (c->block_taps) {
-        const int Bt = B_total > 0 ? B_total : B;
-        int rc = gat_ensure_blk_tap(c, f, Bt);
-        if (rc) return rc;
-        a.blk_tap = f->blk_tap + (size_t)tap_row0 * c->J * kC;
-        a.tapB = Bt;
-    }
-    // L2 warm-up: each workgroup touches its share of the next block's weight stream
-    a.pf_n = std::min(32, (B + 7) / 8);                  // workgroups b and b + 8 share an XCD (round-robin dispatch; speed only)
-    const bool lob = f->opt.gat8_lobyte && !half16;                                   // the byte-lo stream (the one-plane form reads hi and mid of the H3 stream)
-    if (lob) a.wstream = f->g8stream_b;
-    a.pf_loads = (kBlkTiles * (lob ? kTileH3B : kTileX3) * 4 / a.pf_n + 8191) / 8192;       // 8 KiB (64 lines) per instruction
-    if (a.pf_loads > 6) a.pf_loads = 0;      // fewer than ~8 workgroups per XCD (B < 64): a share is so large that touching it costs more than it hides
-    a.tl.warm_n = (tail && a.pf_n >= 8) ? a.pf_n : 0;      // (fewer than 8 workgroups per XCD: a share is too large to be worth touching)
 #ifdef GATOR_DIAG
+// GATOR_GAT_STAMPS: the stamp buffers of one launch, zeroed before it, read back (synchronously) and printed behind it
+constexpr int kGat8Stamps = 2 * kDepth * 23 * 2 + kDepth * 8;
+struct Gat8Diag { DevBuf<unsigned long long> stamps, tstamps; };
+
+static int gat8_diag_setup(const FusedState* f, bool tail, Gat8Args& a, Gat8Diag& d) {
     a.stamps = nullptr;
     a.dbg = f->opt.gat8_dbg;
-    const bool want_stamps = f->opt.gat_stamps;
-    constexpr int kSt = 2 * kDepth * 23 * 2 + kDepth * 8;
-    DevBuf<unsigned long long> d_stamps, d_tstamps;
-    if (want_stamps) {
-        GATOR_TRY(d_stamps.alloc(kSt * sizeof(unsigned long long)));
-        a.stamps = d_stamps.get();
-        GATOR_HIP_CHECK(hipMemset(a.stamps, 0, kSt * sizeof(unsigned long long)));
-    }
-#endif
-#ifdef GATOR_DIAG
     a.tl.tstamps = nullptr;
-    if (want_stamps && tail) {
-        GATOR_TRY(d_tstamps.alloc(64 * sizeof(unsigned long long)));
-        a.tl.tstamps = d_tstamps.get();
+    if (!f->opt.gat_stamps) return GATOR_OK;
+    GATOR_TRY(d.stamps.alloc(kGat8Stamps * sizeof(unsigned long long)));
+    a.stamps = d.stamps.get();
+    GATOR_HIP_CHECK(hipMemset(a.stamps, 0, kGat8Stamps * sizeof(unsigned long long)));
+    if (tail) {
+        GATOR_TRY(d.tstamps.alloc(64 * sizeof(unsigned long long)));
+        a.tl.tstamps = d.tstamps.get();
         GATOR_HIP_CHECK(hipMemset(a.tl.tstamps, 0, 64 * sizeof(unsigned long long)));
     }
-#endif
-    a.lin_inv = std::ldexp(1.0f, -(4 + f->gat8_wshift));
-    // token rows that exist sit in registers r < LR of a row-over-token tile: token t <-> r = (t & 3) + 4 (t >> 3), so J <= 18 / 20 -> 10 / 12
-    if (tail && half16 && c->J == 17) k_gat8<true, 10, true, false, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else if (tail && half16) k_gat8<true, 12, true, false, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else if (tail && lob && c->J == 17) k_gat8<true, 10, false, true, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else if (tail && lob) k_gat8<true, 12, false, true, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else if (tail) return fail(GATOR_EUNSUPPORTED, "k_gat8: no fused tail on the three-plane weight stream");
-    else if (!f->opt.gat8_h4) k_gat8<false, 16><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else if (half16 && c->J <= 18) k_gat8<true, 10, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else if (half16 && c->J <= 20) k_gat8<true, 12, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else if (lob && c->J <= 18) k_gat8<true, 10, false, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else if (lob && c->J <= 20) k_gat8<true, 12, false, true><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else if (c->J <= 18) k_gat8<true, 10><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else if (c->J <= 20) k_gat8<true, 12><<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
-    else return fail(GATOR_EUNSUPPORTED, "k_gat8: more than 20 joints (gator_create admits 17 and 19)");
-    GATOR_HIP_CHECK(hipGetLastError());
-#ifdef GATOR_DIAG
-    if (a.tl.tstamps) {
+    return GATOR_OK;
+}
+
+static int gat8_diag_report(Gat8Diag& d, int B) {
+    if (d.tstamps) {
         unsigned long long ts[64];
-        GATOR_HIP_CHECK(hipMemcpy(ts, a.tl.tstamps, sizeof(ts), hipMemcpyDeviceToHost));
-        d_tstamps.reset();
+        GATOR_HIP_CHECK(hipMemcpy(ts, d.tstamps, sizeof(ts), hipMemcpyDeviceToHost));
+        d.tstamps.reset();
         fprintf(stderr, "[k_gat8 tail stamps, one workgroup, B=%d] s_memtime cycles since wave 0 entered: entry | loads issued + joint-token MFMAs | lifter done | at barrier | past barrier | jf + LN done | job 1 | job 2\n", B);
         for (int v = 0; v < 8; ++v) {
             fprintf(stderr, "  wave %d:", v);
@@ -1593,10 +1526,10 @@ int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* 
             fprintf(stderr, "\n");
         }
     }
-    if (a.stamps) {     // diagnostic build: synchronous read-back; blocks 1..5 averaged (block 0 carries the cold start)
-        std::vector<unsigned long long> hs(kSt);
-        GATOR_HIP_CHECK(hipMemcpy(hs.data(), a.stamps, kSt * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        d_stamps.reset();
+    if (d.stamps) {     // blocks 1..5 averaged (block 0 carries the cold start)
+        std::vector<unsigned long long> hs(kGat8Stamps);
+        GATOR_HIP_CHECK(hipMemcpy(hs.data(), d.stamps, kGat8Stamps * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        d.stamps.reset();
         double tot[2] = {0, 0};
         fprintf(stderr, "[k_gat8 stamps, wg0, B=%d] cycles per step, mean of blocks 1-5: step | product work wait | helper work wait\n", B);
         for (int n = 0; n < 23; ++n) {
@@ -1612,6 +1545,61 @@ int launch_gat8(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* 
         for (int k = 0; k < 8; ++k) fprintf(stderr, " %llu", hs[(size_t)2 * kDepth * 23 * 2 + 1 * 8 + k]);
         fprintf(stderr, "\n");
     }
+    return GATOR_OK;
+}
+#endif
+
+int launch_gat8(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pose2d, int B_total, float* pose3d, void* stream) {
+    Gat8Kernel kernel = nullptr;
+    for (const auto& e : kGat8Kernels)
+        if (e.form == p.gat8) kernel = e.kernel;
+    if (!kernel) return fail(GATOR_EINVAL, "k_gat8: no such form");
+    const int row0 = p.n_tiled, B = B_total - row0;      // this launch's samples start at row row0 of the batch
+    const size_t o = (size_t)row0 * c->J;
+    Gat8Args a;
+    const Weights& w = c->w;
+    a.B = B; a.J = c->J; a.pose2d = pose2d + o * 2;
+    a.gl0_W = w.gl0_W; a.gl0_b = w.gl0_b; a.gn_w = w.gn_w; a.gn_b = w.gn_b; a.gl3_p = f->g_gl3; a.gl3_b = w.gl3_b; a.posT = f->g_posT;
+    a.biasT = f->g_biasT; a.m1T = f->g_m1T; a.m2T = f->g_m2T;
+    a.norm_w = w.norm_w; a.norm_b = w.norm_b;
+    a.wstream = p.gat8.lb ? f->g8stream_b.get() : f->g8stream.get();      // the byte-lo stream, or the H3 stream (the one-plane form reads its hi and mid)
+    for (int i = 0; i < kDepth; ++i) {
+        const GatBlockPk& b = f->gblk[i];
+        a.blk[i] = Gat8Blk{b.back, b.mc, b.mdT, b.aoffT, b.f1b, f->g_vecs + (size_t)i * 2048};
+    }
+    a.feat = ws.feat + o * kC;
+    a.tl = Gat8Tail{};
+    const bool tail = p.gat8.tail;
+    if (tail) {      // the lifter (x_out [B,3J] IS pose3d [B,J,3]) and the MDR joint tokens / K / V tiles of ITS samples as the kernel's epilogue
+        Gat8Tail& tl = a.tl;
+        tl.lifter_w = w.lifter_w; tl.lifter_b = w.lifter_b; tl.x_out = pose3d + o * 3; tl.jkv = ws.jkv + (size_t)row0 * 12 * kTile;
+        if (p.ctr_zero == CtrZero::GAT8_TAIL) { tl.mdr_ctr = ws.mdr_ctr; tl.ctr_B = B_total; }      // ... and the zeroing of the whole forward's MDR counters
+        tl.jf5 = f->jfeat5; tl.jf_h3 = f->jf128_h3; tl.jf_b = w.jfeat_b; tl.posj_T = f->posj_T;
+        auto h3_of = [&](const float* t) { return f->wxbuf + (size_t)(t - f->lay[0].wq) / kTile * kTileX3; };      // the MDR layers' H3 image mirrors wbuf tile for tile
+        for (int i = 0; i < 3; ++i) { tl.j_n1w[i] = w.lay[i].n1w; tl.j_n1b[i] = w.lay[i].n1b; tl.j_wk_h3[i] = h3_of(f->lay[i].wk); tl.j_wv_h3[i] = h3_of(f->lay[i].wv); }
+        tl.jf_inv = std::ldexp(1.0f, -(4 + f->jf128_wshift));
+        tl.kv_inv = std::ldexp(1.0f, -(4 + f->mdr_wshift));
+    }
+    a.blk_tap = nullptr;
+    a.tapB = B;
+    if (c->block_taps) {
+        GATOR_TRY(gat_ensure_blk_tap(c, f, B_total));
+        a.blk_tap = f->blk_tap + (size_t)row0 * c->J * kC; a.tapB = B_total;
+    }
+    // L2 warm-up: each workgroup touches its share of the next block's weight stream
+    a.pf_n = std::min(32, (B + 7) / 8);                  // workgroups b and b + 8 share an XCD (round-robin dispatch; speed only)
+    a.pf_loads = (kBlkTiles * (p.gat8.lb ? kTileH3B : kTileX3) * 4 / a.pf_n + 8191) / 8192;       // 8 KiB (64 lines) per instruction
+    if (a.pf_loads > 6) a.pf_loads = 0;      // fewer than ~8 workgroups per XCD (B < 64): a share is so large that touching it costs more than it hides
+    a.tl.warm_n = (tail && a.pf_n >= 8) ? a.pf_n : 0;      // (fewer than 8 workgroups per XCD: a share is too large to be worth touching)
+    a.lin_inv = std::ldexp(1.0f, -(4 + f->gat8_wshift));
+#ifdef GATOR_DIAG
+    Gat8Diag diag;
+    GATOR_TRY(gat8_diag_setup(f, tail, a, diag));
+#endif
+    kernel<<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
+    GATOR_HIP_CHECK(hipGetLastError());
+#ifdef GATOR_DIAG
+    GATOR_TRY(gat8_diag_report(diag, B));
 #endif
     return GATOR_OK;
 }

@@ -174,18 +174,17 @@ __global__ __launch_bounds__(256) void k_gat_joint(const JointTailArgs a) {
 
 size_t gat_tail_part_floats(int B, int J) { return (size_t)((B + 31) / 32) * J * 2 * kTile; }
 
-int launch_gat_tail(gator_ctx* c, FusedState* f, const float* pose2d, const float* feat, int B, float* x_out, void* stream, bool zero_ctr) {
+int launch_gat_tail(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pose2d, float* x_out, void* stream) {
     const Weights& w = c->w;
-    const int J = c->J, MT = (B + 31) / 32;
+    const int B = p.n_tail, J = c->J, MT = (B + 31) / 32;
     hipStream_t st = (hipStream_t)stream;
-    LifterArgs la{feat, w.lifter_w, f->ws->lpart, B, J};
+    LifterArgs la{ws.feat, w.lifter_w, ws.lpart, B, J};
     k_gat_lifter<<<MT * J, 128, 0, st>>>(la);
     JointTailArgs a{};
-    a.pose2d = pose2d; a.feat = feat; a.part = f->ws->lpart; a.lifter_b = w.lifter_b; a.x_out = x_out; a.B = B; a.J = J;
-    a.mdr_ctr = nullptr;
+    a.pose2d = pose2d; a.feat = ws.feat; a.part = ws.lpart; a.lifter_b = w.lifter_b; a.x_out = x_out; a.B = B; a.J = J;
+    a.mdr_ctr = p.ctr_zero == CtrZero::GAT_JOINT ? ws.mdr_ctr : nullptr;      // (with a fused tail k_gat8 zeroes them for the whole forward)
     a.x2 = f->opt.mdr_x3 == 2;
-    if (f->opt.mdr_persist != 0 && zero_ctr) { a.mdr_ctr = f->ws->mdr_ctr; f->ws->mdr_ctr_clean = true; }      // (!zero_ctr: k_gat8's fused tail zeroes them for the whole forward)
-    a.jkv = f->ws->jkv; a.jf5 = f->jfeat5; a.jf_p = f->jfeat128_p; a.jf_b = w.jfeat_b; a.posj_T = f->posj_T;
+    a.jkv = ws.jkv; a.jf5 = f->jfeat5; a.jf_p = f->jfeat128_p; a.jf_b = w.jfeat_b; a.posj_T = f->posj_T;
     for (int i = 0; i < 3; ++i) { a.j_n1w[i] = w.lay[i].n1w; a.j_n1b[i] = w.lay[i].n1b; a.j_wk_p[i] = f->lay[i].wk; a.j_wv_p[i] = f->lay[i].wv; }
     k_gat_joint<<<B, 256, 0, st>>>(a);
     GATOR_HIP_CHECK(hipGetLastError());

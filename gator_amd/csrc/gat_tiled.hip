@@ -27,8 +27,8 @@
 namespace gator {
 namespace {
 
-constexpr int kTW = 4;                 // waves = 32-token tiles per workgroup
-constexpr int kTT = 32 * kTW;          // token slots per workgroup
+constexpr int kTT = kTiledTokens;      // token slots per workgroup (forward_plan.h: the launch policy counts samples per workgroup with it)
+constexpr int kTW = kTT / 32;          // waves = 32-token tiles per workgroup
 constexpr int kEXS = 36;               // row stride (floats) of an exchange image: 16-byte aligned rows, conflict-free b128 access
 constexpr int kTabS = 20;              // row stride of the J x J tables (J <= 19)
 constexpr int kGrpTiles = 4;           // tiles per weight group (ring slot = 4 x 6 KiB = 24 KiB, 6 pieces of 1 KiB per wave)
@@ -583,61 +583,52 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
 
 }  // namespace
 
-int gat_tiled_samples_per_wg(int J) { return kTT / J; }
+// The six forms of k_gat_tiled, named once: the dynamic-LDS opt-in and the launch both read this table
+using TiledKernel = void (*)(const TiledArgs);
+const struct { TiledForm form; TiledKernel kernel; } kTiledKernels[] = {
+    {{17, false, false}, k_gat_tiled<17, false>}, {{19, false, false}, k_gat_tiled<19, false>}, {{17, true, false}, k_gat_tiled<17, true>},
+    {{19, true, false}, k_gat_tiled<19, true>}, {{17, true, true}, k_gat_tiled<17, true, true>}, {{19, true, true}, k_gat_tiled<19, true, true>}};
+constexpr size_t kTiledLds = kTiledLdsFloats * sizeof(float);
 
 int gat_tiled_prepare_device() {
-    const int ldsb = (int)(kTiledLdsFloats * sizeof(float));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat_tiled<17, false>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsb));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat_tiled<19, false>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsb));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat_tiled<17, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsb));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat_tiled<19, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsb));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat_tiled<17, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsb));
-    GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_gat_tiled<19, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsb));
+    for (const auto& e : kTiledKernels)
+        GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)e.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTiledLds));
     return GATOR_OK;
 }
 
-// pose2d [B,J,2] -> feat [B,J,128]; requires the split-precision weight images (FusedState::gxbuf)
-int launch_gat_tiled(gator_ctx* c, FusedState* f, const float* pose2d, int B, float* feat, void* stream, int B_total, bool half16) {
-    if (half16 && !f->opt.gat_tiled_h4) return fail(GATOR_EUNSUPPORTED, "the 16-bit encoder needs the four-product weight image (GATOR_GAT_TILED_H4=1, the default)");
-    if (!f->opt.gat_x3) return fail(GATOR_EUNSUPPORTED, "the sample-tiled GAT kernel needs the split-precision weights (GATOR_GAT_X3=1)");
+// pose2d [B_total,J,2] -> ws.feat [.,J,128] for the forward's first p.n_tiled samples; reads the split-precision weight images (FusedState::gxbuf)
+int launch_gat_tiled(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pose2d, int B_total, void* stream) {
+    TiledKernel kernel = nullptr;
+    for (const auto& e : kTiledKernels)
+        if (e.form == p.tiled) kernel = e.kernel;
+    if (!kernel) return fail(GATOR_EINVAL, "k_gat_tiled: no such form");
     const Weights& w = c->w;
     TiledArgs a;
-    a.B = B; a.Btap = B_total > 0 ? B_total : B; a.S = gat_tiled_samples_per_wg(c->J); a.pose2d = pose2d;
+    a.B = p.n_tiled; a.Btap = B_total; a.S = kTT / c->J; a.pose2d = pose2d;
     a.gl0_W = w.gl0_W; a.gl0_b = w.gl0_b; a.gn_w = w.gn_w; a.gn_b = w.gn_b; a.gl3_p = f->g_gl3; a.gl3_b = w.gl3_b; a.pos = c->pos_embed;
     a.hop_bias = c->hop_bias; a.adj_diag = c->adj_diag; a.adj_off = c->adj_off; a.m1 = c->mask1; a.m2 = c->mask2;
     a.norm_w = w.norm_w; a.norm_b = w.norm_b;
     for (int i = 0; i < kDepth; ++i) {
-        const GatBlockPk& p = f->gblk[i];
+        const GatBlockPk& b = f->gblk[i];
         TiledBlk& q = a.blk[i];
-        const float* image = f->opt.gat_tiled_h4 ? f->gxbuf_h3.get() : f->gxbuf.get();
+        const float* image = p.tiled.h4 ? f->gxbuf_h3.get() : f->gxbuf.get();
         auto sel = [&](const float* t) { return image + (size_t)(t - f->gblk[0].qkv) / kTile * kTileX3; };
-        q.qkv = sel(p.qkv); q.proj = sel(p.proj); q.w0 = sel(p.w0); q.w1 = sel(p.w1); q.lin0 = sel(p.lin0); q.lin1 = sel(p.lin1);
-        q.back = sel(p.back); q.fc1 = sel(p.fc1); q.fc2 = sel(p.fc2);
+        q.qkv = sel(b.qkv); q.proj = sel(b.proj); q.w0 = sel(b.w0); q.w1 = sel(b.w1); q.lin0 = sel(b.lin0); q.lin1 = sel(b.lin1);
+        q.back = sel(b.back); q.fc1 = sel(b.fc1); q.fc2 = sel(b.fc2);
         q.vecs = f->g_vecs + (size_t)i * 2048;
         q.M = w.blk[i].gcn_M;
         q.lin1_b = w.blk[i].xl1_b;
     }
-    a.feat = feat;
+    a.feat = ws.feat;
     a.blk_tap = nullptr;
     if (c->block_taps) {
-        int rc = gat_ensure_blk_tap(c, f, a.Btap);
-        if (rc) return rc;
+        GATOR_TRY(gat_ensure_blk_tap(c, f, a.Btap));
         a.blk_tap = f->blk_tap;
     }
-    const int nwg = (B + a.S - 1) / a.S;
-    const size_t ldsb = kTiledLdsFloats * sizeof(float);
-    a.lin_s = f->opt.gat_tiled_h4 ? std::ldexp(16.0f, f->gat_tiled_wshift) : 1.0f;
+    const int nwg = (a.B + a.S - 1) / a.S;
+    a.lin_s = p.tiled.h4 ? std::ldexp(16.0f, f->gat_tiled_wshift) : 1.0f;
     a.lin_inv = 1.0f / a.lin_s;
-    if (half16) {
-        if (c->J == 17) k_gat_tiled<17, true, true><<<nwg, 256, ldsb, (hipStream_t)stream>>>(a);
-        else k_gat_tiled<19, true, true><<<nwg, 256, ldsb, (hipStream_t)stream>>>(a);
-    } else if (f->opt.gat_tiled_h4) {
-        if (c->J == 17) k_gat_tiled<17, true><<<nwg, 256, ldsb, (hipStream_t)stream>>>(a);
-        else k_gat_tiled<19, true><<<nwg, 256, ldsb, (hipStream_t)stream>>>(a);
-    } else {
-        if (c->J == 17) k_gat_tiled<17, false><<<nwg, 256, ldsb, (hipStream_t)stream>>>(a);
-        else k_gat_tiled<19, false><<<nwg, 256, ldsb, (hipStream_t)stream>>>(a);
-    }
+    kernel<<<nwg, 256, kTiledLds, (hipStream_t)stream>>>(a);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;
 }

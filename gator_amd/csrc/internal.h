@@ -152,8 +152,7 @@ int fused_set_encoder(gator_ctx* c, int mode);
 int fused_c3_state(const gator_ctx* c, float* bound);
 void fused_disable_persist(gator_ctx* c);      // from now on the four MDR stages run as four launches on this ctx
 int fused_set_graph_replay(gator_ctx* c, int on);          // returns the number of graph launches so far (>= 0)
-// samples of a batch of B that the sample-tiled encoder takes under the policy in force (unpinned: under the ctx's own AUTO policy)
-int fused_tiled_samples(const gator_ctx* c, int B, bool unpinned = false);
+int fused_encoder_for_batch(const gator_ctx* c, int B);      // GATOR_ENCODER_SAMPLE / _TILED: what the ctx's own AUTO policy gives a batch of B
 }  // namespace gator
 
 namespace gator {

@@ -1169,25 +1169,9 @@ __global__ __launch_bounds__(256, 2) void k_mdr_layer(const MdrArgs a, int nwg) 
 // even when the loop runs once; a second, cold copy of the body spills 2 KB per lane.  Not worth 10 % of the dominant kernel.)
 // Counter block of ONE persistent launch: [0..7] tickets per XCD, [8] error flag, [kCtrDone + stage * B + b] finished tiles of (stage,
 // sample), stage 0..3, with B and b the launch's own batch (a large forward runs as several launches over chunks of its samples,
-// launch_mdr: their blocks follow each other in FusedWs::mdr_ctr, see mdr_ctr_block).  The kernel's argument block stays exactly
+// forward_plan.h: their blocks follow each other in FusedWs::mdr_ctr, see MdrChunkPlan::block).  The kernel's argument block stays exactly
 // {stage arguments, ctr}: the tile body needs every scalar register there is, and each further scalar that must survive it
 // (measured with a base pointer, an offset and a stride more) is spilled into VGPR lanes and reloaded in its loops: +30 - 40 us.
-constexpr int kCtrError = 8, kCtrDone = 32;
-// chunk plan of a forward of B samples in nch launches: the first B % nch chunks have one sample more.  -> (chunk, first sample, size)
-// of sample b, and the word offset of a chunk's counter block
-struct MdrChunkPlan {
-    int nch, base, rem;
-    __host__ __device__ void locate(int b, int& ch, int& b0, int& n) const {
-        const int split = rem * (base + 1);
-        if (b < split) { ch = b / (base + 1); n = base + 1; b0 = ch * n; }
-        else { ch = rem + (b - split) / base; n = base; b0 = split + (ch - rem) * base; }
-    }
-    __host__ __device__ size_t block(int ch) const {
-        const int big = ch < rem ? ch : rem;
-        return (size_t)ch * kCtrDone + 4 * ((size_t)big * (base + 1) + (size_t)(ch - big) * base);
-    }
-};
-
 struct HeadArgs {
     const float *hf, *bn_w, *bn_b, *bn_mean, *bn_var, *bconv_w, *bconv_b;
     float *vc, *vcp;
@@ -1666,165 +1650,40 @@ LayerW make_layer(const FusedState* f, const gator_ctx* c, int li) {
     return w;
 }
 
-}  // namespace
+// Each kernel family names its instantiations once, from XA = 3 down (the order the kernels are emitted in): [3 - xa][stage form]
+using MdrLayerKernel = void (*)(const MdrArgs, int);
+using MdrPersistKernel = void (*)(const MdrPersistArgs);
+constexpr MdrLayerKernel kMdrLayer[4][3] = {{k_mdr_layer<0, 3>, k_mdr_layer<1, 3>, k_mdr_layer<2, 3>}, {k_mdr_layer<0, 2>, k_mdr_layer<1, 2>, k_mdr_layer<2, 2>},
+                                            {k_mdr_layer<0, 1>, k_mdr_layer<1, 1>, k_mdr_layer<2, 1>}, {k_mdr_layer<0, 0>, k_mdr_layer<1, 0>, k_mdr_layer<2, 0>}};
+constexpr MdrPersistKernel kMdrPersist[4] = {k_mdr_persist<3>, k_mdr_persist<2>, k_mdr_persist<1>, k_mdr_persist<0>};
 
-// pc [B,J,133] (reference layout) -> f->ws->vc [B,431,3] (vert431) ; taps: f->ws->lbf
-int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream, const float* x_out, const float* pose2d, bool half16) {
-    // half16 (BASELINE config 3): the layers on ONE fp16 activation plane (XA = 3); needs the default weight / joint-tile forms (GATOR_MDR_X3=2)
-    if (half16 && f->opt.mdr_x3 != 2) return fail(GATOR_EUNSUPPORTED, "16-bit MDR layers need GATOR_MDR_X3=2 (the default)");
-    const int xa = half16 ? 3 : f->opt.mdr_x3;
-    hipStream_t st = (hipStream_t)stream;
-    const Weights& w = c->w;
-    JointArgs ja;
-    ja.pc = pc; ja.jw_p = f->jfeat_p; ja.jb = w.jfeat_b; ja.posj_T = f->posj_T; ja.jkv = f->ws->jkv; ja.J = c->J;
-    for (int i = 0; i < 3; ++i) { ja.n1w[i] = w.lay[i].n1w; ja.n1b[i] = w.lay[i].n1b; ja.wk_p[i] = f->lay[i].wk; ja.wv_p[i] = f->lay[i].wv; }
-    ja.mdr_ctr = nullptr;
-    ja.x2 = f->opt.mdr_x3 == 2;
-    if (pc) {
-        if (f->opt.mdr_persist != 0) { ja.mdr_ctr = f->ws->mdr_ctr; f->ws->mdr_ctr_clean = true; }
-        StageTimer tm(c, "mdr_joint", stream);
-        k_mdr_joint<<<B, 128, 0, st>>>(ja);
-    }    // else: done by k_gat's epilogue / k_gat_joint
-    const size_t per = (size_t)f->ws->cap * kVT * 2 * kTile;      // one [B][14][2] tile set
-    const size_t perq = (size_t)f->ws->cap * kVT * 2 * (f->opt.mdr_x3 == 1 ? kTileX3 : kTile);      // q/k/v tile sets: X3 tiles are 1.5x, fp32 and X2 tiles 4 KiB (X1 tiles 2 KiB: half of a set is used)
-    float* set[3][4] = {{f->ws->vf, f->ws->q, f->ws->k, f->ws->v}, {f->ws->vf + per, f->ws->q + perq, f->ws->k + perq, f->ws->v + perq},
-                        {f->ws->vf + 2 * per, f->ws->q + 2 * perq, f->ws->k + 2 * perq, f->ws->v + 2 * perq}};
-    MdrArgs a{};
-    a.B = B; a.J = c->J; a.jkv = f->ws->jkv; a.pc = pc; a.xout = pc ? nullptr : x_out; a.vj = w.vj; a.tok_base = f->tok_base; a.tok_w3 = f->tok_w3;
-    a.head_w = f->opt.mdr_x3 ? f->wxbuf + (size_t)(f->head_w - f->lay[0].wq) / kTile * kTileX3 : f->head_w; a.head_b = f->head_b; a.hf = f->ws->hf; a.lbf = c->block_taps ? f->ws->lbf : nullptr;      // the "mdr_lbf2" tap costs 110 KB of stores per sample: recorded with the block taps only
-    a.hpart = f->opt.mdr_head_partials ? reinterpret_cast<double*>(f->ws->hpart) : nullptr;      // default on; GATOR_MDR_HEAD_PARTIALS=0 at create: the whole head in k_mdr_head (A/B)
-    a.bconv_w = w.bconv_w; a.hbn_w = w.bn_w; a.hbn_b = w.bn_b; a.hbn_mean = w.bn_mean; a.hbn_var = w.bn_var; a.halpha = c->alpha;
-    a.lin_s = f->opt.mdr_x3 == 2 ? std::ldexp(kActScale, f->mdr_wshift) : 1.0f;      // 4-product linears: 16 x activations, 2^wshift x weights
-    a.lin_inv = 1.0f / a.lin_s;
-    const int nwg = (B * kVT + 3) / 4;
 #ifdef GATOR_DIAG
-    {
-        static const int keep = -1, cut = 0;      // (sources of the asynchronous copies: they outlive the call)
-        GATOR_HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mdr_wmask), (f->opt.mdr_cut & 1) ? &cut : &keep, sizeof(int), 0, hipMemcpyHostToDevice, st));
-        GATOR_HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mdr_kvmask), (f->opt.mdr_cut & 2) ? &cut : &keep, sizeof(int), 0, hipMemcpyHostToDevice, st));
-    }
-    const bool want_stamps = f->opt.mdr_stamps;
-    const size_t solo = f->opt.mdr_solo ? 60 * 1024 : 0;      // 1 workgroup per CU (1 wave/SIMD)
-    DevBuf<unsigned long long> d_st, d_ends_buf;
-    if (want_stamps) { GATOR_TRY(d_st.alloc(512 * sizeof(unsigned long long))); GATOR_HIP_CHECK(hipMemset(d_st, 0, 512 * sizeof(unsigned long long))); }
-#else
-    constexpr size_t solo = 0;
-#endif
-    MdrPersistArgs pa{};
-    MdrChunkPlan plan{1, B, 0};
-    // Persistent launch(es) or four per-stage launches?  Same tile body, bitwise the same results.  The persistent form has no
-    // fractional generation per stage (R = workgroups per CU: 3.5 at B = 256 is billed as 4 by each of the four launches) and, cut
-    // into chunks, keeps a sample's tiles cache-resident between stages; below R = 3 (B < ~220) its per-sample dependency chain
-    // costs more than it saves.
-    const bool ctr_clean = f->ws->mdr_ctr_clean;      // zeroed for THIS call by the joint-token kernel queued just before (either entry point)
-    f->ws->mdr_ctr_clean = false;
-    const double R = (double)nwg / f->n_cu;
-    const bool auto_persist = R >= 3.0;      // (round 3 also asked for a wasted fractional generation >= 4 %; with chunked launches the persistent form wins from R = 3 on: sweep in DESIGN.md)
-    bool persist = f->opt.mdr_persist < 0 ? auto_persist : f->opt.mdr_persist > 0;
-    // the queues are per XCD and a workgroup serves the queue of the XCD it runs on: that drains every queue only when the device is
-    // the whole 8-XCD part (a partitioned device shows fewer CUs; its workgroups would all sit on one XCD).  A placement that leaves
-    // an XCD empty anyway is caught by k_mdr_head (completion counts) and answered by api.hip (four launches from then on).
-    if (f->n_cu != 256 && f->opt.mdr_persist < 0) persist = false;
-#ifdef GATOR_DIAG
-    if (want_stamps) persist = false;       // the stamps describe the per-stage launches
-#endif
-    for (int li = 0; li <= 3; ++li) {
-#ifdef GATOR_DIAG
-        a.stamps = (li == 1) ? d_st.get() : nullptr;
-#endif
-        // four launches: two sets in turn.  One persistent launch: stage li writes set li and nothing else ever does, so no CU can
-        // hold a stale L1 copy of a tile it reads (a line is only read after its one and only write) -- no cache invalidate in the
-        // kernel at all (`buffer_inv sc1` per tile start cost 30 us per forward, and `sc0` does not touch the L1 in this mode)
-        float** in = persist ? set[(li + 2) % 3] : set[(li + 1) & 1];
-        float** out = persist ? set[li % 3] : set[li & 1];
-        a.layer = li;
-        a.vf_in = in[0]; a.q_in = in[1]; a.k_in = in[2]; a.v_in = in[3];
-        a.vf_out = out[0]; a.q_out = out[1]; a.k_out = out[2]; a.v_out = out[3];
-        if (li > 0) a.prev = make_layer(f, c, li - 1);
-        if (li < 3) a.cur = make_layer(f, c, li);
-        if (persist) { pa.st[li] = a; continue; }
-        StageTimer tm(c, li == 0 ? "mdr_layer0" : (li < 3 ? "mdr_layer" : "mdr_attn_head"), stream);
-        if (xa == 3) {
-            if (li == 0) k_mdr_layer<0, 3><<<nwg, 256, solo, st>>>(a, nwg);
-            else if (li < 3) k_mdr_layer<1, 3><<<nwg, 256, solo, st>>>(a, nwg);
-            else k_mdr_layer<2, 3><<<nwg, 256, 0, st>>>(a, nwg);
-        } else if (f->opt.mdr_x3 == 2) {
-            if (li == 0) k_mdr_layer<0, 2><<<nwg, 256, solo, st>>>(a, nwg);
-            else if (li < 3) k_mdr_layer<1, 2><<<nwg, 256, solo, st>>>(a, nwg);
-            else k_mdr_layer<2, 2><<<nwg, 256, 0, st>>>(a, nwg);
-        } else if (f->opt.mdr_x3 == 1) {
-            if (li == 0) k_mdr_layer<0, 1><<<nwg, 256, solo, st>>>(a, nwg);
-            else if (li < 3) k_mdr_layer<1, 1><<<nwg, 256, solo, st>>>(a, nwg);
-            else k_mdr_layer<2, 1><<<nwg, 256, 0, st>>>(a, nwg);
-        } else {
-            if (li == 0) k_mdr_layer<0, 0><<<nwg, 256, 0, st>>>(a, nwg);
-            else if (li < 3) k_mdr_layer<1, 0><<<nwg, 256, 0, st>>>(a, nwg);
-            else k_mdr_layer<2, 0><<<nwg, 256, 0, st>>>(a, nwg);
-        }
-    }
-#ifdef GATOR_DIAG
-    unsigned long long* d_ends = nullptr;
+// The diagnostic library's probes around the MDR launches (set-up before them, synchronous read-back and printing behind them): GATOR_MDR_STAMPS' and
+// GATOR_MDR_ENDS' buffers, GATOR_MDR_SOLO's dynamic LDS that leaves one workgroup per CU (1 wave/SIMD)
+struct MdrDiag { DevBuf<unsigned long long> st, ends; size_t solo = 0; };
+
+int mdr_diag_setup(const FusedState* f, bool persist, hipStream_t st, MdrDiag& d) {
+    static const int keep = -1, cut = 0;      // (sources of the asynchronous copies: they outlive the call)
+    GATOR_HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mdr_wmask), (f->opt.mdr_cut & 1) ? &cut : &keep, sizeof(int), 0, hipMemcpyHostToDevice, st));
+    GATOR_HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mdr_kvmask), (f->opt.mdr_cut & 2) ? &cut : &keep, sizeof(int), 0, hipMemcpyHostToDevice, st));
+    d.solo = f->opt.mdr_solo ? 60 * 1024 : 0;
+    if (f->opt.mdr_stamps) { GATOR_TRY(d.st.alloc(512 * sizeof(unsigned long long))); GATOR_HIP_CHECK(hipMemset(d.st, 0, 512 * sizeof(unsigned long long))); }
     if (f->opt.mdr_ends && persist) {
-        GATOR_TRY(d_ends_buf.alloc(3 * 1024 * sizeof(unsigned long long)));
-        d_ends = d_ends_buf.get();
+        GATOR_TRY(d.ends.alloc(3 * 1024 * sizeof(unsigned long long)));
+        unsigned long long* d_ends = d.ends.get();
         GATOR_HIP_CHECK(hipMemset(d_ends, 0, 3 * 1024 * sizeof(unsigned long long)));
         GATOR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_persist_ends), &d_ends, sizeof(d_ends)));
     }
-#endif
-    if (persist) {      // the four stages as persistent launches (k_mdr_persist): tickets and per-sample completion counts start from zero
-        if (!ctr_clean) GATOR_HIP_CHECK(hipMemsetAsync(f->ws->mdr_ctr, 0, mdr_ctr_words(B) * sizeof(unsigned), st));
-        StageTimer tm(c, "mdr_layers", stream);
-        int grid = 2 * f->n_cu;             // two workgroups per CU is what the registers allow; any grid drains the queues
-        if (f->opt.mdr_persist_grid > 0) grid = f->opt.mdr_persist_grid;      // GATOR_MDR_PERSIST_GRID (tests: a grid that leaves XCDs without a workgroup)
-        // A large batch runs as several launches over chunks of 256 .. 511 samples.  The tickets are stage-major, so a sample's Q/K/V/residual
-        // tiles (448 KB) are read one stage after they were written: at B = 256 / 384 the 115 / 172 MB in between stay in the Infinity
-        // Cache, at B = 512 and above they do not and the launch costs 1.545 - 1.565 us per sample instead of 1.495 (measured, round 4).
-        // Chunks are independent (a tile depends on its own sample only) and each writes its own tiles exactly once, so the hand-off
-        // rules of the kernel hold per launch; results are bitwise those of one launch.
-        // Chunk size, measured at the end of round 4 (MDR stage in ms, one box, two repetitions; GATOR_MDR_PERSIST_CHUNK): B = 512: one
-        // launch 0.79, 2 x 256 0.76; B = 1024: 3 x 342 1.525, 4 x 256 1.49; B = 2048: 6 x 342 2.99 - 3.18, 8 x 256 2.97 - 3.00; B = 4096:
-        // 12 x 342 6.43, 16 x 256 6.34 -- so floor(B / 256) launches.  (Every chunk using the first chunk's tile region again -- legal: a
-        // chunk-local sample keeps its XCD and a launch starts with an empty L1 -- changes nothing: the tiles are written before they are read.
-        // Odd chunks on a second, low-priority stream so that a chunk's workgroups move into the slots the previous chunk's tail frees:
-        // nothing either, B = 512 .. 2048, two repetitions.)
-        // (the one-plane form's Q / K / V tiles are half the size: chunks of 342 - 512 samples measure 6 % faster than 256 at B = 2 048 -- 3.25
-        // against 3.45 ms per forward, two repetitions, one box -- so it runs ceil(B / 384) launches)
-        int nch = f->opt.mdr_persist_chunk > 0 ? (B + f->opt.mdr_persist_chunk - 1) / f->opt.mdr_persist_chunk : (xa == 3 ? (B + 383) / 384 : B / 256);
-        if (nch < 1) nch = 1;
-        if (nch > kMdrCtrChunks) nch = kMdrCtrChunks;
-        const size_t tq = f->opt.mdr_x3 == 1 ? kTileX3 : (xa == 3 ? kTileX1 : kTile);
-        plan = MdrChunkPlan{nch, B / nch, B % nch};
-        for (int ch = 0, b0 = 0; ch < nch; ++ch) {
-            const int n = B / nch + (ch < B % nch ? 1 : 0);
-            MdrPersistArgs pc_ = pa;
-            for (int li = 0; li <= 3; ++li) {
-                MdrArgs& s = pc_.st[li];
-                const size_t ov = (size_t)b0 * kVT * 2 * kTile, oq = (size_t)b0 * kVT * 2 * tq;
-                s.B = n;
-                s.vf_in += ov; s.q_in += oq; s.k_in += oq; s.v_in += oq;
-                s.vf_out += ov; s.q_out += oq; s.k_out += oq; s.v_out += oq;
-                s.jkv += (size_t)b0 * 12 * kTile;
-                if (s.pc) s.pc += (size_t)b0 * c->J * 133;
-                if (s.xout) s.xout += (size_t)b0 * c->J * 3;
-                s.hf += (size_t)b0 * kV * 32;
-                if (s.hpart) s.hpart += (size_t)b0 * kVT * 64;
-                if (s.lbf) s.lbf += (size_t)b0 * kV * kE;
-            }
-            pc_.ctr = f->ws->mdr_ctr + plan.block(ch);
-            if (xa == 3) k_mdr_persist<3><<<grid, 256, 0, st>>>(pc_);
-            else if (f->opt.mdr_x3 == 2) k_mdr_persist<2><<<grid, 256, 0, st>>>(pc_);
-            else if (f->opt.mdr_x3 == 1) k_mdr_persist<1><<<grid, 256, 0, st>>>(pc_);
-            else k_mdr_persist<0><<<grid, 256, 0, st>>>(pc_);
-            b0 += n;
-        }
-    }
-#ifdef GATOR_DIAG
-    if (d_ends) {      // synchronous read-back (diagnostic build only): when did each workgroup of the LAST persistent launch start / take its last ticket / end?
+    return GATOR_OK;
+}
+
+int mdr_diag_report(MdrDiag& d, int B) {
+    if (d.ends) {      // synchronous read-back (diagnostic build only): when did each workgroup of the LAST persistent launch start / take its last ticket / end?
         std::vector<unsigned long long> he(3 * 1024);
-        GATOR_HIP_CHECK(hipMemcpy(he.data(), d_ends, he.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        GATOR_HIP_CHECK(hipMemcpy(he.data(), d.ends, he.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         unsigned long long* none = nullptr;
         GATOR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_persist_ends), &none, sizeof(none)));
-        d_ends_buf.reset();
+        d.ends.reset();
         unsigned long long t0 = ~0ull, t1 = 0;
         int n = 0;
         for (int i = 0; i < 1024; ++i) if (he[3 * i + 2]) { t0 = std::min(t0, he[3 * i]); t1 = std::max(t1, he[3 * i + 2]); ++n; }
@@ -1844,9 +1703,9 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
                     B, n, (double)(t1 - t0) / 100.0, start_spread, first_end, ends[n / 10], ends[n / 2], ends[n * 9 / 10], ends[n - 1], idle / n, lastlen / n);
         }
     }
-    if (d_st) {
+    if (d.st) {
         unsigned long long hst[512];
-        GATOR_HIP_CHECK(hipMemcpy(hst, d_st, sizeof(hst), hipMemcpyDeviceToHost));
+        GATOR_HIP_CHECK(hipMemcpy(hst, d.st, sizeof(hst), hipMemcpyDeviceToHost));
         const int ns = (B * kVT + 63) / 64;
         unsigned long long t0 = ~0ull;
         for (int i = 0; i < ns && i < 120; ++i) if (hst[8 + 4 * i] && hst[8 + 4 * i] < t0) t0 = hst[8 + 4 * i];
@@ -1855,30 +1714,118 @@ int launch_mdr(gator_ctx* c, FusedState* f, const float* pc, int B, void* stream
             fprintf(stderr, " %d:(%.0f,%.0f,%llu,x%llu,cu%llu.se%llu)", i * 64, (hst[8 + 4 * i] - t0) / 100.0, (hst[9 + 4 * i] - t0) / 100.0,
                     hst[10 + 4 * i] / 1000, hst[11 + 4 * i] >> 32, (hst[11 + 4 * i] >> 8) & 0xf, (hst[11 + 4 * i] >> 13) & 0x7);
         fprintf(stderr, "\n");
-        d_st.reset();
+        d.st.reset();
         fprintf(stderr, "[k_mdr_layer<1> stamps, tile 0] attention(2 heads)=%llu outproj+res=%llu cross-attn block=%llu mlp=%llu customLN+qkv=%llu\n",
                 hst[0], hst[1], hst[2], hst[3], hst[4]);
     }
+    return GATOR_OK;
+}
+#endif
+
+}  // namespace
+
+// pc [B,J,133] (reference layout) -> ws.vc [B,431,3] (vert431) ; taps: ws.lbf.  Layer form, persistent launches and chunks, head, who zeroes the counters: p
+int launch_mdr(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pc, int B, void* stream, const float* x_out, const float* pose2d) {
+    const int xa = p.xa, persist = p.persist;
+    hipStream_t st = (hipStream_t)stream;
+    const Weights& w = c->w;
+    JointArgs ja;
+    ja.pc = pc; ja.jw_p = f->jfeat_p; ja.jb = w.jfeat_b; ja.posj_T = f->posj_T; ja.jkv = ws.jkv; ja.J = c->J;
+    for (int i = 0; i < 3; ++i) { ja.n1w[i] = w.lay[i].n1w; ja.n1b[i] = w.lay[i].n1b; ja.wk_p[i] = f->lay[i].wk; ja.wv_p[i] = f->lay[i].wv; }
+    ja.mdr_ctr = p.ctr_zero == CtrZero::MDR_JOINT ? ws.mdr_ctr : nullptr;
+    ja.x2 = f->opt.mdr_x3 == 2;
+    if (pc) {
+        StageTimer tm(c, "mdr_joint", stream);
+        k_mdr_joint<<<B, 128, 0, st>>>(ja);
+    }    // else: done by k_gat8's epilogue / k_gat_joint
+    const size_t per = (size_t)ws.cap * kVT * 2 * kTile;      // one [B][14][2] tile set
+    const size_t perq = (size_t)ws.cap * kVT * 2 * (f->opt.mdr_x3 == 1 ? kTileX3 : kTile);      // q/k/v tile sets: X3 tiles are 1.5x, fp32 and X2 tiles 4 KiB (X1 tiles 2 KiB: half of a set is used)
+    float* set[3][4] = {{ws.vf, ws.q, ws.k, ws.v}, {ws.vf + per, ws.q + perq, ws.k + perq, ws.v + perq},
+                        {ws.vf + 2 * per, ws.q + 2 * perq, ws.k + 2 * perq, ws.v + 2 * perq}};
+    MdrArgs a{};
+    a.B = B; a.J = c->J; a.jkv = ws.jkv; a.pc = pc; a.xout = pc ? nullptr : x_out; a.vj = w.vj; a.tok_base = f->tok_base; a.tok_w3 = f->tok_w3;
+    a.head_w = f->opt.mdr_x3 ? f->wxbuf + (size_t)(f->head_w - f->lay[0].wq) / kTile * kTileX3 : f->head_w; a.head_b = f->head_b; a.hf = ws.hf; a.lbf = c->block_taps ? ws.lbf : nullptr;      // the "mdr_lbf2" tap costs 110 KB of stores per sample: recorded with the block taps only
+    a.hpart = p.head == MdrHead::FINISH ? reinterpret_cast<double*>(ws.hpart) : nullptr;      // the tiles leave the head conv's partial sums; else the whole head runs in k_mdr_head (A/B)
+    a.bconv_w = w.bconv_w; a.hbn_w = w.bn_w; a.hbn_b = w.bn_b; a.hbn_mean = w.bn_mean; a.hbn_var = w.bn_var; a.halpha = c->alpha;
+    a.lin_s = f->opt.mdr_x3 == 2 ? std::ldexp(kActScale, f->mdr_wshift) : 1.0f;      // 4-product linears: 16 x activations, 2^wshift x weights
+    a.lin_inv = 1.0f / a.lin_s;
+    const int nwg = (B * kVT + 3) / 4;
+#ifdef GATOR_DIAG
+    MdrDiag diag;
+    GATOR_TRY(mdr_diag_setup(f, persist, st, diag));
+    const size_t solo = xa != 0 ? diag.solo : 0;
+#else
+    constexpr size_t solo = 0;
+#endif
+    MdrPersistArgs pa{};
+    for (int li = 0; li <= 3; ++li) {
+#ifdef GATOR_DIAG
+        a.stamps = (li == 1) ? diag.st.get() : nullptr;
+#endif
+        // four launches: two sets in turn.  One persistent launch: stage li writes set li and nothing else ever does, so no CU can
+        // hold a stale L1 copy of a tile it reads (a line is only read after its one and only write) -- no cache invalidate in the
+        // kernel at all (`buffer_inv sc1` per tile start cost 30 us per forward, and `sc0` does not touch the L1 in this mode)
+        float** in = persist ? set[(li + 2) % 3] : set[(li + 1) & 1];
+        float** out = persist ? set[li % 3] : set[li & 1];
+        a.layer = li;
+        a.vf_in = in[0]; a.q_in = in[1]; a.k_in = in[2]; a.v_in = in[3];
+        a.vf_out = out[0]; a.q_out = out[1]; a.k_out = out[2]; a.v_out = out[3];
+        if (li > 0) a.prev = make_layer(f, c, li - 1);
+        if (li < 3) a.cur = make_layer(f, c, li);
+        if (persist) { pa.st[li] = a; continue; }
+        StageTimer tm(c, li == 0 ? "mdr_layer0" : (li < 3 ? "mdr_layer" : "mdr_attn_head"), stream);
+        const MdrLayerKernel layer = kMdrLayer[3 - xa][li == 0 ? 0 : li < 3 ? 1 : 2];
+        layer<<<nwg, 256, li < 3 ? solo : 0, st>>>(a, nwg);
+    }
+    if (persist) {      // the four stages as persistent launches (k_mdr_persist): tickets and per-sample completion counts start from zero (p.ctr_zero's launch)
+        StageTimer tm(c, "mdr_layers", stream);
+        const size_t tq = f->opt.mdr_x3 == 1 ? kTileX3 : (xa == 3 ? kTileX1 : kTile);
+        for (int ch = 0, b0 = 0; ch < p.chunks.nch; ++ch) {
+            const int n = p.chunks.base + (ch < p.chunks.rem ? 1 : 0);
+            MdrPersistArgs pc_ = pa;
+            for (int li = 0; li <= 3; ++li) {
+                MdrArgs& s = pc_.st[li];
+                const size_t ov = (size_t)b0 * kVT * 2 * kTile, oq = (size_t)b0 * kVT * 2 * tq;
+                s.B = n;
+                s.vf_in += ov; s.q_in += oq; s.k_in += oq; s.v_in += oq;
+                s.vf_out += ov; s.q_out += oq; s.k_out += oq; s.v_out += oq;
+                s.jkv += (size_t)b0 * 12 * kTile;
+                if (s.pc) s.pc += (size_t)b0 * c->J * 133;
+                if (s.xout) s.xout += (size_t)b0 * c->J * 3;
+                s.hf += (size_t)b0 * kV * 32;
+                if (s.hpart) s.hpart += (size_t)b0 * kVT * 64;
+                if (s.lbf) s.lbf += (size_t)b0 * kV * kE;
+            }
+            pc_.ctr = ws.mdr_ctr + p.chunks.block(ch);
+            const MdrPersistKernel layers = kMdrPersist[3 - xa];
+            layers<<<p.grid, 256, 0, st>>>(pc_);
+            b0 += n;
+        }
+    }
+#ifdef GATOR_DIAG
+    GATOR_TRY(mdr_diag_report(diag, B));
 #endif
     HeadArgs ha;
-    ha.hf = f->ws->hf; ha.bn_w = w.bn_w; ha.bn_b = w.bn_b; ha.bn_mean = w.bn_mean; ha.bn_var = w.bn_var;
-    ha.bconv_w = w.bconv_w; ha.bconv_b = w.bconv_b; ha.vc = f->ws->vc; ha.vcp = f->ws->vcp;
-    ha.persist_ctr = persist ? f->ws->mdr_ctr : nullptr;
-    ha.plan = plan;
+    ha.hf = ws.hf; ha.bn_w = w.bn_w; ha.bn_b = w.bn_b; ha.bn_mean = w.bn_mean; ha.bn_var = w.bn_var;
+    ha.bconv_w = w.bconv_w; ha.bconv_b = w.bconv_b; ha.vc = ws.vc; ha.vcp = ws.vcp;
+    ha.persist_ctr = persist ? ws.mdr_ctr : nullptr;
+    ha.plan = p.chunks;
     ha.status = c->status_dev;
     ha.pose2d = pose2d; ha.J = c->J;      // nullptr from the MDR-only entry point: its input is the pose features, not the poses
-    ha.vcp2 = f->opt.up_x3 == 2 ? (_Float16*)f->ws->vcp3 : nullptr;
-    ha.vcp3 = f->opt.up_x3 == 1 ? (__bf16*)f->ws->vcp3 : nullptr; ha.vcp3_plane = upsample_x3_vcp_elems(f->ws->cap) / 3;     // plane stride fixed by the workspace capacity
+    ha.vcp2 = f->opt.up_x3 == 2 ? (_Float16*)ws.vcp3 : nullptr;
+    ha.vcp3 = f->opt.up_x3 == 1 ? (__bf16*)ws.vcp3 : nullptr; ha.vcp3_plane = upsample_x3_vcp_elems(ws.cap) / 3;     // plane stride fixed by the workspace capacity
     ha.alpha = c->alpha;
     {
         StageTimer tm(c, "mdr_head", stream);
-        if (a.hpart) k_mdr_head_finish<<<B, 256, 0, st>>>(ha, a.hpart);      // the conv came out of the tiles as partial sums: what is left is light
-        else if (B <= 2 * f->n_cu) k_mdr_head<512, true><<<B, 512, 0, st>>>(ha);
-        else k_mdr_head<512, false><<<B, 512, 0, st>>>(ha);
+        switch (p.head) {
+        case MdrHead::FINISH: k_mdr_head_finish<<<B, 256, 0, st>>>(ha, a.hpart); break;      // the conv came out of the tiles as partial sums: what is left is light
+        case MdrHead::WHOLE_HOIST: k_mdr_head<512, true><<<B, 512, 0, st>>>(ha); break;
+        case MdrHead::WHOLE: k_mdr_head<512, false><<<B, 512, 0, st>>>(ha); break;
+        }
     }
     GATOR_HIP_CHECK(hipGetLastError());
-    c->set_tap(TAP_MDR_LBF2, c->block_taps ? f->ws->lbf : nullptr, c->block_taps ? (int64_t)B * kV * kE : 0);
-    c->set_tap(TAP_VERT431, f->ws->vc, (int64_t)B * kV * 3);
+    c->set_tap(TAP_MDR_LBF2, c->block_taps ? ws.lbf : nullptr, c->block_taps ? (int64_t)B * kV * kE : 0);
+    c->set_tap(TAP_VERT431, ws.vc, (int64_t)B * kV * 3);
     return GATOR_OK;
 }
 

@@ -111,13 +111,13 @@ int pack_upsample_bf16(const float* up_w, void* dst, void* stream) {
     return GATOR_OK;
 }
 
-int launch_upsample_bf16(const FusedState* f, const gator_ctx* c, const float* vc, int B, float* verts, void* stream) {
+int launch_upsample_bf16(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const float* vc, int B, float* verts, void* stream) {
     const int MT = (B + 31) / 32;
     const int64_t total = (int64_t)upsample_bf16_vcp_elems(B);
-    k_pack_vc_bf16<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(vc, B, (__bf16*)f->ws->vcp16.get(), total);
+    k_pack_vc_bf16<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(vc, B, (__bf16*)ws.vcp16.get(), total);
     const int MP = (MT + 1) / 2;
     const int nwg = kOB * ((MP + 3) / 4);
-    k_upsample_bf16<<<nwg, 256, 0, (hipStream_t)stream>>>((const __bf16*)f->ws->vcp16.get(), (const __bf16*)f->up_w16.get(), c->w.up_b, c->w.v6890,
+    k_upsample_bf16<<<nwg, 256, 0, (hipStream_t)stream>>>((const __bf16*)ws.vcp16.get(), (const __bf16*)f->up_w16.get(), c->w.up_b, c->w.v6890,
                                                          verts, B, MT, nwg);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;

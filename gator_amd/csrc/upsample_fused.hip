@@ -138,16 +138,16 @@ int launch_pack_vc(const float* vc, int B, float* vcp, void* stream) {
     return GATOR_OK;
 }
 
-int launch_upsample(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream) {
+int launch_upsample(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream) {
     const int MT = (B + 31) / 32;
     if (MT >= 8) {          // >= 225 samples: two tiles per wave
         const int MP = (MT + 1) / 2, nwg = kOB * ((MP + 3) / 4);
-        k_upsample<2><<<nwg, 256, 0, (hipStream_t)stream>>>(f->ws->vcp, f->up_w, c->w.up_b, c->w.v6890, verts, B, MT, nwg);
+        k_upsample<2><<<nwg, 256, 0, (hipStream_t)stream>>>(ws.vcp, f->up_w, c->w.up_b, c->w.v6890, verts, B, MT, nwg);
         GATOR_HIP_CHECK(hipGetLastError());
         return GATOR_OK;
     }
     const int nwg = kOB * ((MT + 3) / 4);
-    k_upsample<1><<<nwg, 256, 0, (hipStream_t)stream>>>(f->ws->vcp, f->up_w, c->w.up_b, c->w.v6890, verts, B, MT, nwg);
+    k_upsample<1><<<nwg, 256, 0, (hipStream_t)stream>>>(ws.vcp, f->up_w, c->w.up_b, c->w.v6890, verts, B, MT, nwg);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;
 }

@@ -266,13 +266,13 @@ int launch_pack_vc_x2(const float* vc, int B, void* vcp2, void* stream) {
 }
 
 // verts == nullptr: vertices are not stored (joint regression only); with_joints: also fill f->jr_P for launch_jreg_reduce
-int launch_upsample_x2(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints, bool w1) {
+int launch_upsample_x2(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream, bool with_joints, bool w1) {
     const int MT = (B + 31) / 32, MG = (MT + 3) / 4;
     const JregEpi jr = jreg_epi(f, with_joints);
     const int nwg = (kOB / 2) * MG;
-    if (w1) k_upsample_x2<false><<<nwg, 512, kX2Lds, (hipStream_t)stream>>>((const _Float16*)f->ws->vcp3, (const _Float16*)f->up_w2.get(), c->w.up_b, c->w.v6890,
+    if (w1) k_upsample_x2<false><<<nwg, 512, kX2Lds, (hipStream_t)stream>>>((const _Float16*)ws.vcp3, (const _Float16*)f->up_w2.get(), c->w.up_b, c->w.v6890,
                                                                            verts, B, MT, MG, nwg, f->up_w2_unscale, jr);
-    else k_upsample_x2<true><<<nwg, 512, kX2Lds, (hipStream_t)stream>>>((const _Float16*)f->ws->vcp3, (const _Float16*)f->up_w2.get(), c->w.up_b, c->w.v6890,
+    else k_upsample_x2<true><<<nwg, 512, kX2Lds, (hipStream_t)stream>>>((const _Float16*)ws.vcp3, (const _Float16*)f->up_w2.get(), c->w.up_b, c->w.v6890,
                                                                        verts, B, MT, MG, nwg, f->up_w2_unscale, jr);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;

@@ -232,12 +232,12 @@ int launch_jreg_reduce(const FusedState* f, int B, float* joints, void* stream) 
 }
 
 // verts == nullptr: vertices are not stored (joint regression only); with_joints: also fill f->jr_P for launch_jreg_reduce
-int launch_upsample_x3(const FusedState* f, const gator_ctx* c, int B, float* verts, void* stream, bool with_joints) {
+int launch_upsample_x3(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream, bool with_joints) {
     const int MT = (B + 31) / 32;
     const JregEpi jr = jreg_epi(f, with_joints);
-    const int64_t w_plane = (int64_t)upsample_x3_weight_elems() / 3, a_plane = (int64_t)upsample_x3_vcp_elems(f->ws->cap) / 3;
+    const int64_t w_plane = (int64_t)upsample_x3_weight_elems() / 3, a_plane = (int64_t)upsample_x3_vcp_elems(ws.cap) / 3;
     const int nwg = kOB * ((MT + kX3Waves - 1) / kX3Waves);
-    k_upsample_x3<<<nwg, 64 * (kX3Waves + 1), 0, (hipStream_t)stream>>>((const __bf16*)f->ws->vcp3, (const __bf16*)f->up_w3.get(), c->w.up_b,
+    k_upsample_x3<<<nwg, 64 * (kX3Waves + 1), 0, (hipStream_t)stream>>>((const __bf16*)ws.vcp3, (const __bf16*)f->up_w3.get(), c->w.up_b,
                                                                        c->w.v6890, verts, B, MT, nwg, a_plane, w_plane, jr);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;
