@@ -618,10 +618,34 @@ __global__ __launch_bounds__(kThreads) void k_t_softmax_bwd(const float* __restr
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
     const float *pr = p + row * n, *dr = dp + row * n;
-    double s = 0.0;
-    for (int i = lane; i < n; i += 64) s += (double)pr[i] * dr[i];
-    const float t = (float)wave_sum(s);
-    for (int i = lane; i < n; i += 64) dx[row * n + i] = pr[i] * (dr[i] - t);
+    // dx = p (dp - sum(p dp)) does not change when a constant c is taken off dp.  Where one p is (nearly) 1, dp - sum(p dp) of that entry
+    // cancels down to the other entries' p (1e-10, say), below what the rounded p - they sum to 1 only to ~1e-7 - or even a double sum can
+    // hold.  With c = dp at the largest p (ties: the lowest index, so that every lane agrees) that entry's term is exactly 0 and the rest
+    // keep their relative precision; dividing by sum(p) makes the stored p a distribution again.
+    float pm = -1.f;
+    int im = 0;
+    for (int i = lane; i < n; i += 64)
+        if (pr[i] > pm) {
+            pm = pr[i];
+            im = i;
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float po = __shfl_xor(pm, o);
+        const int io = __shfl_xor(im, o);
+        if (po > pm || (po == pm && io < im)) {
+            pm = po;
+            im = io;
+        }
+    }
+    const double c = (double)dr[im];
+    double s = 0.0, z = 0.0;
+    for (int i = lane; i < n; i += 64) {
+        s += (double)pr[i] * ((double)dr[i] - c);
+        z += (double)pr[i];
+    }
+    const double t = wave_sum(s) / wave_sum(z);
+    for (int i = lane; i < n; i += 64) dx[row * n + i] = (float)((double)pr[i] * (((double)dr[i] - c) - t));
 }
 
 // ------------------------------------------------------------------------------------------------------------ dropout
@@ -1056,7 +1080,7 @@ int gator_t_layernorm_fwd(const float* x, int64_t rows, int n, const float* w, c
 
 int gator_t_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rinv, const float* w, int64_t rows, int n, float eps,
                           int mode, float* dx, float* dy_xhat, const float* add, gator_stream stream) {
-    if (!dy || !x || !mean || !rinv || !dx) return fail(1, "gator_t_layernorm_bwd: null argument");
+    if (!dy || !x || !mean || !rinv || !dx || n < 1 || (mode == 1 && n < 2)) return fail(1, "gator_t_layernorm_bwd: bad argument");
     if (rows == 0) return 0;
     hipLaunchKernelGGL(k_t_ln_bwd, dim3((unsigned)((rows + 3) / 4)), dim3(kThreads), 0, (hipStream_t)stream, dy, x, mean, rinv, w, rows, n, eps, mode, dx,
                        dy_xhat, add);
@@ -1220,6 +1244,7 @@ int gator_t_mgcn_bwd(const float* h0, const float* h1, const float* adj, const f
 int gator_t_batchnorm_fwd(const float* x, const float* w, const float* b, float* y, float* mean, float* rinv, float* run_mean, float* run_var, int B,
                           int C, int L, float eps, float momentum, gator_stream stream) {
     if (!x || !w || !b || !y || !mean || !rinv || B <= 0 || C <= 0 || L <= 0 || (run_mean && !run_var)) return fail(1, "gator_t_batchnorm_fwd: bad argument");
+    if ((int64_t)B * L < 2) return fail(1, "gator_t_batchnorm_fwd: training mode needs more than one value per channel (B * L = 1)");
     BnArgs a;
     a.x = x; a.w = w; a.b = b; a.y = y; a.mean = mean; a.rinv = rinv; a.run_mean = run_mean; a.run_var = run_var; a.B = B; a.C = C; a.L = L;
     a.eps = eps; a.momentum = momentum; a.dy = nullptr; a.dx = a.dw = a.db = nullptr;

@@ -100,7 +100,8 @@ int gator_t_mgcn_bwd(const float* h0, const float* h1, const float* adj, const f
 
 /* nn.BatchNorm1d(C) in training mode on x [B,C,L] (the MDR head's BatchNorm1d(431) over [B,431,3], MDR.py:119,159): batch statistics over
  * (B, L), biased variance in the normalisation; run_mean / run_var (or NULL) updated with `momentum` and the unbiased variance, as torch does.
- * mean / rinv [C] are kept for the backward, which writes dx and the whole dw, db. */
+ * mean / rinv [C] are kept for the backward, which writes dx and the whole dw, db.  B * L = 1 (one value per channel: no variance to
+ * normalise by, no unbiased one for run_var) is refused before anything is written, as torch refuses it. */
 int gator_t_batchnorm_fwd(const float* x, const float* w, const float* b, float* y, float* mean, float* rinv, float* run_mean, float* run_var, int B,
                           int C, int L, float eps, float momentum, gator_stream stream);
 int gator_t_batchnorm_bwd(const float* dy, const float* x, const float* w, const float* mean, const float* rinv, float* dx, float* dw, float* db, int B,
@@ -112,14 +113,15 @@ int64_t gator_t_struct_size(int which);
 /* rows of n contiguous floats.  mode 0: nn.LayerNorm (biased variance, eps inside the root); mode 1: the MDR LayerNorm
  * (lib/models/vanilla_transformer_encoder.py:31-34: unbiased std, eps added to the std).  w, b may be NULL (no affine).
  * forward saves mean[rows] and rinv[rows] (1/sqrt(var+eps) resp. 1/(std+eps)); backward writes dx and, if dy_xhat != NULL,
- * dy * xhat (whose column sums are the weight gradient). */
+ * dy * xhat (whose column sums are the weight gradient).  Both refuse n < 1, and n < 2 in mode 1 (no unbiased std of one value). */
 int gator_t_layernorm_fwd(const float* x, int64_t rows, int n, const float* w, const float* b, float eps, int mode, float* y,
                           float* mean, float* rinv, gator_stream stream);
 int gator_t_layernorm_bwd(const float* dy, const float* x, const float* mean, const float* rinv, const float* w, int64_t rows,
                           int n, float eps, int mode, float* dx, float* dy_xhat, const float* add /* dx += add (the residual branch), or NULL */,
                           gator_stream stream);
 
-/* softmax over rows of n contiguous floats, and its backward dx = p * (dp - sum(dp * p)) */
+/* softmax over rows of n contiguous floats, and its backward dx = p * (dp - sum(dp * p)), formed as p * ((dp - c) - sum(p * (dp - c)) / sum(p))
+ * with c = dp at the row's largest p: the same value, without the cancellation against the rounding of the stored p where one p is nearly 1 */
 int gator_t_softmax_fwd(const float* x, int64_t rows, int n, float* p, gator_stream stream);
 int gator_t_softmax_bwd(const float* p, const float* dp, int64_t rows, int n, float* dx, gator_stream stream);
 

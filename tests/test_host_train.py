@@ -82,3 +82,56 @@ def test_keep_mask_reference_statistics_at_the_device_round_count():
     assert np.array_equal(keep_mask(123, 1, 64, 0.4, step=3), keep_mask(123, 1 + (3 << 32), 64, 0.4))
     assert not np.array_equal(keep_mask(123, 1, 64, 0.4, step=3), masks[0.4][:64])
     assert keep_threshold(0.0) == 0 and keep_threshold(0.5) == 1 << 31 and keep_threshold(0.99999999999) == 0xffffffff
+
+
+def test_mgcn_reference_equals_the_explicit_triple_loop():
+    import torch
+    from tests.train_refs import mgcn_ref
+    rs = np.random.RandomState(40)
+    B, J, C = 2, 3, 4
+    h0, h1, adj, Mw, bias = rs.randn(B, J, C), rs.randn(B, J, C), rs.randn(J, J), rs.randn(J, C), rs.randn(C)
+    want = np.zeros((B, J, C))
+    for b in range(B):
+        for i in range(J):
+            for c in range(C):
+                acc = adj[i, i] * Mw[i, c] * h0[b, i, c] + bias[c]
+                for j in range(J):
+                    if j != i:
+                        acc += adj[i, j] * Mw[j, c] * h1[b, j, c]
+                want[b, i, c] = acc
+    got = mgcn_ref(*[torch.from_numpy(a) for a in (h0, h1, adj, Mw, bias)]).numpy()
+    assert got.shape == want.shape and np.abs(got - want).max() <= 1e-14 * np.abs(want).max()
+    assert np.abs(adj - adj.T).max() > 0.1                 # a transposed adjacency would not pass
+
+
+def test_adam_reference_follows_torch_adam_for_five_steps():
+    import torch
+    from tests.train_refs import adam_step_ref
+    rs = np.random.RandomState(41)
+    for lr, betas, eps in ((1e-3, (0.9, 0.999), 1e-8), (3e-2, (0.8, 0.99), 1e-6)):
+        p = torch.from_numpy(rs.randn(33))
+        tp = p.clone().requires_grad_(True)
+        opt = torch.optim.Adam([tp], lr=lr, betas=betas, eps=eps)
+        m, v = torch.zeros_like(p), torch.zeros_like(p)
+        for t in range(1, 6):
+            g = torch.from_numpy(rs.randn(33) * 10.0 ** rs.randint(-3, 3, 33))
+            tp.grad = g.clone()
+            opt.step()
+            p, m, v = adam_step_ref(p, g, m, v, lr, betas[0], betas[1], eps, t)
+            st = opt.state[tp]
+            for ours, theirs in ((p, tp.detach()), (m, st['exp_avg']), (v, st['exp_avg_sq'])):
+                assert float((ours - theirs).abs().max()) <= 1e-13 * float(theirs.abs().max()), t
+
+
+def test_layernorm_reference_mode_1_equals_the_oracle():
+    import torch
+    from oracle.gator_oracle import _custom_ln
+    from tests.train_refs import layernorm_ref
+    rs = np.random.RandomState(42)
+    for n in (2, 20, 65):
+        x, w, b = [torch.from_numpy(rs.randn(*s)) for s in ((5, n), (n,), (n,))]
+        want = _custom_ln(x, w, b, 1e-6)
+        assert float((layernorm_ref(x, w, b, 1e-6, 1) - want).abs().max()) <= 1e-14 * float(want.abs().max())
+        assert float((layernorm_ref(x, None, None, 1e-6, 1) - _custom_ln(x, 1.0, 0.0, 1e-6)).abs().max()) <= 1e-14 * float(want.abs().max())
+    x = torch.from_numpy(rs.randn(3, 7))
+    assert torch.equal(layernorm_ref(x, None, None, 1e-5, 0), torch.nn.functional.layer_norm(x, (7,), None, None, 1e-5))

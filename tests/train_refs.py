@@ -1,7 +1,8 @@
 """Host references for the training-row tests: a numpy Philox4x32 (Salmon et al., SC'11 / Random123) that is checked against the
 published known-answer vectors in tests/test_host_train.py, the keep mask include/gator_train.h documents for gator_t_dropout, and
-float64 torch-CPU forms of the fused dropout-on operations built on that mask, the error criterion the new GPU tests share, and the
-per-term quantities of the oracle's face losses from which the kink margins are measured.  Nothing here calls the library under test."""
+float64 torch-CPU forms of the fused dropout-on operations built on that mask, of both LayerNorm modes, the MGCN layer and one Adam step
+(each checked on the host in tests/test_host_train.py), the error criterion the new GPU tests share, and the per-term quantities of the
+oracle's face losses from which the kink margins are measured.  Nothing here calls the library under test."""
 import numpy as np
 import torch
 
@@ -79,6 +80,42 @@ def drop_fused_ref(x, res, gelu, elem_keep, path_keep):
     if path_keep is not None:
         v = v * path_keep.reshape([-1] + [1] * (x.dim() - 1))
     return v if res is None else res + v
+
+
+def layernorm_ref(x, w, b, eps, mode):
+    """float64 rows over the last dim.  mode 0: F.layer_norm (biased variance, eps inside the root); mode 1: w (x - mean) / (std + eps) + b
+    with the unbiased std (lib/models/vanilla_transformer_encoder.py:31-34).  w, b may be None."""
+    if mode == 0:
+        return torch.nn.functional.layer_norm(x, (x.shape[-1],), w, b, eps)
+    y = (x - x.mean(-1, keepdim=True)) / (x.std(-1, keepdim=True, unbiased=True) + eps)
+    if w is not None:
+        y = w * y
+    return y if b is None else y + b
+
+
+def mgcn_ref(h0, h1, adj, M, bias):
+    """include/gator_train.h: out = diag(adj) (M . h0) + (adj . (1 - I)) @ (M . h1) + bias; h0, h1 [B,J,C], adj [J,J], M [J,C], bias [C]"""
+    eye = torch.eye(adj.shape[0], dtype=adj.dtype)
+    return torch.diagonal(adj).reshape(1, -1, 1) * (M * h0) + (adj * (1.0 - eye)) @ (M * h1) + bias
+
+
+def adam_step_ref(p, g, m, v, lr, b1, b2, eps, t):
+    """One step of torch.optim.Adam's rule (no weight decay, no amsgrad) at step t >= 1 -> (p, m, v), float64"""
+    m = b1 * m + (1.0 - b1) * g
+    v = b2 * v + (1.0 - b2) * g * g
+    bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+    return p - (lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + eps), m, v
+
+
+def close_bound(ref64, tol=2e-5, noise32=None, scale=None):
+    """(bound, scale) exactly as check_close forms them, for a test that must also cap the bound (the noise term must not make it vacuous)"""
+    ref64 = ref64.detach().double()
+    if scale is None:
+        scale = max(1e-30, float(ref64.abs().max())) if ref64.numel() else 1.0
+    bound = tol * scale
+    if noise32 is not None:
+        bound += 4.0 * float((noise32.detach().double() - ref64).abs().max())
+    return bound, scale
 
 
 def check_close(name, ours, ref64, tol=2e-5, noise32=None, verbose=True, scale=None):
