@@ -68,10 +68,30 @@ def hop_path_bias(sd, c, dtype, p='pose_lifter.get_hop_path_encoding.'):
     return spb + eb * spatial                                       # [H,J,J]
 
 
-def gat_forward(sd, c, pose2d, dtype=torch.float32, taps=None, p='pose_lifter.'):
+class DropRates:
+    """Dropout / DropPath probabilities of the reference in .train(), by the line that sets them.  Any object with these eight
+    attributes may be passed as `rates` (a test with other values); `gat_path` has one entry per GAT block."""
+
+    def __init__(self):
+        self.gat_attn = 0.4                      # lib/models/GAT.py:47 attn_drop_rate -> :119 attn_drop -> modules.py:117 (on the softmax, :133)
+        self.gat_proj = 0.4                      # GAT.py:47 drop_rate -> :119 drop -> GAT.py:23 proj_drop -> modules.py:119,137
+        self.gat_mlp = 0.1                       # modules.py:180 (GAT.py:28 passes none), used twice :192,194
+        self.gat_path = [x.item() for x in torch.linspace(0, 0.2, 6)]      # GAT.py:47,114; GAT.py:25: nn.Identity where it is 0
+        self.mdr_attn = 0.2                      # lib/models/MDR.py:49 attn_drop -> :30,42
+        self.mdr_drop = 0.2                      # MDR.py:49 drop -> :55 proj_drop (:32,45) and :62 timm Mlp drop (after act and after fc2)
+        self.mdr_path = 0.2                      # MDR.py:50,57, used twice :66,68
+        self.mdr_self = 0.1                      # MDR.py:97 MultiHeadedAttention dropout (vanilla_transformer_encoder.py:80,45) and MDR.py:76,107 (:143,148,153)
+
+
+def gat_forward(sd, c, pose2d, dtype=torch.float32, taps=None, p='pose_lifter.', drop=None, rates=None):
     """GAT.forward lib/models/GAT.py:133-152 with GATBlock :33-43 and the modules it calls
     (lib/models/backbones/modules.py: GraphLinear :49-50, Attention :121-138, MGCN :243-255,
-    X_Feat :158-177, MLP :188-196).  pose2d [B,J,2] -> (x_out [B,3J] mm, feat [B,J,128])."""
+    X_Feat :158-177, MLP :188-196).  pose2d [B,J,2] -> (x_out [B,3J] mm, feat [B,J,128]).
+    `drop(site, x, rate, per_sample=False) -> x * keep` is called at the reference's dropout / DropPath sites of .train(), in its
+    call order, with the reference's qualified module name as `site` (`rates`: a DropRates, the reference's by default); with
+    drop = None (eval, or training with every probability at 0) nothing is called."""
+    if drop is not None and rates is None:
+        rates = DropRates()
     g = lambda k: sd[p + k].to(dtype)
     B, J, H = pose2d.shape[0], c.J, NUM_HEADS
     x = pose2d.to(dtype).reshape(B, J, 2).permute(0, 2, 1)                          # [B,2,J]
@@ -103,8 +123,12 @@ def gat_forward(sd, c, pose2d, dtype=torch.float32, taps=None, p='pose_lifter.')
         att = (q @ k.transpose(-2, -1)) * ((C // H) ** -0.5)
         att = att + bias.expand(B, -1, -1, -1)
         att = att.softmax(dim=-1)
+        if drop is not None:
+            att = drop(p + b + 'attn.attn_drop', att, rates.gat_attn)                       # modules.py:133
         a = (att @ v).transpose(1, 2).reshape(B, J, C)
         a = F.linear(a, g(b + 'attn.proj.weight'), g(b + 'attn.proj.bias'))
+        if drop is not None:
+            a = drop(p + b + 'attn.proj_drop', a, rates.gat_proj)                           # modules.py:137
         # MGCN
         W = g(b + 'gcn.W')
         h0 = torch.matmul(y, W[0])
@@ -114,6 +138,8 @@ def gat_forward(sd, c, pose2d, dtype=torch.float32, taps=None, p='pose_lifter.')
         M = g(b + 'gcn.M')
         gout = torch.matmul(adj * E, M * h0) + torch.matmul(adj * (1 - E), M * h1) + g(b + 'gcn.bias').view(1, 1, -1)
         s = a + gout
+        if drop is not None:
+            s = drop(p + b + 'drop_path', s, rates.gat_path[i], True)                       # GAT.py:38
         # X_Feat
         f0 = torch.bmm(m1.expand(B, -1, -1), F.linear(s, g(b + 'x_feat.linears.0.weight'), g(b + 'x_feat.linears.0.bias')))
         f1 = torch.bmm(m2.expand(B, -1, -1), F.linear(s, g(b + 'x_feat.linears.1.weight'), g(b + 'x_feat.linears.1.bias')))
@@ -122,7 +148,12 @@ def gat_forward(sd, c, pose2d, dtype=torch.float32, taps=None, p='pose_lifter.')
         # MLP
         y2 = F.layer_norm(x, (C,), g(b + 'norm2.weight'), g(b + 'norm2.bias'), 1e-5)
         hdn = F.gelu(F.linear(y2, g(b + 'mlp.fc1.weight'), g(b + 'mlp.fc1.bias')))
-        x = x + F.linear(hdn, g(b + 'mlp.fc2.weight'), g(b + 'mlp.fc2.bias'))
+        if drop is None:
+            x = x + F.linear(hdn, g(b + 'mlp.fc2.weight'), g(b + 'mlp.fc2.bias'))
+        else:
+            hdn = drop(p + b + 'mlp.dropout', hdn, rates.gat_mlp)                           # modules.py:192
+            y2 = drop(p + b + 'mlp.dropout', F.linear(hdn, g(b + 'mlp.fc2.weight'), g(b + 'mlp.fc2.bias')), rates.gat_mlp)   # :194
+            x = x + drop(p + b + 'drop_path', y2, rates.gat_path[i], True)                  # GAT.py:42
         if taps is not None:
             taps['gat_block%d' % i] = x
     x = F.layer_norm(x, (C,), g('norm.weight'), g('norm.bias'), 1e-5)
@@ -144,10 +175,14 @@ def _custom_ln(x, a2, b2, eps=1e-6):
     return a2 * (x - mean) / (std + eps) + b2
 
 
-def mdr_forward(sd, c, pc, dtype=torch.float32, taps=None, p='pose2mesh.', train=False):
+def mdr_forward(sd, c, pc, dtype=torch.float32, taps=None, p='pose2mesh.', train=False, drop=None, rates=None):
     """MDR.forward lib/models/MDR.py:124-170 (CrossAttentionBlock :64-69, CrossAttention :34-46,
     MultiHeadedAttention lib/models/vanilla_transformer_encoder.py:82-94, attention :36-46).
-    pc [B,J,2+3+128] -> vertices [B,6890,3] (metres)."""
+    pc [B,J,2+3+128] -> vertices [B,6890,3] (metres).  `drop` / `rates` as in gat_forward; used with train=True only."""
+    if not train:
+        drop = None
+    if drop is not None and rates is None:
+        rates = DropRates()
     g = lambda k: sd[p + k].to(dtype)
     B, J = pc.shape[0], c.J
     pc = pc.to(dtype)
@@ -170,11 +205,22 @@ def mdr_forward(sd, c, pc, dtype=torch.float32, taps=None, p='pose2mesh.', train
         k = F.linear(fz[:, V:], g(e + 'attn.wk.weight')).reshape(B, J, Hh, d).permute(0, 2, 1, 3)
         v = F.linear(fz[:, V:], g(e + 'attn.wv.weight')).reshape(B, J, Hh, d).permute(0, 2, 1, 3)
         att = ((q @ k.transpose(-2, -1)) * (d ** -0.5)).softmax(dim=-1)
+        if drop is not None:
+            att = drop(p + e + 'attn.attn_drop', att, rates.mdr_attn)                       # MDR.py:42
         o = (att @ v).transpose(1, 2).reshape(B, V, E)
-        vf = vf + F.linear(o, g(e + 'attn.proj.weight'), g(e + 'attn.proj.bias'))
+        if drop is None:
+            vf = vf + F.linear(o, g(e + 'attn.proj.weight'), g(e + 'attn.proj.bias'))
+        else:
+            o = drop(p + e + 'attn.proj_drop', F.linear(o, g(e + 'attn.proj.weight'), g(e + 'attn.proj.bias')), rates.mdr_drop)   # MDR.py:45
+            vf = vf + drop(p + e + 'drop_path', o, rates.mdr_path, True)                    # MDR.py:66
         y = F.layer_norm(vf, (E,), g(e + 'norm2.weight'), g(e + 'norm2.bias'), 1e-5)
-        vf = vf + F.linear(F.gelu(F.linear(y, g(e + 'mlp.fc1.weight'), g(e + 'mlp.fc1.bias'))),
-                           g(e + 'mlp.fc2.weight'), g(e + 'mlp.fc2.bias'))
+        if drop is None:
+            vf = vf + F.linear(F.gelu(F.linear(y, g(e + 'mlp.fc1.weight'), g(e + 'mlp.fc1.bias'))),
+                               g(e + 'mlp.fc2.weight'), g(e + 'mlp.fc2.bias'))
+        else:                                                                               # timm Mlp: drop after the activation and after fc2
+            hdn = drop(p + e + 'mlp.drop', F.gelu(F.linear(y, g(e + 'mlp.fc1.weight'), g(e + 'mlp.fc1.bias'))), rates.mdr_drop)
+            y = drop(p + e + 'mlp.drop', F.linear(hdn, g(e + 'mlp.fc2.weight'), g(e + 'mlp.fc2.bias')), rates.mdr_drop)
+            vf = vf + drop(p + e + 'drop_path', y, rates.mdr_path, True)                    # MDR.py:68
         if taps is not None:
             taps['mdr_cross%d' % li] = vf
         vf = _custom_ln(vf, g('norm%s.a_2' % sfx), g('norm%s.b_2' % sfx))
@@ -185,8 +231,13 @@ def mdr_forward(sd, c, pc, dtype=torch.float32, taps=None, p='pose2mesh.', train
         pa = F.softmax(sc, dim=-1)
         if KEEP_ATTENTION_MAPS:
             _ATTN_KEPT[li] = pa
+        if drop is not None:
+            pa = drop(p + 'selfatt%s.dropout' % sfx, pa, rates.mdr_self)                    # vanilla_transformer_encoder.py:45
         xo = torch.matmul(pa, vv).transpose(1, 2).contiguous().view(B, -1, E)
-        vf = vf + F.linear(xo, g(sa + '3.weight'), g(sa + '3.bias'))
+        if drop is None:
+            vf = vf + F.linear(xo, g(sa + '3.weight'), g(sa + '3.bias'))
+        else:
+            vf = vf + drop(p + 'dropout', F.linear(xo, g(sa + '3.weight'), g(sa + '3.bias')), rates.mdr_self)   # MDR.py:143,148,153
         if taps is not None:
             taps['mdr_lbf%d' % li] = vf
     ac = F.linear(vf, g('motion_linear.weight'), g('motion_linear.bias'))
@@ -229,14 +280,15 @@ def gator_forward(sd, c, pose2d, dtype=torch.float32, taps=None):
 
 # ---- training row: the differentiable forward and the losses, for torch-CPU autograd as the gradient oracle ----
 
-def gator_forward_train(sd, c, pose2d, dtype=torch.float64):
-    """GATOR.forward in .train() mode with every dropout / DropPath probability at 0 (the reference's RNG stream is not
-    reproducible elsewhere): differs from eval only in BatchNorm1d using batch statistics.  Differentiable w.r.t. sd tensors."""
+def gator_forward_train(sd, c, pose2d, dtype=torch.float64, drop=None, rates=None):
+    """GATOR.forward in .train() mode.  drop = None: every dropout / DropPath probability at 0, which differs from eval only in
+    BatchNorm1d using batch statistics.  With `drop` (see gat_forward) the masks come from the caller - the reference's own RNG
+    stream is not reproducible elsewhere, a host Philox is (tests/train_refs.py::DropSites).  Differentiable w.r.t. sd tensors."""
     pose2d = pose2d.to(dtype)
-    x_out, feat = gat_forward(sd, c, pose2d.reshape(len(pose2d), -1), dtype)
+    x_out, feat = gat_forward(sd, c, pose2d.reshape(len(pose2d), -1), dtype, drop=drop, rates=rates)
     pose3d = x_out.reshape(-1, c.J, 3)
     pc = torch.cat((pose2d, pose3d / 1000, feat), dim=2)
-    return mdr_forward(sd, c, pc, dtype, train=True), pose3d
+    return mdr_forward(sd, c, pc, dtype, train=True, drop=drop, rates=rates), pose3d
 
 
 def coord_loss(pred, target, valid):

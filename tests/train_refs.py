@@ -1,5 +1,6 @@
 """Host references for the training-row tests: a numpy Philox4x32 (Salmon et al., SC'11 / Random123) that is checked against the
-published known-answer vectors in tests/test_host_train.py, the keep mask include/gator_train.h documents for gator_t_dropout, and
+published known-answer vectors in tests/test_host_train.py, the keep mask include/gator_train.h documents for gator_t_dropout, the
+provider of those masks to the oracle's and the recorded reference's dropout sites (DropSites), and
 float64 torch-CPU forms of the fused dropout-on operations built on that mask, of both LayerNorm modes, the MGCN layer and one Adam step
 (each checked on the host in tests/test_host_train.py), the error criterion the new GPU tests share, and the per-term quantities of the
 oracle's face losses from which the kink margins are measured.  Nothing here calls the library under test."""
@@ -45,12 +46,71 @@ def keep_mask(seed, offset, n, rate, step=0, rounds=DEVICE_ROUNDS):
     return (words >= np.uint32(keep_threshold(rate))).astype(np.uint8)
 
 
-def keep_factor(seed, offset, shape, rate):
+def keep_factor(seed, offset, shape, rate, step=0):
     """float64 torch tensor of `shape`: keep / (1 - rate) at the flat index of a contiguous tensor (ones when rate == 0)"""
     n = int(np.prod(shape))
     if rate <= 0.0:
         return torch.ones(shape, dtype=torch.float64)
-    return torch.from_numpy(keep_mask(seed, offset, n, rate).astype(np.float64) / (1.0 - rate)).reshape(shape)
+    return torch.from_numpy(keep_mask(seed, offset, n, rate, step).astype(np.float64) / (1.0 - rate)).reshape(shape)
+
+
+class DropSites:
+    """The `drop` argument of the oracle's training forward (oracle/gator_oracle.py), and the forward hook of the recorded reference
+    step (tools/gen_golden.py::train_drop_golden): every call with rate > 0 takes the next Philox offset, starting at `first_offset`,
+    in the step word `step`, and multiplies by the host keep factor - per element at the flat index of the contiguous tensor
+    (nn.Dropout), or one decision per sample broadcast over it (timm DropPath: shape (B, 1, ...), kept samples / (1 - rate)).  A call
+    with rate == 0 draws nothing.  `log` holds one (site, kind, rate, shape, offset) per draw; `next_offset` is where the following
+    step continues when the stream runs on."""
+
+    def __init__(self, seed, first_offset=1, step=0):
+        self.seed, self.next_offset, self.step, self.log = int(seed), int(first_offset), int(step), []
+
+    def factor(self, site, shape, rate, per_sample=False):
+        """float64 keep factor of one draw, broadcastable to `shape`; None when the site draws nothing"""
+        rate = float(rate)
+        if rate <= 0.0:
+            return None
+        shape = tuple(int(d) for d in shape)
+        offset, self.next_offset = self.next_offset, self.next_offset + 1
+        self.log.append((str(site), 'path' if per_sample else 'element', rate, shape, offset))
+        if per_sample:
+            keep = keep_mask(self.seed, offset, shape[0], rate, self.step).astype(np.float64) / (1.0 - rate)
+            return torch.from_numpy(keep).reshape((shape[0],) + (1,) * (len(shape) - 1))
+        return keep_factor(self.seed, offset, shape, rate, self.step)
+
+    def __call__(self, site, x, rate, per_sample=False):
+        f = self.factor(site, x.shape, rate, per_sample)
+        return x if f is None else x * f.to(x.dtype)
+
+
+PATH_FAMILIES = ('gat_attn_mgcn', 'gat_mlp', 'mdr_cross', 'mdr_mlp')
+
+
+def path_families(log):
+    """{family: [(rate, offset), ...]} of the per-sample draws of a DropSites log.  A block's DropPath module is called twice per
+    forward (lib/models/GAT.py:38,42, MDR.py:66,68): its 1st, 3rd, ... call in the log is the attention branch (GAT: attention +
+    MGCN; MDR: cross-attention), its 2nd, 4th, ... the MLP branch."""
+    fam = {f: [] for f in PATH_FAMILIES}
+    seen = {}
+    for site, kind, rate, shape, offset in log:
+        if kind != 'path':
+            continue
+        n = seen[site] = seen.get(site, 0) + 1
+        gat = '.blocks.' in '.' + site                                  # GATBlock lives in GAT.blocks; CrossAttentionBlock is MDR.encoder*
+        fam[('gat_attn_mgcn' if gat else 'mdr_cross') if n % 2 else ('gat_mlp' if gat else 'mdr_mlp')].append((rate, offset))
+    return fam
+
+
+def live_path_families(seed, log, B, step=0):
+    """The families of path_families(log) in which at least one site keeps one of the B samples and drops another: masks under
+    which per-sample DropPath differs from a per-batch or per-element decision and from none at all"""
+    live = set()
+    for f, draws in path_families(log).items():
+        for rate, offset in draws:
+            m = keep_mask(seed, offset, B, rate, step)
+            if 0 < int(m.sum()) < B:
+                live.add(f)
+    return live
 
 
 def attention_ref(q, k, v, heads, scale, keep):

@@ -4,7 +4,7 @@ mounted read-only at /root/reference) on CPU with import shims.  Dev-container o
 never travels to the GPU box; only the small data fixtures written here do.
 
 Usage:  python tools/gen_golden.py            (re-creates tests/golden/*.npz)
-        python tools/gen_golden.py camfit     (one section only: base, scale, train, rigid, preprocess, camfit)
+        python tools/gen_golden.py camfit     (one section only: base, scale, train, train_drop, rigid, preprocess, camfit)
 
 Shims: timm DropPath/Mlp stubs, easydict stub, a pre-seeded core.config.cfg (the real
 one mkdirs under the read-only tree at import), funcs_utils stub (imports cv2/matplotlib), a 3-point
@@ -51,6 +51,7 @@ def install_shims(scratch, alpha):
     class DropPath(nn.Module):
         def __init__(self, p=0.):
             super().__init__()
+            self.drop_prob = p                              # kept for train_drop_golden's hook; the forward stays the identity
 
         def forward(self, x):
             return x
@@ -236,6 +237,22 @@ def train_golden(name, J, alpha, seed, B=4):
     is the identity stub) - the reference's RNG stream cannot be reproduced elsewhere - so BatchNorm1d runs on batch statistics;
     loss = lib/core/base.py:137-148 incl. the edge term, criteria = lib/core/loss.py get_loss(faces) loaded from its file.
     Stores loss parts and, per parameter, the gradient's max / norm and 48 fixed entries, from the fp32 run and an fp64 run."""
+    _train_recording('train_' + name, J, alpha, seed, B, None)
+
+
+def train_drop_golden(name, J, alpha, seed, mask_seed, B=4):
+    """train_golden with the reference's dropout and DropPath ON, the masks drawn on the host: the reference modules stay as they
+    are, every nn.Dropout gets p = 0 after its value is remembered, the DropPath stub is the identity with its drop_prob stored,
+    and a forward hook on each of them multiplies the module's output by the keep factor of tests/train_refs.py::DropSites - in
+    call order the next Philox offset from 1 on, step word 0; nn.Dropout per element at the flat index of the contiguous output,
+    DropPath one decision per sample / (1 - p) (timm's).  nn.Identity (block 0's DropPath) and p == 0 draw nothing.  The fp32 and
+    the fp64 run get the same masks.  `mask_seed` is the first candidate: the seed used and recorded is the first one from there
+    on whose masks are not inert (train_refs.live_path_families: each of the four DropPath families has a site that keeps one
+    sample and drops another), judged from the host masks alone.  Adds `mask_seed` and the site log to what train_golden stores."""
+    _train_recording('train_drop_' + name, J, alpha, seed, B, mask_seed)
+
+
+def _train_recording(out_name, J, alpha, seed, B, mask_seed):
     import importlib.util
     import scipy.sparse as sps
     scratch = tempfile.mkdtemp(prefix='gator_golden_')
@@ -262,16 +279,42 @@ def train_golden(name, J, alpha, seed, B=4):
     sd.update({k: torch.from_numpy(v) for k, v in new.items()})
     model.load_state_dict(sd)
     model.train()
-    for m in model.modules():
+    remembered = {}
+    for qual, m in model.named_modules():
         if isinstance(m, nn.Dropout):
+            remembered[qual] = (m, float(m.p), False)
             m.p = 0.0
+        elif isinstance(m, sys.modules['timm.models.layers'].DropPath):
+            remembered[qual] = (m, float(m.drop_prob), True)
+    sites = {'cur': None}
+    if mask_seed is not None:
+        from tests.train_refs import DropSites, live_path_families
+
+        def make_hook(qual, p, per_sample):
+            def hook(mod, inputs, out):
+                f = sites['cur'].factor(qual, out.shape, p, per_sample)
+                return None if f is None else out * f.to(out.dtype)
+            return hook
+
+        for qual, (m, p, per_sample) in remembered.items():
+            m.register_forward_hook(make_hook(qual, p, per_sample))
     faces = synthetic.synthetic_faces(seed)
     jreg_t = synthetic.load_j_regressors()['h36m'].astype(np.float32)          # target_joint_set regressor (base.py:104)
     pose2d = synthetic.synthetic_pose2d(B, J, seed + 3)
     tg = synthetic.training_targets(B, J, base, jreg_t, seed)
     crit = ref_loss.get_loss(faces=faces)
 
+    if mask_seed is not None:
+        sites['cur'] = DropSites(mask_seed)                 # which sites draw, in which order, does not depend on the seed
+        with torch.no_grad():
+            model(torch.from_numpy(pose2d))
+        order = sites['cur'].log
+        while len(live_path_families(mask_seed, order, B)) < 4:
+            mask_seed += 1
+
     def step(mdl, dt):
+        if mask_seed is not None:
+            sites['cur'] = DropSites(mask_seed)
         t = {k: torch.from_numpy(v).to(dt) for k, v in tg.items()}
         mdl.zero_grad()
         pred_mesh, lift_pose = mdl(torch.from_numpy(pose2d).to(dt))
@@ -288,6 +331,7 @@ def train_golden(name, J, alpha, seed, B=4):
         return parts, grads, pred_mesh.detach(), lift_pose.detach()
 
     parts32, g32, mesh32, _ = step(model, torch.float32)
+    log32 = sites['cur'].log if mask_seed is not None else None
     m64 = model.double()
     for blk in m64.pose_lifter.blocks:
         blk.adj = blk.adj.double()
@@ -313,10 +357,20 @@ def train_golden(name, J, alpha, seed, B=4):
         gmax.append(np.abs(a64).max()); gnorm.append(np.sqrt((a64 ** 2).sum())); noise.append(np.abs(a32 - a64).max())
     out.update(probe_idx=np.stack(probe_idx), grad_f64=np.stack(probe64), grad_f32=np.stack(probe32), grad_absmax=np.array(gmax),
                grad_norm=np.array(gnorm), ref32_minus_f64_max=np.array(noise))
-    np.savez(os.path.join(OUT, 'train_' + name + '.npz'), **out)
+    if mask_seed is not None:
+        log = sites['cur'].log
+        assert log == log32 == order
+        shapes = np.full((len(log), 4), -1, np.int64)
+        for i, e in enumerate(log):
+            shapes[i, :len(e[3])] = e[3]
+        out.update(mask_seed=np.int64(mask_seed), site_name=np.array([e[0] for e in log]), site_kind=np.array([e[1] for e in log]),
+                   site_p=np.array([e[2] for e in log], np.float64), site_shape=shapes, site_offset=np.array([e[4] for e in log], np.int64))
+        print('%s: mask seed %d, %d draws (%d per sample), live DropPath families %s'
+              % (out_name, mask_seed, len(log), sum(e[1] == 'path' for e in log), sorted(live_path_families(mask_seed, log, B))))
+    np.savez(os.path.join(OUT, out_name + '.npz'), **out)
     rel = np.array(noise) / np.maximum(np.array(gmax), 1e-300)
-    print('train_%s: loss %.6f (fp32 %.6f) parts %s; %d parameter tensors, ref fp32-vs-fp64 gradient error / max|g|: median %.1e max %.1e'
-          % (name, parts64[-1], parts32[-1], parts64[:5].round(5).tolist(), len(names), np.median(rel), rel.max()))
+    print('%s: loss %.6f (fp32 %.6f) parts %s; %d parameter tensors, ref fp32-vs-fp64 gradient error / max|g|: median %.1e max %.1e'
+          % (out_name, parts64[-1], parts32[-1], parts64[:5].round(5).tolist(), len(names), np.median(rel), rel.max()))
     os.chdir(REPO)
 
 
@@ -553,6 +607,9 @@ if __name__ == '__main__':
     if not only or 'train' in only:
         train_golden('h36m17_bn', 17, False, seed=0)
         train_golden('coco19_alpha', 19, True, seed=100)
+    if not only or 'train_drop' in only:
+        train_drop_golden('h36m17_bn', 17, False, seed=0, mask_seed=2024)
+        train_drop_golden('coco19_alpha', 19, True, seed=100, mask_seed=2025)
     if not only or 'rigid' in only:
         rigid_align_golden()
     if not only or 'preprocess' in only:
