@@ -58,7 +58,7 @@ struct FusedOptions {
     bool mdr_ends = false;              // GATOR_MDR_ENDS (set): the last persistent launch prints when its workgroups started and ended
 };
 
-constexpr int kCtrError = 8, kCtrDone = 32;      // words of a persistent MDR launch's counter block (mdr_fused.hip)
+constexpr int kCtrError = 8, kCtrDone = 32;      // words of a persistent MDR launch's counter block (mdr_fused.hip: k_mdr_persist; read back by the head kernels, mdr_head.hip)
 // chunk plan of a forward of B samples in nch launches: the first B % nch chunks have one sample more.  -> (chunk, first sample, size)
 // of sample b, and the word offset of a chunk's counter block
 struct MdrChunkPlan {

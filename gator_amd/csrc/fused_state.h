@@ -148,7 +148,11 @@ int pack_upsample_x2(const float* up_w, void* dst, float* unscale, void* stream)
 int launch_pack_vc_x2(const float* vc, int B, void* vcp2, void* stream);
 int launch_upsample_x2(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream, bool with_joints, bool w1);
 int launch_upsample_any(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const RegressorPlan& r, int B, float* verts, void* stream);      // fp32-input MFMA | bf16 x 3 | fp16 x 2 (the bf16 kernel: fused_api.hip)
-// mdr_fused.hip: the joint tokens (pc, the MDR entry point; else x_out and pose2d of the whole forward), the layers and the head, as p says
+// mdr_fused.hip: the joint tokens (pc, the MDR entry point; else x_out and pose2d of the whole forward), the layers and the head, as p says; the first
+// and the last through mdr_head.hip's launchers below
 int launch_mdr(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pc, int B, void* stream, const float* x_out, const float* pose2d);
+// mdr_head.hip: what launch_mdr runs in front of the layers (the MDR entry point's joint tokens) and behind them (the head kernel p.head)
+int launch_mdr_joint(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pc, int B, void* stream);
+int launch_mdr_head(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, int B, void* stream, const float* pose2d);
 
 }  // namespace gator

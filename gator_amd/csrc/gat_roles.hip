@@ -785,7 +785,7 @@ __device__ __forceinline__ void gat8_tail(const Gat8Tail& tl, const float* pose2
     const f32x16 d0 = jf[0] - mean, d1 = jf[1] - mean;
     const float rstd = 1.0f / sqrtf(rs(d0 * d0, d1 * d1) * (1.0f / 64.0f) + 1e-5f);
     GAT8_TSTAMP(5);
-    // per LBF layer: k = wk(LN1(jf)), v = wv(LN1(jf)) as MFMA operand tiles (two fp16 planes of 16 x value: mdr_fused.hip, cross_attention_head_x2)
+    // per LBF layer: k = wk(LN1(jf)), v = wv(LN1(jf)) as MFMA operand tiles (two fp16 planes of 16 x value: mdr_ops.h, cross_attention_head / JointX2)
     const f32x16 fz0 = d0 * rstd * chanvec_lds(VJ, TVJ_N1W + 64 * li, h) + chanvec_lds(VJ, TVJ_N1B + 64 * li, h);
     const f32x16 fz1 = d1 * rstd * chanvec_lds(VJ, TVJ_N1W + 64 * li + 32, h) + chanvec_lds(VJ, TVJ_N1B + 64 * li + 32, h);
     const X2 z0 = x2_split(fz0 * 16.0f), z1 = x2_split(fz1 * 16.0f);

@@ -51,7 +51,7 @@ struct JointTailArgs {
     const float *jf5, *jf_p, *jf_b, *posj_T;       // get_joint_feature: columns 0..4 as [5][64], columns 5..132 packed [2][4], bias
     const float *j_n1w[3], *j_n1b[3], *j_wk_p[3], *j_wv_p[3];
     int B, J;
-    int x2;                       // K/V tiles as two fp16 planes of 16 x value (mdr_fused.hip: cross_attention_head_x2)
+    int x2;                       // K/V tiles as two fp16 planes of 16 x value (mdr_ops.h: cross_attention_head, JointX2)
 };
 
 __device__ __forceinline__ float row_sum32x2(const f32x16& a, const f32x16& b) {

@@ -84,7 +84,7 @@ enum TapId { TAP_FEAT = 0, TAP_MDR_LBF2, TAP_VERT431, TAP_GAT_BLOCKS, TAP_COUNT 
 struct Tap { const float* p = nullptr; int64_t n = 0; };
 
 // Sticky device status of a ctx: host-mapped words written by kernels, read by the host at the next API call / gator_device_status.  Word r
-// (1 .. DEV_REASONS - 1) is set to 1 when a kernel reports reason r (mdr_fused.hip: head_report); the host takes them as a mask of (1 << r).
+// (1 .. DEV_REASONS - 1) is set to 1 when a kernel reports reason r (mdr_head.hip: head_report); the host takes them as a mask of (1 << r).
 enum DeviceStatus { DEV_OK = 0, DEV_PERSIST_INCOMPLETE = 1, DEV_NONFINITE = 2, DEV_INPUT_NONFINITE = 3, DEV_REASONS = 4 };
 
 struct FusedState;   // packed weights + workspace of the fused path (fused_*.hip)

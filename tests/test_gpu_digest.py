@@ -1,7 +1,9 @@
 """Bit-identity of the fp32 forward against recorded digests (tests/golden/fp32_digests.json, written by tools/ab_digest.py on a GPU box).
 Round 4 made several changes that were meant to be schedules only and checked them by hand with tools/ab_digest.py; this is that check
 as a test: per-sample kernel and sample-tiled kernel, persistent and four-launch MDR forms (B = 5 / 256 / 700), both golden variants.
-A change that is meant to move bits re-records the file (and re-runs the error budget); any other change must leave it green."""
+A change that is meant to move bits re-records the file (and re-runs the error budget); any other change must leave it green.
+tests/golden/mdr_form_digests.json does the same for the MDR kernels' other forms (tools/ab_digest.py: form_digests): exact split, fp32-input
+MFMA, config 3 and the whole-head kernels, four-launch and persistent, at B = 11."""
 import json
 import os
 
@@ -9,6 +11,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'fp32_digests.json')
+FORMS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'mdr_form_digests.json')
 
 
 def test_fp32_forward_digests_match_the_recorded_build():
@@ -21,6 +24,22 @@ def test_fp32_forward_digests_match_the_recorded_build():
     got = digests()
     bad = {k: (got.get(k), h) for k, h in want.items() if got.get(k) != h}
     assert not bad, 'outputs moved bits against tests/golden/fp32_digests.json: %s' % bad
+
+
+@pytest.mark.parametrize('form', ['default', 'x3_1', 'x3_0', 'bf16', 'head_partials0'])
+def test_mdr_form_digests_match_the_recorded_build(form):
+    """Every MDR form bit for bit: GATOR_MDR_PERSIST = 0 and 1, both golden variants, the whole forward and the MDR entry point on a random
+    pose_combine (k_mdr_joint, both K/V tile forms), B = 11; head_partials0 also at B = 513, where the plan picks the rolled k_mdr_head."""
+    if not os.path.exists(FORMS_PATH):
+        pytest.skip('no recorded digests (tools/ab_digest.py --forms --write tests/golden/mdr_form_digests.json on a GPU box)')
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tools.ab_digest import form_digests
+    want = {k: h for k, h in json.load(open(FORMS_PATH))['digests'].items() if k.startswith(form + ' ')}
+    got = form_digests([form])
+    assert len(want) >= 8 and set(got) == set(want)
+    bad = {k: (got.get(k), h) for k, h in want.items() if got.get(k) != h}
+    assert not bad, 'outputs moved bits against tests/golden/mdr_form_digests.json: %s' % bad
 
 
 def test_byte_lo_weight_stream_equals_the_three_plane_stream_bit_for_bit(monkeypatch):

@@ -265,7 +265,7 @@ def _forward(key, x, precision='f32'):
 @pytest.mark.parametrize('B', (1, 33, 129, 257))
 @pytest.mark.parametrize('form', ('fp32', 'x3', 'x2'))
 def test_forward_packer(params, form, B):
-    """In a full forward the MDR head writes the packed operand itself (mdr_fused.hip head_store); behind it runs the same kernel as
+    """In a full forward the MDR head writes the packed operand itself (mdr_head.hip head_store); behind it runs the same kernel as
     behind k_pack_vc*.  The head's packed values are the stage packers' by construction (same scale, same splits), so the vertices are
     bit-equal to the stage entry on the tapped coarse vertices, and hold bound (3) against their product."""
     verts, _, tap = _forward(form, _pose(B))
