@@ -31,6 +31,10 @@ class SmplModel(ctypes.Structure):              # include/gator_hip.h: gator_smp
                 ('j_regressor', ctypes.c_void_p), ('parents', ctypes.c_void_p)]
 
 
+class GatorCoo(ctypes.Structure):              # include/gator_hip.h: gator_coo (device pointers)
+    _fields_ = [('row', ctypes.c_void_p), ('col', ctypes.c_void_p), ('val', ctypes.c_void_p), ('nnz', ctypes.c_int32), ('n_joint', ctypes.c_int32)]
+
+
 ABI_VERSION = 2                                 # include/gator_hip.h: GATOR_ABI_VERSION this binding was written against
 EDEVICE, EDEVICE_DEFERRED = -7, -8
 REASON_PERSIST_INCOMPLETE, REASON_NONFINITE, REASON_INPUT_NONFINITE = 1, 2, 3      # gator_status_reason
@@ -70,6 +74,7 @@ SIGNATURES = {
     'gator_preprocess_chain_f32': (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     'gator_joint_errors_f32': (_I, [_P, _P, _I, _I, _P, _I, _I, ctypes.c_float, _P, _P]),
     'gator_rigid_align_f32': (_I, [_P, _P, _I, _I, _P, _P]),
+    'gator_mesh_errors_f32': (_I, [_P, _P, _I, _I, ctypes.c_float, ctypes.c_float, ctypes.POINTER(GatorCoo), _I, ctypes.POINTER(GatorCoo), _I, _P, _I, _P, _P]),
     'gator_crop_joints_f32': (_I, [_P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
     'gator_fit_camera_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),
     'gator_smpl_create': (_I, [_P, ctypes.POINTER(_P)]),

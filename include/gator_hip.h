@@ -323,6 +323,40 @@ int gator_emulate_gather_traffic(const void* src, void* dst, int64_t bytes, int3
 int gator_joint_errors_f32(const float* pred_joints, const float* target_joints, int32_t batch, int32_t n_joint,
                            const int32_t* eval_joints, int32_t n_eval, int32_t root, float pred_scale, float* errors, void* stream);
 
+/* Whole-mesh evaluation of a batch in ONE launch: what the datasets' `evaluate` (data/PW3D/dataset.py:322-375,
+ * data/Human36M/dataset.py:515-600) and compute_both_err (data/PW3D/dataset.py:273-286, lib/core/base.py:219-223) take from the two
+ * meshes on the host.  A regressor is a sparse [n_joint, n_verts] matrix as COO in DEVICE arrays; the struct itself is read on the
+ * host at the call.  Entries may come in any order and duplicates add; a col is used as a raw vertex offset, so every col in
+ * [0, n_verts) is the caller's contract (gator_amd.eval checks it), as for gator_regress_joints_f32.
+ *   pred, target [batch, n_verts, 3], n_verts >= 3; each coordinate is multiplied by pred_scale / target_scale in float32 (1000 for
+ *   metres -> mm, lib/core/base.py:219), everything after that is fp64.
+ *   root_regressor with 1..64 joints, root in [0, n_joint): both meshes are aligned on their own regressed root joint (the 24-joint
+ *   SMPL regressor with root 0 for `evaluate`, the H36M regressor with root 0 for compute_both_err).
+ *   eval_regressor (1..64 joints) with eval_root, and eval_joints: n_eval = 3..32 joint indices (device), each in [0, n_joint), or NULL
+ *   for all joints.  No evaluation regressor: eval_regressor = NULL, or nnz = 0 with three NULL arrays.
+ *   errors [batch, 5], per sample:
+ *     0  MPJPE of the evaluation joints, each set aligned on its own eval_root           (PW3D/dataset.py:364-373)
+ *     1  PA-MPJPE of the same joints                                                     (:374-375)
+ *     2  mean error of ALL root-regressor joints after root alignment, mpjpe_smpl        (:351-353)
+ *     3  MPVPE, the mean over vertices of |(p - root_p) - (t - root_t)|                  (:356-358; compute_both_err :275,283)
+ *     4  PA-MPVPE, the mean over vertices of |c R p + tr - t| with the similarity fit of all n_verts vertices
+ *        (:360-361, which the reference leaves commented out; lib/coord_utils.py:127-149)
+ *   Columns 0 and 1 are NaN without an evaluation regressor.  A non-finite coordinate makes the columns that depend on it NaN in its
+ *   own sample; a prediction of zero variance has column 4 = NaN (c = 0 / 0, as numpy gives).  A sample's row does not depend on the
+ *   batch around it, bit for bit.
+ * Enqueues one kernel on `stream`: no allocation, no synchronisation, capturable into a graph.  GATOR_EINVAL, before any launch and
+ * with `errors` untouched: a NULL mesh / errors / root_regressor, batch <= 0, n_verts < 3, n_joint outside 1..64, a root outside its
+ * joints, nnz < 0, nnz > 0 with a NULL array, an evaluation count outside 3..32. */
+typedef struct {
+    const int32_t* row;
+    const int32_t* col;
+    const float* val;
+    int32_t nnz, n_joint;
+} gator_coo;
+int gator_mesh_errors_f32(const float* pred, const float* target, int32_t batch, int32_t n_verts, float pred_scale, float target_scale,
+                          const gator_coo* root_regressor, int32_t root, const gator_coo* eval_regressor, int32_t eval_root,
+                          const int32_t* eval_joints, int32_t n_eval, float* errors, void* stream);
+
 /* Host-side graph constants (no GPU needed).  Replace the absent Cython algos.pyx
  * (lib/models/backbones/setup.py:1-6) and lib/models/backbones/modules.py:6-29, lib/graph_utils.py:71-89. */
 int gator_floyd_warshall(const float* adj, int32_t n, int64_t* dist, int64_t* path);
