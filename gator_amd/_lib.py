@@ -81,6 +81,14 @@ SIGNATURES = {
     'gator_smpl_destroy': (_I, [_P]),
     'gator_smpl_forward_f32': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P, _P]),
     'gator_smpl_workspace': (_I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_L)]),
+    'gator_renderer_create': (_I, [_P, _I, _I, ctypes.POINTER(_P)]),
+    'gator_renderer_destroy': (_I, [_P]),
+    'gator_render_f32': (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _I, ctypes.c_float, _I, _P, _P, _P, _P]),
+    'gator_render_vertices_f32': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'gator_render_raster': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    'gator_render_resolve': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _I, ctypes.c_float, _P, _P, _P, _P]),
+    'gator_renderer_workspace': (_I, [_P, ctypes.POINTER(_L), ctypes.POINTER(_L)]),
+    'gator_renderer_set_small_box': (_I, [_P, _I]),
     'gator_comm_unique_id': (_I, [_P]),
     'gator_comm_create': (_I, [_P, _I, _I, ctypes.POINTER(_P)]),
     'gator_comm_destroy': (_I, [_P]),

@@ -5,7 +5,7 @@ camera that lays the mesh over the image.
   forward_joints' joints [B,n,3] + target --fit_camera-->  cam [B,3] (s, tx, ty), loss [B][, orig_cam [B,4]]   demo/run.py:138-157,21-39
 
 fit_camera runs the reference's 1500 Adam steps of models.project_net.OptimzeCamLayer for every sample of the batch in one launch;
-fit_mesh_to_image is the demo's whole flow, batched."""
+fit_mesh_to_image is the demo's whole flow, batched; render_fit draws its result over the frames (gator_amd.render, demo/renderer.py)."""
 import ctypes
 
 import numpy as np
@@ -91,3 +91,21 @@ def fit_mesh_to_image(model, raw_joints, joint_set, image_size, init=None, steps
     cam, loss, orig_cam = fit_camera(joints, target, init=init, steps=steps, schedule=schedule, crop_size=crop_size,
                                      n_fit=joints.shape[1], bbox=bbox, image_size=image_size)
     return {'mesh': mesh, 'pose3d': pose3d, 'joints': joints, 'cam': cam, 'orig_cam': orig_cam, 'bbox': bbox, 'loss': loss, 'valid': valid}
+
+
+def render_fit(fit, faces_or_renderer, images=None, image_size=None, colors=None):
+    """fit_mesh_to_image's dict -> the overlay images [B,H,W,3] uint8 on the device (gator_amd.render: the demo's renderer, batched).
+    faces_or_renderer: the mesh's faces [F,3] or a render.MeshRenderer to reuse (its workspace then serves every call);
+    images: [B,H,W,3] uint8 on the device to draw over, or None (black) with image_size = (width, height); colors: (3,) or [B,3]."""
+    from . import render
+    mesh, cam = fit['mesh'], fit['orig_cam']
+    if images is None and image_size is None:
+        raise ValueError('render_fit: give images or image_size = (width, height)')
+    if images is not None:
+        size = (int(images.shape[2]), int(images.shape[1]))
+        if image_size is not None and (int(image_size[0]), int(image_size[1])) != size:
+            raise ValueError('render_fit: image_size %s does not match images of %d x %d (width x height)' % (tuple(image_size), size[0], size[1]))
+    else:
+        size = (int(image_size[0]), int(image_size[1]))
+    r = faces_or_renderer if isinstance(faces_or_renderer, render.MeshRenderer) else render.MeshRenderer(faces_or_renderer, mesh.device, n_verts=mesh.shape[1])
+    return r.render(mesh, cam, background=images, color=render.DEMO_COLOR if colors is None else colors, size=size)

@@ -357,6 +357,59 @@ int gator_mesh_errors_f32(const float* pred, const float* target, int32_t batch,
                           const gator_coo* root_regressor, int32_t root, const gator_coo* eval_regressor, int32_t eval_root,
                           const int32_t* eval_joints, int32_t n_eval, float* errors, void* stream);
 
+/* The demo's mesh overlay (demo/renderer.py) on the device: a batched software rasteriser for the weak-perspective camera
+ * (gator_amd/csrc/render.hip derives the geometry; DESIGN.md "Renderer").  For a vertex (x, y, z) of the model's output and
+ * cam = (sx, sy, tx, ty):  column = (1 + sx (x + tx)) / 2 * W,  row = (1 + sy (y + ty)) / 2 * H,  depth = z (smaller is nearer, fragments
+ * outside [-1, 1] are clipped), sampled at pixel centres; rot3x3 (HOST, row major, or NULL = identity) is the reference's `rotate` /
+ * `angle, axis` matrix, applied to the mesh after its Rx(180 deg) flip as the reference applies it.
+ *
+ * gator_renderer_create: faces [n_faces,3] on the HOST.  GATOR_EINVAL with a reason for a vertex index outside [0, n_verts),
+ * n_faces < 1, n_verts < 3.  Builds the vertex-to-face lists, uploads both, and owns every allocation until gator_renderer_destroy.
+ *
+ * gator_render_f32: n_meshes meshes verts [n_meshes,n_verts,3] with cams [n_meshes,4] and colors [n_meshes,3] (linear base colour; NULL:
+ * (1, 1, 0.9)), all on the device, drawn into n_images images of H x W.  image_index [n_meshes] on the HOST names the image of each
+ * mesh: several meshes of one image share its depth buffer; NULL: mesh m alone in image m (needs n_meshes <= n_images).
+ * background [n_images,H,W,3] uint8 on the device or NULL (black).  lights: n_lights <= 4 HOST rows (lx, ly, lz, intensity), the unit
+ * direction TOWARDS the light in the model's output coordinates; shading is lin = base (ambient + (1/pi) sum_k I_k max(0, n . l_k)),
+ * out = round(255 clamp(lin^(1/2.2))) -- a documented diffuse model, not pyrender's shader.  flags: GATOR_RENDER_CULL_BACKFACES.
+ * Outputs (device, each may be NULL, not all): out_rgb [n_images,H,W,3] uint8; out_face_id [n_images,H,W] int32 = slot * n_faces + face
+ * with slot the rank of the winning mesh among the meshes of its image, -1 where empty; out_depth [n_images,H,W] f32, +Inf where empty.
+ * An image is the same bits from run to run and whatever else is in the batch (integer atomic min on (depth, id) keys).
+ * A vertex that is not finite or projects beyond +-2^20 px drops every face that touches it.  Workspace grows inside the handle (the
+ * device is synchronised when it does); a call no larger than an earlier one allocates nothing; a growth that fails leaves the handle
+ * usable for smaller calls.  image_index is read before the call returns (into a pinned block of the handle, copied on `stream`).  The
+ * calls on one handle are ordered by the caller: one stream, or events between streams.
+ * GATOR_EINVAL, before any launch: a NULL handle / verts / cams, no output, H or W outside 1..8192, n_meshes or n_images < 1,
+ * n_meshes > 65535, an image_index[m] outside [0, n_images), (most meshes in one image) * n_faces >= 2^32 (2^31 with out_face_id),
+ * more than 4 lights, a non-finite light, ambient or rot3x3 entry.
+ *
+ * The three launches alone, for callers that keep the intermediates (and for the tests):
+ *   gator_render_vertices_f32 -> xy_fixed [n_meshes,n_verts,2] int32 (24.8 fixed point, round to nearest even; INT32_MIN for a dropped
+ *                                vertex), z [n_meshes,n_verts] (without a rotation the input's z bit for bit, except that -0 becomes +0 and that z
+ *                                is NaN where x or y is not finite -- a dropped vertex), normals [n_meshes,n_verts,3] (area-weighted, unit length)
+ *   gator_render_raster       -> keys [n_images,H,W] uint64: ordered_bits(depth) << 32 | face id, all ones where empty
+ *   gator_render_resolve      -> the outputs of gator_render_f32 from those */
+#define GATOR_RENDER_CULL_BACKFACES 1
+typedef struct gator_renderer gator_renderer;
+int gator_renderer_create(const int32_t* faces, int32_t n_faces, int32_t n_verts, gator_renderer** out);
+int gator_renderer_destroy(gator_renderer* r);
+int gator_render_f32(gator_renderer* r, const float* verts, const float* cams, const float* colors, const int32_t* image_index,
+                     int32_t n_meshes, const uint8_t* background, int32_t n_images, int32_t H, int32_t W, const float* rot3x3,
+                     const float* lights, int32_t n_lights, float ambient, int32_t flags, uint8_t* out_rgb, int32_t* out_face_id,
+                     float* out_depth, void* stream);
+int gator_render_vertices_f32(gator_renderer* r, const float* verts, const float* cams, int32_t n_meshes, int32_t H, int32_t W,
+                              const float* rot3x3, int32_t* xy_fixed, float* z, float* normals, void* stream);
+int gator_render_raster(gator_renderer* r, const int32_t* xy_fixed, const float* z, const int32_t* image_index, int32_t n_meshes,
+                        int32_t n_images, int32_t H, int32_t W, int32_t flags, uint64_t* keys, void* stream);
+int gator_render_resolve(gator_renderer* r, const uint64_t* keys, const int32_t* xy_fixed, const float* normals, const float* colors,
+                         const int32_t* image_index, int32_t n_meshes, const uint8_t* background, int32_t n_images, int32_t H, int32_t W,
+                         const float* lights, int32_t n_lights, float ambient, uint8_t* out_rgb, int32_t* out_face_id, float* out_depth,
+                         void* stream);
+/* Test hook: bytes of workspace the handle holds and how many allocations it has made since create. */
+int gator_renderer_workspace(const gator_renderer* r, int64_t* bytes, int64_t* allocations);
+/* Measurement hook (tools/render_bench.py): bounding-box area in pixels up to which one lane walks a triangle alone; 0 = built-in. */
+int gator_renderer_set_small_box(gator_renderer* r, int32_t pixels);
+
 /* Host-side graph constants (no GPU needed).  Replace the absent Cython algos.pyx
  * (lib/models/backbones/setup.py:1-6) and lib/models/backbones/modules.py:6-29, lib/graph_utils.py:71-89. */
 int gator_floyd_warshall(const float* adj, int32_t n, int64_t* dist, int64_t* path);
