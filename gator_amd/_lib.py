@@ -75,6 +75,8 @@ SIGNATURES = {
     'gator_joint_errors_f32': (_I, [_P, _P, _I, _I, _P, _I, _I, ctypes.c_float, _P, _P]),
     'gator_rigid_align_f32': (_I, [_P, _P, _I, _I, _P, _P]),
     'gator_mesh_errors_f32': (_I, [_P, _P, _I, _I, ctypes.c_float, ctypes.c_float, ctypes.POINTER(GatorCoo), _I, ctypes.POINTER(GatorCoo), _I, _P, _I, _P, _P]),
+    'gator_one_euro_f32': (_I, [_P, _P, _L, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P, _P]),
+    'gator_sequence_errors': (_I, [_P, _I, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
     'gator_crop_joints_f32': (_I, [_P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
     'gator_fit_camera_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),
     'gator_smpl_create': (_I, [_P, ctypes.POINTER(_P)]),

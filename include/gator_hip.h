@@ -357,6 +357,34 @@ int gator_mesh_errors_f32(const float* pred, const float* target, int32_t batch,
                           const gator_coo* root_regressor, int32_t root, const gator_coo* eval_regressor, int32_t eval_root,
                           const int32_t* eval_joints, int32_t n_eval, float* errors, void* stream);
 
+/* The per-video, temporal part of the evaluation (data/PW3D/dataset.py:383-415, commented out there but complete; gator_amd/csrc/temporal.hip).
+ * The frames of n_videos videos lie one video after another; seg_start [n_videos + 1] (int64, DEVICE) holds each video's first frame and,
+ * last, n_frames.  It must start at 0 and increase strictly (every video has a frame): the kernels use it as raw offsets, unchecked --
+ * gator_amd.temporal builds it from checked lengths.
+ *
+ * gator_one_euro_f32: lib/smooth_utils.smooth_pose (a one-euro filter) along every channel of every video in ONE launch.
+ *   x [n_frames, n_channels] float32; out the same shape, float64 (out_f64 != 0) or float32 (the float32 rounding of the float64 value;
+ *   the state is always carried in fp64).  The recursion is lib/smooth_utils.py:27-46 step for step in fp64, t_e = dt at every step,
+ *   no contracted multiply-add: for finite inputs the float64 output equals numpy's bit for bit.  smooth_pose itself has d_cutoff = 1, dt = 1.
+ *   A non-finite input makes its own channel of its own video NaN from that frame on, as numpy does, and nothing else.
+ *
+ * gator_sequence_errors: two launches.
+ *   pred [n_frames, n_eval, 3] float64 (pred_f64 != 0, e.g. gator_one_euro_f32's output) or float32; gt the same shape, float32;
+ *   valid [n_frames] uint8 or NULL; 3 <= n_eval <= 32.  No root is subtracted: the caller passes root-aligned joints, as the reference does.
+ *   rows [n_frames, 3] float64, per frame i of a video that ends before frame e:
+ *     0  the acceleration error of the triple (i, i+1, i+2), mean over joints of |(p_i - 2 p_i+1 + p_i+2) - (g_i - 2 g_i+1 + g_i+2)|
+ *        (lib/coord_utils.py:194-222); NaN when i + 2 >= e or one of the three frames is not valid
+ *     1  mean over joints of |p_i - g_i|                                                   (:398)
+ *     2  the same after the similarity fit of p_i onto g_i                                 (:400-403, lib/coord_utils.py:127-149)
+ *   video_sums [n_videos, 6] float64: the sums of the three columns over the video's frames (column 0 over its non-NaN rows), the number
+ *   of those rows, the number of frames, 0 -- summed in a fixed order.
+ * Both enqueue on `stream` without allocation or synchronisation and use no atomics: the same input gives the same bits.
+ * GATOR_EINVAL before any launch: a NULL array, a count < 1, more videos than frames, dt <= 0, n_eval outside 3..32. */
+int gator_one_euro_f32(const float* x, const int64_t* seg_start, int64_t n_frames, int32_t n_videos, int32_t n_channels, double min_cutoff,
+                       double beta, double d_cutoff, double dt, int32_t out_f64, void* out, void* stream);
+int gator_sequence_errors(const void* pred, int32_t pred_f64, const float* gt, const uint8_t* valid, const int64_t* seg_start,
+                          int64_t n_frames, int32_t n_videos, int32_t n_eval, double* rows, double* video_sums, void* stream);
+
 /* The demo's mesh overlay (demo/renderer.py) on the device: a batched software rasteriser for the weak-perspective camera
  * (gator_amd/csrc/render.hip derives the geometry; DESIGN.md "Renderer").  For a vertex (x, y, z) of the model's output and
  * cam = (sx, sy, tx, ty):  column = (1 + sx (x + tx)) / 2 * W,  row = (1 + sy (y + ty)) / 2 * H,  depth = z (smaller is nearer, fragments
