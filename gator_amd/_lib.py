@@ -35,7 +35,19 @@ class GatorCoo(ctypes.Structure):              # include/gator_hip.h: gator_coo 
     _fields_ = [('row', ctypes.c_void_p), ('col', ctypes.c_void_p), ('val', ctypes.c_void_p), ('nnz', ctypes.c_int32), ('n_joint', ctypes.c_int32)]
 
 
-ABI_VERSION = 2                                 # include/gator_hip.h: GATOR_ABI_VERSION this binding was written against
+class CameraTargetsArgs(ctypes.Structure):     # include/gator_hip.h: gator_camera_targets_args (device pointers)
+    _fields_ = [('struct_size', ctypes.c_int32), ('batch', ctypes.c_int32), ('n_verts', ctypes.c_int32), ('n_smpl_joints', ctypes.c_int32),
+                ('root_idx', ctypes.c_int32), ('compensate_root', ctypes.c_int32), ('lift_set', ctypes.c_int32), ('n_pairs', ctypes.c_int32),
+                ('reg_h36m_n_verts', ctypes.c_int32), ('reg_coco_n_verts', ctypes.c_int32), ('fitting_thr', ctypes.c_float),
+                ('reserved', ctypes.c_int32)] + \
+        [(n, ctypes.c_void_p) for n in ('verts', 'joints', 'trans', 'cam_t', 'R', 'focal', 'princpt')] + \
+        [('reg_h36m', GatorCoo), ('reg_coco', GatorCoo)] + \
+        [(n, ctypes.c_void_p) for n in ('joint_cam', 'joint_img', 'rot_deg', 'flip', 'flip_pairs', 'mesh', 'reg_pose3d', 'lift_pose3d',
+                                        'joint_img_out', 'fit_error', 'valid')]
+
+
+LIFT_HUMAN36, LIFT_COCO = 0, 1                  # include/gator_hip.h: GATOR_LIFT_*
+ABI_VERSION = 2                                # include/gator_hip.h: GATOR_ABI_VERSION this binding was written against
 EDEVICE, EDEVICE_DEFERRED = -7, -8
 REASON_PERSIST_INCOMPLETE, REASON_NONFINITE, REASON_INPUT_NONFINITE = 1, 2, 3      # gator_status_reason
 
@@ -77,7 +89,9 @@ SIGNATURES = {
     'gator_mesh_errors_f32': (_I, [_P, _P, _I, _I, ctypes.c_float, ctypes.c_float, ctypes.POINTER(GatorCoo), _I, ctypes.POINTER(GatorCoo), _I, _P, _I, _P, _P]),
     'gator_one_euro_f32': (_I, [_P, _P, _L, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P, _P]),
     'gator_sequence_errors': (_I, [_P, _I, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
-    'gator_crop_joints_f32': (_I, [_P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
+    'gator_batch_prepare_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    'gator_camera_targets_f32': (_I, [ctypes.POINTER(CameraTargetsArgs), _P]),
+    'gator_crop_joints_f32':(_I, [_P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
     'gator_fit_camera_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),
     'gator_smpl_create': (_I, [_P, ctypes.POINTER(_P)]),
     'gator_smpl_destroy': (_I, [_P]),

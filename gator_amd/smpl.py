@@ -167,7 +167,8 @@ def targets_from_smpl(layer, pose, shape, trans, regressor_h36m, regressor_coco=
     """The un-augmented tail of the datasets' __getitem__ (data/AMASS/dataset.py:252-265,301) on the device: mesh and joints from the
     layer in mm, the H36M (and COCO + pelvis + neck) joints regressed from the mesh, everything root-relative.
     regressor_*: gator_amd.eval.JointRegressor.  -> the dict Trainer.step takes: 'mesh' [B,6890,3] in metres, 'reg_pose3d' [B,17,3]
-    and 'lift_pose3d' [B,17|19,3] in mm.  The camera-frame root rotation, augmentation and noise stay with the caller."""
+    and 'lift_pose3d' [B,17|19,3] in mm.  The camera-frame root rotation, augmentation and noise stay with the caller
+    (gator_amd.batch.camera_frame_batch builds the first two on the device)."""
     mesh, _ = get_smpl_coord(layer, pose, shape, trans)
     h36m = regressor_h36m(mesh)
     root = h36m[:, :1]

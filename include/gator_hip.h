@@ -385,6 +385,62 @@ int gator_one_euro_f32(const float* x, const int64_t* seg_start, int64_t n_frame
 int gator_sequence_errors(const void* pred, int32_t pred_f64, const float* gt, const uint8_t* valid, const int64_t* seg_start,
                           int64_t n_frames, int32_t n_videos, int32_t n_eval, double* rows, double* video_sums, void* stream);
 
+/* Camera-frame training targets: the deterministic part of the datasets' __getitem__ around the SMPL layer, for a whole batch
+ * (data/Human36M/dataset.py:254-309,339-407, data/AMASS/dataset.py:182-304; gator_amd/csrc/train_batch.hip, gator_amd.batch).  The
+ * detector noise (lib/noise_utils.py) is not part of it.  All pointers are device pointers unless said otherwise; both calls enqueue one
+ * kernel on `stream`, never allocate or synchronise, and can be captured into a graph; batch == 0 is GATOR_OK and launches nothing.
+ *
+ * gator_batch_prepare_f32, before the layer.  pose [batch, n_pose] (n_pose = 3 per joint), R [batch,3,3] row major or NULL, betas
+ * [batch, n_betas] or NULL.  pose_out = pose with joint root_idx replaced by the rotation vector of R exp(root) (Human36M:267-274,
+ * AMASS:188-196), computed in fp64 through the product's quaternion: angle in [0, pi], accurate near 0 and near pi.  A ZERO root vector
+ * is the identity (the reference divides 0 / 0 there and yields NaN); a non-finite root or R makes that sample's root NaN and nothing
+ * else.  With R == NULL the pose is copied bit for bit.  betas_out: a row with any |beta| > 3 becomes zeros (Human36M:265), any other
+ * row is copied bit for bit.  pose_out == pose and betas_out == betas are allowed.  GATOR_EINVAL: a NULL pose / pose_out, betas without
+ * betas_out, n_pose < 3 or no multiple of 3, root_idx outside the joints, batch < 0.
+ *
+ * gator_camera_targets_f32, after the layer, one workgroup per sample; fp64 throughout with one rounding per output; no atomics, a
+ * sample's outputs are the same bits whatever the batch.  In the struct below:
+ *   verts [batch, n_verts, 3], joints [batch, n_smpl_joints, 3]: the layer's outputs in metres, not translated (joints is read only with
+ *     compensate_root); trans, cam_t [batch,3] in metres, each may be NULL (= 0); R [batch,3,3] or NULL.
+ *   T = R trans + cam_t - root + R root with root = joints[root_idx] when compensate_root (Human36M:288-292), else trans + cam_t
+ *     (AMASS:205-207); mesh_cam = (verts + T) * 1000.
+ *   reg_h36m (1..64 joints), reg_coco (13..62 joints, or n_joint = 0 for none): COO over n_verts columns -- reg_*_n_verts states the
+ *     width each was built for; a column inside it is the caller's contract, as for gator_mesh_errors_f32.  The coco set gets its
+ *     pelvis (mean of joints 11, 12) and neck (mean of 5, 6) appended.  Jh = reg_h36m.n_joint; Jl = Jh (GATOR_LIFT_HUMAN36) or
+ *     reg_coco.n_joint + 2 (GATOR_LIFT_COCO).
+ *   focal, princpt [batch,2]: cam2pixel, x = X / Z * fx + cx (lib/coord_utils.py:104-109); Z = 0 gives the IEEE result.
+ *   joint_cam [batch,Jh,3] in mm and joint_img [batch,Jh,2] or NULL: the dataset's own joints (Human3.6M has them).
+ *   rot_deg [batch] float, flip [batch] int32, each may be NULL; flip_pairs [n_pairs,2] int32 (a pair outside the lift set is skipped).
+ *   Outputs: mesh [batch,n_verts,3] = (mesh_cam - root_h) / 1000 with root_h = joint_cam[0] when given, else the regressed h36m[0];
+ *     mesh == verts is allowed.  reg_pose3d [batch,Jh,3] = joint_cam - joint_cam[0] when given, else h36m - h36m[0].  lift_pose3d
+ *     [batch,Jl,3]: the lift set relative to its root (coco: its pelvis) after j3d_processing (lib/aug_utils.py:67-83: about z by
+ *     -rot_deg, then the pairs swapped and x negated).  joint_img_out [batch,Jl,2]: the lift set's pixels -- the dataset's joint_img
+ *     passed through when given and the lift set is human36.  fit_error [batch]: get_fitting_error in mm (Human36M:302-309), NaN
+ *     without joint_cam.  valid [batch,3] = (mesh, lift, reg): ones; fit_error > fitting_thr clears mesh, and lift too for coco.
+ * GATOR_EINVAL with a text, before any launch: NULL args or a required pointer, struct_size not this header's, n_verts < 1, a
+ * regressor's n_verts != n_verts, GATOR_LIFT_COCO without reg_coco, a coco regressor outside 13..62 joints, joint_cam without joint_img
+ * for GATOR_LIFT_HUMAN36, compensate_root without R, root_idx outside [0, n_smpl_joints). */
+#define GATOR_LIFT_HUMAN36 0
+#define GATOR_LIFT_COCO 1
+typedef struct {
+    int32_t struct_size; /* = sizeof of this struct in the caller's header */
+    int32_t batch, n_verts, n_smpl_joints, root_idx;
+    int32_t compensate_root, lift_set, n_pairs;
+    int32_t reg_h36m_n_verts, reg_coco_n_verts;
+    float fitting_thr;
+    int32_t reserved;
+    const float *verts, *joints, *trans, *cam_t, *R, *focal, *princpt;
+    gator_coo reg_h36m, reg_coco;
+    const float *joint_cam, *joint_img;
+    const float* rot_deg;
+    const int32_t* flip;
+    const int32_t* flip_pairs;
+    float *mesh, *reg_pose3d, *lift_pose3d, *joint_img_out, *fit_error, *valid;
+} gator_camera_targets_args;
+int gator_batch_prepare_f32(const float* pose, const float* R, const float* betas, int32_t batch, int32_t n_pose, int32_t n_betas,
+                            int32_t root_idx, float* pose_out, float* betas_out, void* stream);
+int gator_camera_targets_f32(const gator_camera_targets_args* args, void* stream);
+
 /* The demo's mesh overlay (demo/renderer.py) on the device: a batched software rasteriser for the weak-perspective camera
  * (gator_amd/csrc/render.hip derives the geometry; DESIGN.md "Renderer").  For a vertex (x, y, z) of the model's output and
  * cam = (sx, sy, tx, ty):  column = (1 + sx (x + tx)) / 2 * W,  row = (1 + sy (y + ty)) / 2 * H,  depth = z (smaller is nearer, fragments
