@@ -3,6 +3,11 @@ does not load, importing the HIP path raises -- the product never routes through
 import ctypes
 import os
 
+try:
+    import torch        # the callers' tensors and streams; the binding itself loads without it
+except ImportError:
+    torch = None
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GATOR_AMD_LIB selects another build of the same ABI (the diagnostic library of `python -m gator_amd.build --diag`)
 LIB_PATH = os.environ.get('GATOR_AMD_LIB') or os.path.join(_HERE, 'lib', 'libgator_hip.so')
@@ -173,6 +178,23 @@ def load():
             raise RuntimeError('%s is ABI %d, this binding is ABI %d: rebuild with `python -m gator_amd.build`' % (LIB_PATH, lib.gator_abi_version(), ABI_VERSION))
         _lib = lib
     return _lib
+
+
+def stream_ptr(device):
+    """The current torch stream of `device` as the `void* stream` argument of the C ABI."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr(t):
+    """A tensor's address, or None (a NULL pointer) for an absent optional tensor."""
+    return None if t is None else t.data_ptr()
+
+
+def need_device(who, *tensors, what='inputs'):
+    """There is no CPU path: every given tensor (None = absent) must live on a HIP device."""
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError('%s: %s must live on a HIP device (there is no CPU path)' % (who, what))
 
 
 class DeviceStatusError(RuntimeError):

@@ -22,14 +22,6 @@ MAX_LIFT_JOINTS = 64             # csrc/train_batch.hip: kCamMaxJoints
 LIFT_SETS = {'human36': _lib.LIFT_HUMAN36, 'coco': _lib.LIFT_COCO}
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _tensor(x, who, name):
     if x is None:
         return None
@@ -54,11 +46,6 @@ def _rows(x, shape, who, name, device, dtype=torch.float32, broadcast=False):
     return x.to(dtype).contiguous()
 
 
-def _need_device(x, who):
-    if not x.is_cuda:
-        raise RuntimeError('%s: inputs must live on a HIP device (there is no CPU path)' % who)
-
-
 def _checked_pose(pose, n_joints, who):
     pose = _tensor(pose, who, 'pose')
     if pose is None or pose.dim() != 2 or pose.shape[0] < 1 or pose.shape[1] != n_joints * 3 or not pose.is_floating_point():
@@ -69,9 +56,9 @@ def _checked_pose(pose, n_joints, who):
 
 def _launch_prepare(pose, R, betas, root_idx, pose_out, betas_out):
     """pose [B,NJ*3], R [B,3,3] | None, betas [B,NB] | None: contiguous float32 on one HIP device.  One launch."""
-    _lib.check(_lib.load().gator_batch_prepare_f32(pose.data_ptr(), _ptr(R), _ptr(betas), pose.shape[0], pose.shape[1],
+    _lib.check(_lib.load().gator_batch_prepare_f32(pose.data_ptr(), _lib.ptr(R), _lib.ptr(betas), pose.shape[0], pose.shape[1],
                                                    0 if betas is None else betas.shape[1], int(root_idx), pose_out.data_ptr(),
-                                                   _ptr(betas_out), _stream(pose.device)), 'gator_batch_prepare_f32')
+                                                   _lib.ptr(betas_out), _lib.stream_ptr(pose.device)), 'gator_batch_prepare_f32')
     return pose_out, betas_out
 
 
@@ -88,7 +75,7 @@ def root_to_camera(pose, R, root_idx=SMPL_ROOT):
     if R is None:
         raise ValueError('%s: R is required' % who)
     R = _rows(R, (pose.shape[0], 3, 3), who, 'R', pose.device, broadcast=True)
-    _need_device(pose, who)
+    _lib.need_device(who, pose)
     p = pose.float().contiguous()
     with torch.cuda.device(p.device):
         return _launch_prepare(p, R, None, root_idx, torch.empty_like(p), None)[0]
@@ -103,13 +90,13 @@ def _camera_targets_args(verts, joints, trans, cam_t, R, compensate_root, focal,
     a.batch, a.n_verts, a.n_smpl_joints, a.root_idx = verts.shape[0], verts.shape[1], joints.shape[1], int(root_idx)
     a.compensate_root, a.lift_set, a.n_pairs = int(bool(compensate_root)), int(lift_set), 0 if pairs is None else int(pairs.shape[0])
     a.fitting_thr = float(fitting_thr)
-    a.verts, a.joints, a.trans, a.cam_t, a.R = verts.data_ptr(), joints.data_ptr(), _ptr(trans), _ptr(cam_t), _ptr(R)
+    a.verts, a.joints, a.trans, a.cam_t, a.R = verts.data_ptr(), joints.data_ptr(), _lib.ptr(trans), _lib.ptr(cam_t), _lib.ptr(R)
     a.focal, a.princpt = focal.data_ptr(), princpt.data_ptr()
     a.reg_h36m, a.reg_h36m_n_verts = gator_eval._coo_struct(reg_h), _n_verts(reg_h)
     if reg_c is not None:
         a.reg_coco, a.reg_coco_n_verts = gator_eval._coo_struct(reg_c), _n_verts(reg_c)
-    a.joint_cam, a.joint_img, a.rot_deg, a.flip = _ptr(joint_cam), _ptr(joint_img), _ptr(rot), _ptr(flip)
-    a.flip_pairs = _ptr(pairs) if a.n_pairs else None
+    a.joint_cam, a.joint_img, a.rot_deg, a.flip = _lib.ptr(joint_cam), _lib.ptr(joint_img), _lib.ptr(rot), _lib.ptr(flip)
+    a.flip_pairs = _lib.ptr(pairs) if a.n_pairs else None
     a.mesh, a.reg_pose3d, a.lift_pose3d = mesh.data_ptr(), reg_pose3d.data_ptr(), lift_pose3d.data_ptr()
     a.joint_img_out, a.fit_error, a.valid = joint_img_out.data_ptr(), fit_error.data_ptr(), valid.data_ptr()
     return a
@@ -118,7 +105,7 @@ def _camera_targets_args(verts, joints, trans, cam_t, R, compensate_root, focal,
 def _launch_camera_targets(verts, *rest):
     """_camera_targets_args' arguments.  One launch; nothing is allocated and the host does not wait."""
     a = _camera_targets_args(verts, *rest)
-    _lib.check(_lib.load().gator_camera_targets_f32(ctypes.byref(a), _stream(verts.device)), 'gator_camera_targets_f32')
+    _lib.check(_lib.load().gator_camera_targets_f32(ctypes.byref(a), _lib.stream_ptr(verts.device)), 'gator_camera_targets_f32')
 
 
 def _n_verts(reg):
@@ -223,7 +210,7 @@ def camera_frame_batch(layer, pose, shape, *, trans=None, cam_R=None, cam_t=None
         raise ValueError('%s: res must be (width, height)' % who)
     if res[0] < 1 or res[1] < 1:
         raise ValueError('%s: res %s must be positive' % (who, (res,)))
-    _need_device(pose, who)
+    _lib.need_device(who, pose)
 
     with torch.cuda.device(dev):
         p = pose.float().contiguous()

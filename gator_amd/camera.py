@@ -17,15 +17,11 @@ DEMO_SCHEDULE = ((0, 0.1), (500, 0.05), (1000, 0.001))     # demo/run.py:135,154
 DEMO_CROP = 500                                             # demo/run.py:177 virtual_crop_size
 
 
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
 
 def crop_joints(joints, crop_size=DEMO_CROP, box_scale=1.25, box_aspect=1.0, add_pelvis_neck=False):
     """joints [B,J,2|3] f32 on a HIP device (pixels) -> (xy [B,J(+2),2] in crop pixels, bbox [B,4] = bbox1 (x, y, w, h),
     valid [B] int32: 0 where process_bbox rejects the box; xy and bbox are 0 there).  crop_size is an int or (width, height)."""
-    if not joints.is_cuda:
-        raise RuntimeError('crop_joints: joints must live on a HIP device (there is no CPU path)')
+    _lib.need_device('crop_joints', joints, what='joints')
     if joints.dim() != 3 or joints.shape[2] < 2:
         raise ValueError('crop_joints: expected [B,J,2|3], got %s' % (tuple(joints.shape),))
     cw, ch = (crop_size, crop_size) if np.isscalar(crop_size) else crop_size
@@ -36,7 +32,7 @@ def crop_joints(joints, crop_size=DEMO_CROP, box_scale=1.25, box_aspect=1.0, add
     bbox = torch.empty((B, 4), device=dev, dtype=torch.float32)
     valid = torch.empty((B,), device=dev, dtype=torch.int32)
     _lib.check(_lib.load().gator_crop_joints_f32(x.data_ptr(), B, J, C, int(bool(add_pelvis_neck)), float(box_aspect), float(box_scale),
-                                                 int(cw), int(ch), xy.data_ptr(), bbox.data_ptr(), valid.data_ptr(), _stream(dev)),
+                                                 int(cw), int(ch), xy.data_ptr(), bbox.data_ptr(), valid.data_ptr(), _lib.stream_ptr(dev)),
                'gator_crop_joints_f32')
     return xy, bbox, valid
 
@@ -46,8 +42,7 @@ def fit_camera(joints3d, target, init=None, steps=1500, schedule=DEMO_SCHEDULE, 
     device; the first n_fit joints of each are used.  init [B,3] (default: torch.rand on the device, as OptimzeCamLayer draws it).
     schedule: up to 8 (milestone, lr) pairs -- the first lr from step 0, every later lr from step milestone + 1.
     -> (cam [B,3], loss [B]) or, with bbox [B,4] and image_size = (width, height), (cam, loss, orig_cam [B,4] = (sx, sy, tx, ty))."""
-    if not joints3d.is_cuda or not target.is_cuda:
-        raise RuntimeError('fit_camera: inputs must live on a HIP device (there is no CPU path)')
+    _lib.need_device('fit_camera', joints3d, target)
     if joints3d.dim() != 3 or joints3d.shape[2] != 3 or target.dim() != 3 or target.shape[2] != 2 or target.shape[0] != joints3d.shape[0]:
         raise ValueError('fit_camera: expected joints3d [B,n,3] and target [B,m,2], got %s and %s' % (tuple(joints3d.shape), tuple(target.shape)))
     if (bbox is None) != (image_size is None):
@@ -69,8 +64,8 @@ def fit_camera(joints3d, target, init=None, steps=1500, schedule=DEMO_SCHEDULE, 
         oc = torch.empty((B, 4), device=dev, dtype=torch.float32)
         w, h = float(image_size[0]), float(image_size[1])
     _lib.check(_lib.load().gator_fit_camera_f32(p.data_ptr(), B, p.shape[1], t.data_ptr(), t.shape[1], int(n_fit), c0.data_ptr(), int(crop_size),
-                                                int(steps), ms, lrs, len(sched), bb.data_ptr() if bb is not None else None, w, h, cam.data_ptr(),
-                                                loss.data_ptr(), oc.data_ptr() if oc is not None else None, _stream(dev)),
+                                                int(steps), ms, lrs, len(sched), _lib.ptr(bb), w, h, cam.data_ptr(),
+                                                loss.data_ptr(), _lib.ptr(oc), _lib.stream_ptr(dev)),
                'gator_fit_camera_f32')
     return (cam, loss) if oc is None else (cam, loss, oc)
 

@@ -37,10 +37,8 @@ class NativeComm:
             pose3d = pose3d.contiguous()
             J = pose3d.shape[1]
             out_p = torch.empty((self.world * B, J, 3), device=verts.device, dtype=torch.float32)
-        st = ctypes.c_void_p(torch.cuda.current_stream(verts.device).cuda_stream)
-        _lib.check(_lib.load().gator_allgather_verts(self._h, verts.data_ptr(), pose3d.data_ptr() if pose3d is not None else None, B, J,
-                                                     out_v.data_ptr(), out_p.data_ptr() if out_p is not None else None, st),
-                   'gator_allgather_verts')
+        _lib.check(_lib.load().gator_allgather_verts(self._h, verts.data_ptr(), _lib.ptr(pose3d), B, J, out_v.data_ptr(), _lib.ptr(out_p),
+                                                     _lib.stream_ptr(verts.device)), 'gator_allgather_verts')
         return (out_v, out_p) if pose3d is not None else out_v
 
     def close(self):

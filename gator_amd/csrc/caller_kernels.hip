@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
+#include "joints2d.h"
 #include "procrustes.h"
 
 namespace gator {
@@ -14,39 +15,16 @@ namespace {
 // shift, which cancels in the per-axis standardisation that follows it (checked on the demo input to 5e-8):
 // out = (xy - mean) / std over the joints of the sample, population std (np.std).  COCO inputs first get pelvis = (L_Hip+R_Hip)/2
 // and neck = (L_Shoulder+R_Shoulder)/2 appended (joints 11,12 and 5,6).
-// element j of this thread's column of a [n][threads] LDS image
-template <class T> struct ColT {
-    T* base; int tid, stride;
-    __device__ __forceinline__ T& operator[](int j) const { return base[j * stride + tid]; }
-};
-typedef ColT<double> Col;
-typedef ColT<float> ColF;
-__global__ void k_preprocess(const float* __restrict__ in, int B, int jin, int comps, int add_pn, float* __restrict__ out) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(64) void k_preprocess(const float* __restrict__ in, int B, int jin, int comps, int add_pn, float* __restrict__ out) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    const int jout = jin + (add_pn ? 2 : 0);
-    const float* p = in + (size_t)b * jin * comps;
-    // the joints of a sample as one COLUMN of a [32][blockDim] LDS image (run-time indexed private arrays would live in scratch)
-    __shared__ double xs_[32 * 64], ys_[32 * 64];
-    const Col x{xs_, (int)threadIdx.x, (int)blockDim.x}, y{ys_, (int)threadIdx.x, (int)blockDim.x};
-    for (int j = 0; j < jin; ++j) { x[j] = p[j * comps]; y[j] = p[j * comps + 1]; }
-    if (add_pn) {
-        x[jin] = (x[11] + x[12]) * 0.5;     y[jin] = (y[11] + y[12]) * 0.5;          // pelvis
-        x[jin + 1] = (x[5] + x[6]) * 0.5;   y[jin + 1] = (y[5] + y[6]) * 0.5;        // neck
-    }
-    double mx = 0.0, my = 0.0;
-    for (int j = 0; j < jout; ++j) { mx += x[j]; my += y[j]; }
-    mx /= jout; my /= jout;
-    double vx = 0.0, vy = 0.0;
-    for (int j = 0; j < jout; ++j) { vx += (x[j] - mx) * (x[j] - mx); vy += (y[j] - my) * (y[j] - my); }
-    const double sx = sqrt(vx / jout), sy = sqrt(vy / jout);      // a degenerate axis gives inf/nan exactly as numpy does
-    float* o = out + (size_t)b * jout * 2;
-    for (int j = 0; j < jout; ++j) { o[j * 2] = (float)((x[j] - mx) / sx); o[j * 2 + 1] = (float)((y[j] - my) / sy); }
+    __shared__ double xs_[kMaxJ * 64], ys_[kMaxJ * 64];
+    const Col<double> x{xs_, (int)threadIdx.x}, y{ys_, (int)threadIdx.x};
+    const int jout = load_joints(in + (size_t)b * jin * comps, jin, comps, add_pn, x, y);
+    standardise(x, y, jout, out + (size_t)b * jout * 2);
 }
 
-// svd3 / rigid_fit (the 3x3 Jacobi SVD, the reflection fix, the LDS point sets): csrc/procrustes.h, shared with mesh_eval.hip
-constexpr int kMaxPts = 32;
-constexpr size_t kPtsLds = (size_t)2 * kMaxPts * 3 * 64 * sizeof(double);      // 96 KB: the two point sets of a 64-thread block
+// svd3 / rigid_fit (the 3x3 Jacobi SVD, the reflection fix, the LDS point sets, kMaxPts / kPtsLds): csrc/procrustes.h
 __global__ void k_rigid_align(const float* __restrict__ A, const float* __restrict__ Bt, int nb, int n, float* __restrict__ out) {
     extern __shared__ double pts_lds[];                  // [2][kMaxPts][3][blockDim.x]
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -92,15 +70,7 @@ __global__ void k_joint_errors(const float* __restrict__ P, const float* __restr
     }
     double c, R[3][3], tr[3];
     rigid_fit(pa, pt, ne, c, R, tr);
-    double e1 = 0.0;
-    for (int i = 0; i < ne; ++i) {
-        double d2 = 0.0;
-        for (int r = 0; r < 3; ++r) {
-            const double al = (double)(float)(c * (R[r][0] * pa(i, 0) + R[r][1] * pa(i, 1) + R[r][2] * pa(i, 2)) + tr[r]);
-            d2 += (al - pt(i, r)) * (al - pt(i, r));
-        }
-        e1 += sqrt(d2);
-    }
+    const double e1 = aligned_error<true>(pa, pt, ne, c, R, tr);
     err[b * 2] = (float)(e0 / ne);
     err[b * 2 + 1] = (float)(e1 / ne);
 }
@@ -117,68 +87,32 @@ namespace {
 // (lib/aug_utils.py:140-173: three float32 point pairs, solved as cv2.getAffineTransform does) -> affine per joint, optional
 // flip_2d_joint (:31-38) -> float32 -> /[W,H] -> per-axis standardisation.  One thread per sample; float32 roundings where the
 // reference has them (bbox, centre/scale, the point pairs, the transformed joints, the division), fp64 in between.
-__global__ void k_preprocess_chain(const float* __restrict__ in, int B, int jin, int comps, int add_pn, const float* __restrict__ rot_deg,
-                                   const int32_t* __restrict__ flip, const int32_t* __restrict__ pairs, int n_pairs, int res_w, int res_h,
-                                   float* __restrict__ out, int32_t* __restrict__ valid) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(64) void k_preprocess_chain(const float* __restrict__ in, int B, int jin, int comps, int add_pn,
+                                                         const float* __restrict__ rot_deg, const int32_t* __restrict__ flip,
+                                                         const int32_t* __restrict__ pairs, int n_pairs, int res_w, int res_h,
+                                                         float* __restrict__ out, int32_t* __restrict__ valid) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    const int J = jin + (add_pn ? 2 : 0);
-    const float* p = in + (size_t)b * jin * comps;
-    __shared__ double xs_[32 * 64], ys_[32 * 64];          // one column per thread (48 KB with the float32 images below: 64-thread blocks)
-    __shared__ float fxs_[32 * 64], fys_[32 * 64];
-    const Col x{xs_, (int)threadIdx.x, (int)blockDim.x}, y{ys_, (int)threadIdx.x, (int)blockDim.x};
-    const ColF fxn{fxs_, (int)threadIdx.x, (int)blockDim.x}, fyn{fys_, (int)threadIdx.x, (int)blockDim.x};
-    for (int j = 0; j < jin; ++j) { x[j] = p[j * comps]; y[j] = p[j * comps + 1]; }
-    if (add_pn) {
-        x[jin] = (x[11] + x[12]) * 0.5;     y[jin] = (y[11] + y[12]) * 0.5;
-        x[jin + 1] = (x[5] + x[6]) * 0.5;   y[jin + 1] = (y[5] + y[6]) * 0.5;
-    }
+    __shared__ double xs_[kMaxJ * 64], ys_[kMaxJ * 64];    // one column per thread (48 KB with the float32 images below: 64-thread blocks)
+    __shared__ float fxs_[kMaxJ * 64], fys_[kMaxJ * 64];
+    const Col<double> x{xs_, (int)threadIdx.x}, y{ys_, (int)threadIdx.x};
+    const Col<float> fxn{fxs_, (int)threadIdx.x}, fyn{fys_, (int)threadIdx.x};
+    const int J = load_joints(in + (size_t)b * jin * comps, jin, comps, add_pn, x, y);
     float* o = out + (size_t)b * J * 2;
-    double xmin = x[0], xmax = x[0], ymin = y[0], ymax = y[0];
-    for (int j = 1; j < J; ++j) { xmin = fmin(xmin, x[j]); xmax = fmax(xmax, x[j]); ymin = fmin(ymin, y[j]); ymax = fmax(ymax, y[j]); }
-    // get_bbox: centre +- half extent, cast to float32
-    const double xc = (xmin + xmax) / 2., bw0 = xmax - xmin, yc = (ymin + ymax) / 2., bh0 = ymax - ymin;
-    const double bxmin = xc - 0.5 * bw0, bxmax = xc + 0.5 * bw0, bymin = yc - 0.5 * bh0, bymax = yc + 0.5 * bh0;
-    const float bx = (float)bxmin, by = (float)bymin, bw = (float)(bxmax - bxmin), bh = (float)(bymax - bymin);
-    // process_bbox (float32 arithmetic on the float32 box, as numpy does)
-    const float x2 = bx + (bw - 1.f), y2 = by + (bh - 1.f);
-    const bool ok = (bw * bh > 0.f) && x2 >= bx && y2 >= by;
+    float w0, h0, cx, cy;
+    const bool ok = box_extent(tight_box(x, y, J), w0, h0, cx, cy);
     if (valid) valid[b] = ok ? 1 : 0;
     if (!ok) {
         for (int j = 0; j < 2 * J; ++j) o[j] = 0.f;
         return;
     }
-    float w = x2 - bx, h = y2 - by;
-    const float cx = bx + w / 2.f, cy = by + h / 2.f;
-    const double ar = (double)res_w / (double)res_h;       // cfg.MODEL.input_shape[1] / [0]; python float (fp64) against float32 values
-    if ((double)w > ar * (double)h) h = (float)((double)w / ar);
-    else if ((double)w < ar * (double)h) w = (float)((double)h * ar);
+    const Extent e = aspect_fp64(w0, h0, res_w, res_h);
+    const float w = e.w, h = e.h;
     const float fx = cx - w / 2.f, fy = cy - h / 2.f;
-    // get_center_scale + get_affine_transform: float32 point pairs
-    const float cen0 = fx + w * 0.5f, cen1 = fy + h * 0.5f;
+    // get_center_scale, then the affine with the sample's rotation
     const double rr = M_PI * (rot_deg ? (double)rot_deg[b] : 0.0) / 180.0, sn = sin(rr), cs = cos(rr);
-    const double p1 = (double)(w * -0.5f);
-    const double sd0 = 0.0 * cs - p1 * sn, sd1 = 0.0 * sn + p1 * cs;                      // get_dir([0, -w/2], rot)
-    float src[3][2], dst[3][2];
-    src[0][0] = cen0; src[0][1] = cen1;
-    src[1][0] = (float)((double)cen0 + sd0); src[1][1] = (float)((double)cen1 + sd1);
-    dst[0][0] = res_w * 0.5f; dst[0][1] = res_h * 0.5f;
-    dst[1][0] = (float)((double)(res_w * 0.5) + 0.0); dst[1][1] = (float)((double)(res_h * 0.5) + (double)(res_w * -0.5f));
-    for (int q = 0; q < 2; ++q) {
-        float (*m)[2] = q ? dst : src;
-        const float d0 = m[0][0] - m[1][0], d1 = m[0][1] - m[1][1];
-        m[2][0] = m[1][0] + (-d1); m[2][1] = m[1][1] + d0;                                 // get_3rd_point
-    }
-    // solve [sx sy 1] T^T = [dx dy] for the 2x3 matrix (Cramer, fp64)
-    const double a0 = src[0][0], b0 = src[0][1], a1 = src[1][0], b1 = src[1][1], a2 = src[2][0], b2 = src[2][1];
-    const double det = a0 * (b1 - b2) - b0 * (a1 - a2) + (a1 * b2 - a2 * b1);
     double T[2][3];
-    for (int r = 0; r < 2; ++r) {
-        const double d0 = dst[0][r], d1 = dst[1][r], d2 = dst[2][r];
-        T[r][0] = (d0 * (b1 - b2) - b0 * (d1 - d2) + (d1 * b2 - d2 * b1)) / det;
-        T[r][1] = (a0 * (d1 - d2) - d0 * (a1 - a2) + (a1 * d2 - a2 * d1)) / det;
-        T[r][2] = (a0 * (b1 * d2 - b2 * d1) - b0 * (a1 * d2 - a2 * d1) + d0 * (a1 * b2 - a2 * b1)) / det;
-    }
+    crop_affine(fx + w * 0.5f, fy + h * 0.5f, w, sn, cs, res_w, res_h, T);
     for (int j = 0; j < J; ++j) {
         const double nx = T[0][0] * x[j] + T[0][1] * y[j] + T[0][2], ny = T[1][0] * x[j] + T[1][1] * y[j] + T[1][2];
         x[j] = nx; y[j] = ny;
@@ -191,13 +125,7 @@ __global__ void k_preprocess_chain(const float* __restrict__ in, int B, int jin,
         }
     }
     for (int j = 0; j < J; ++j) { fxn[j] = (float)x[j] / (float)res_w; fyn[j] = (float)y[j] / (float)res_h; }   // astype(float32); /= [W,H]
-    double mx = 0.0, my = 0.0;
-    for (int j = 0; j < J; ++j) { mx += fxn[j]; my += fyn[j]; }
-    mx /= J; my /= J;
-    double vx = 0.0, vy = 0.0;
-    for (int j = 0; j < J; ++j) { vx += (fxn[j] - mx) * (fxn[j] - mx); vy += (fyn[j] - my) * (fyn[j] - my); }
-    const double sx = sqrt(vx / J), sy = sqrt(vy / J);
-    for (int j = 0; j < J; ++j) { o[j * 2] = (float)((fxn[j] - mx) / sx); o[j * 2 + 1] = (float)((fyn[j] - my) / sy); }
+    standardise(fxn, fyn, J, o);
 }
 }  // namespace
 }  // namespace gator
@@ -223,18 +151,6 @@ extern "C" int gator_preprocess_pose2d_f32(const float* joints, int32_t batch, i
     if (add_pelvis_neck && num_joint_in < 13) return fail(GATOR_EINVAL, "gator_preprocess_pose2d_f32: pelvis/neck need the COCO joint order (>= 13 joints)");
     k_preprocess<<<(batch + 63) / 64, 64, 0, (hipStream_t)stream>>>(joints, batch, num_joint_in, comps, add_pelvis_neck, pose2d);      // 64-thread blocks: the kernel's LDS images have 64 columns
     GATOR_HIP_CHECK(hipGetLastError());
-    return GATOR_OK;
-}
-
-// 96 KB of dynamic LDS > the 64 KB default: raised once PER DEVICE (the attribute belongs to the device's copy of the function; a
-// process that evaluates on a second GPU, or whose first call failed transiently, must not inherit a cached answer)
-static int raise_pts_lds(const void* fn, bool (&done)[64]) {
-    int dev = 0;
-    GATOR_HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        GATOR_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gator::kPtsLds));
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
     return GATOR_OK;
 }
 

@@ -9,76 +9,40 @@
 #include <mutex>
 
 #include "internal.h"
+#include "joints2d.h"
 
 namespace gator {
 namespace {
 
-// element j of this lane's column of a [n][64] LDS image (run-time indexed private arrays would live in scratch)
-template <class T> struct Col {
-    T* base; int tid;
-    __device__ __forceinline__ T& operator[](int j) const { return base[j * 64 + tid]; }
-};
-
 // get_bbox (lib/coord_utils.py:21-39) -> process_bbox(bbox, aspect, scale) (:42-66) -> j2d_processing(joints, (crop_w, crop_h), bbox1,
-// rot 0, no flip) (lib/aug_utils.py:51-64,140-179).  numpy 2 keeps `float32 op python float` in float32 (NEP 50), so the box is float32
-// arithmetic throughout with aspect and scale rounded to float32; the joints, the centre of the tight box and the affine solve are fp64
-// as in the reference (its joints are float64, cv2 solves in double); the joints are rounded to float32 at the end (kp.astype).
+// rot 0, no flip) (lib/aug_utils.py:51-64,140-179), from the pieces of joints2d.h.  numpy 2 keeps `float32 op python float` in float32
+// (NEP 50), so the box is float32 arithmetic throughout with aspect and scale rounded to float32; the joints, the centre of the tight
+// box and the affine solve are fp64 as in the reference (its joints are float64, cv2 solves in double); the joints are rounded to
+// float32 at the end (kp.astype).
 __global__ __launch_bounds__(64) void k_crop_joints(const float* __restrict__ in, int B, int jin, int comps, int add_pn, float aspect,
                                                     float scale, int crop_w, int crop_h, float* __restrict__ xy, float* __restrict__ box,
                                                     int32_t* __restrict__ valid) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    const int J = jin + (add_pn ? 2 : 0);
-    const float* p = in + (size_t)b * jin * comps;
     __shared__ double xs_[kMaxJ * 64], ys_[kMaxJ * 64];
     const Col<double> x{xs_, (int)threadIdx.x}, y{ys_, (int)threadIdx.x};
-    for (int j = 0; j < jin; ++j) { x[j] = p[j * comps]; y[j] = p[j * comps + 1]; }
-    if (add_pn) {                                           // demo/run.py:103-121: pelvis = (L_Hip + R_Hip) / 2, neck = (L_Shoulder + R_Shoulder) / 2
-        x[jin] = (x[11] + x[12]) * 0.5;     y[jin] = (y[11] + y[12]) * 0.5;
-        x[jin + 1] = (x[5] + x[6]) * 0.5;   y[jin + 1] = (y[5] + y[6]) * 0.5;
-    }
+    const int J = load_joints(in + (size_t)b * jin * comps, jin, comps, add_pn, x, y);
     float* o = xy + (size_t)b * J * 2;
-    double xmin = x[0], xmax = x[0], ymin = y[0], ymax = y[0];
-    for (int j = 1; j < J; ++j) { xmin = fmin(xmin, x[j]); xmax = fmax(xmax, x[j]); ymin = fmin(ymin, y[j]); ymax = fmax(ymax, y[j]); }
-    const double xc = (xmin + xmax) / 2., bw0 = xmax - xmin, yc = (ymin + ymax) / 2., bh0 = ymax - ymin;
-    const double bxmin = xc - 0.5 * bw0, bxmax = xc + 0.5 * bw0, bymin = yc - 0.5 * bh0, bymax = yc + 0.5 * bh0;
-    const float bx = (float)bxmin, by = (float)bymin, bw = (float)(bxmax - bxmin), bh = (float)(bymax - bymin);
-    const float x2 = bx + (bw - 1.f), y2 = by + (bh - 1.f);
-    const bool ok = (bw * bh > 0.f) && x2 >= bx && y2 >= by;
+    float w0, h0, cx, cy;
+    const bool ok = box_extent(tight_box(x, y, J), w0, h0, cx, cy);
     valid[b] = ok ? 1 : 0;
     if (!ok) {                                              // process_bbox returns None: the sample has no crop
         for (int j = 0; j < 2 * J; ++j) o[j] = 0.f;
         for (int k = 0; k < 4; ++k) box[b * 4 + k] = 0.f;
         return;
     }
-    float w = x2 - bx, h = y2 - by;
-    const float cx = bx + w / 2.f, cy = by + h / 2.f;
-    if (w > aspect * h) h = w / aspect;
-    else if (w < aspect * h) w = h * aspect;
-    const float sw = w * scale, sh = h * scale;
+    const Extent e = aspect_f32(w0, h0, aspect);
+    const float sw = e.w * scale, sh = e.h * scale;
     const float fx = cx - sw / 2.f, fy = cy - sh / 2.f;
     box[b * 4] = fx; box[b * 4 + 1] = fy; box[b * 4 + 2] = sw; box[b * 4 + 3] = sh;
-    // get_center_scale + get_affine_transform (rot 0): float32 point pairs, the second source point formed in fp64
-    const float cen0 = fx + sw * 0.5f, cen1 = fy + sh * 0.5f;
-    float src[3][2], dst[3][2];
-    src[0][0] = cen0; src[0][1] = cen1;
-    src[1][0] = (float)((double)cen0 + 0.0); src[1][1] = (float)((double)cen1 + (double)(sw * -0.5f));
-    dst[0][0] = crop_w * 0.5f; dst[0][1] = crop_h * 0.5f;
-    dst[1][0] = (float)((double)(crop_w * 0.5) + 0.0); dst[1][1] = (float)((double)(crop_h * 0.5) + (double)(crop_w * -0.5f));
-    for (int q = 0; q < 2; ++q) {
-        float (*m)[2] = q ? dst : src;
-        const float d0 = m[0][0] - m[1][0], d1 = m[0][1] - m[1][1];
-        m[2][0] = m[1][0] + (-d1); m[2][1] = m[1][1] + d0;                                 // get_3rd_point
-    }
-    const double a0 = src[0][0], b0 = src[0][1], a1 = src[1][0], b1 = src[1][1], a2 = src[2][0], b2 = src[2][1];
-    const double det = a0 * (b1 - b2) - b0 * (a1 - a2) + (a1 * b2 - a2 * b1);
+    // get_center_scale, then the affine without a rotation
     double T[2][3];
-    for (int r = 0; r < 2; ++r) {
-        const double d0 = dst[0][r], d1 = dst[1][r], d2 = dst[2][r];
-        T[r][0] = (d0 * (b1 - b2) - b0 * (d1 - d2) + (d1 * b2 - d2 * b1)) / det;
-        T[r][1] = (a0 * (d1 - d2) - d0 * (a1 - a2) + (a1 * d2 - a2 * d1)) / det;
-        T[r][2] = (a0 * (b1 * d2 - b2 * d1) - b0 * (a1 * d2 - a2 * d1) + d0 * (a1 * b2 - a2 * b1)) / det;
-    }
+    crop_affine(fx + sw * 0.5f, fy + sh * 0.5f, sw, 0.0, 1.0, crop_w, crop_h, T);
     for (int j = 0; j < J; ++j) {
         o[j * 2] = (float)(T[0][0] * x[j] + T[0][1] * y[j] + T[0][2]);
         o[j * 2 + 1] = (float)(T[1][0] * x[j] + T[1][1] * y[j] + T[1][2]);

@@ -18,15 +18,13 @@ namespace gator {
 namespace {
 
 constexpr int kMeshThreads = 256, kMeshWaves = kMeshThreads / 64;
-constexpr int kMaxRegJoints = 64, kMaxEvalPts = 32, kLanesPerJoint = kMeshThreads / kMaxRegJoints;
+constexpr int kMaxRegJoints = 64, kLanesPerJoint = kMeshThreads / kMaxRegJoints;      // the joint fit takes kMaxPts points (procrustes.h)
 
-// v[k] := the sum of v[k] over the workgroup, in every thread, the same bits in each: a + b == b + a bit for bit, so after each xor
-// step both partners hold one value.  red: [kMeshWaves][K] doubles of LDS.
+// v[k] := the sum of v[k] over the workgroup, in every thread, the same bits in each (wave_sum, then the four waves' values in a
+// fixed order).  red: [kMeshWaves][K] doubles of LDS.
 template <int K> __device__ void block_sum(double (&v)[K], double* red) {
 #pragma unroll
-    for (int k = 0; k < K; ++k)
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) v[k] += __shfl_xor(v[k], m);
+    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
     __syncthreads();                                     // the readers of the previous sum are done with red
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_errors(const float* __res
                                                               const int32_t* __restrict__ idx, int ne, float* __restrict__ err) {
     __shared__ double red[kMeshWaves * 11];
     __shared__ double jr[2][kMaxRegJoints][3], je[2][kMaxRegJoints][3];      // regressed joints: [pred / target][joint][axis]
-    __shared__ double pts[2 * kMaxEvalPts * 3];                               // the root-aligned evaluation joints of the joint fit
+    __shared__ double pts[2 * kMaxPts * 3];                                   // the root-aligned evaluation joints of the joint fit
     __shared__ double fit[13];                                                // c, R, tr of the mesh
     const int tid = threadIdx.x;
     const float* p = P + (size_t)blockIdx.x * n * 3;
@@ -115,14 +113,13 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_errors(const float* __res
             for (int k = 0; k < 3; ++k) { const double d = (jr[0][j][k] - rp[k]) - (jr[1][j][k] - rt[k]); e2 += d * d; }
             e2 = sqrt(e2);
         }
-#pragma unroll
-        for (int w = 1; w < 64; w <<= 1) e2 += __shfl_xor(e2, w);
+        e2 = wave_sum(e2);
         if ((tid & 63) == 0) {
             o[2] = finite_or_nan(e2 / rg.n_joint);
             if (!has_eval) { o[0] = o[1] = __builtin_nanf(""); }
             else {
-                const Pts pa{pts, 0, 1}, pt{pts + kMaxEvalPts * 3, 0, 1};
-                double e0 = 0.0, e1 = 0.0;
+                const Pts pa{pts, 0, 1}, pt{pts + kMaxPts * 3, 0, 1};
+                double e0 = 0.0;
                 for (int i = 0; i < ne; ++i) {
                     const int j = idx ? idx[i] : i;
                     double d2 = 0.0;
@@ -134,17 +131,8 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_errors(const float* __res
                     e0 += sqrt(d2);
                 }
                 rigid_fit(pa, pt, ne, c, R, tr);
-                for (int i = 0; i < ne; ++i) {
-                    double d2 = 0.0;
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-                        const double al = c * (R[r][0] * pa(i, 0) + R[r][1] * pa(i, 1) + R[r][2] * pa(i, 2)) + tr[r];
-                        d2 += (al - pt(i, r)) * (al - pt(i, r));
-                    }
-                    e1 += sqrt(d2);
-                }
                 o[0] = finite_or_nan(e0 / ne);
-                o[1] = finite_or_nan(e1 / ne);
+                o[1] = finite_or_nan(aligned_error<false>(pa, pt, ne, c, R, tr) / ne);
             }
         }
     } else {
@@ -216,7 +204,7 @@ extern "C" int gator_mesh_errors_f32(const float* pred, const float* target, int
         if (!coo_ok(ev) || eval_root < 0 || eval_root >= ev.n_joint)
             return fail(GATOR_EINVAL, "gator_mesh_errors_f32: evaluation regressor (nnz >= 0 with its arrays, 1..64 joints, root inside them)");
         ne = eval_joints ? n_eval : ev.n_joint;
-        if (ne < 3 || ne > kMaxEvalPts) return fail(GATOR_EINVAL, "gator_mesh_errors_f32: 3..32 evaluation joints");
+        if (ne < 3 || ne > kMaxPts) return fail(GATOR_EINVAL, "gator_mesh_errors_f32: 3..32 evaluation joints");
     }
     k_mesh_errors<<<batch, kMeshThreads, 0, (hipStream_t)stream>>>(pred, target, n_verts, pred_scale, target_scale, *root_regressor, root, ev,
                                                                    eval_root, has_eval ? eval_joints : nullptr, ne, errors);

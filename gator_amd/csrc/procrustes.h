@@ -1,10 +1,38 @@
-// Similarity (Procrustes) fit shared by the evaluation kernels: caller_kernels.hip (k_rigid_align, k_joint_errors: one sample per
-// lane, <= 32 points) and mesh_eval.hip (k_mesh_errors: one workgroup per sample, the moments reduced over the whole mesh).
+// Similarity (Procrustes) fit shared by the evaluation kernels: caller_kernels.hip (k_rigid_align, k_joint_errors) and temporal.hip
+// (k_seq_errors): one sample per lane, <= kMaxPts points; mesh_eval.hip (k_mesh_errors): one workgroup per sample, the moments reduced
+// over the whole mesh.  With it what those kernels share around the fit: the point-set bound and its LDS, the error under the fit,
+// the wave's fp64 sum (train_batch.hip: k_camera_targets uses that too).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "internal.h"
+
 namespace gator {
 namespace {
+
+constexpr int kMaxPts = 32;                                                       // points of a per-lane fit (3..32 evaluation joints)
+constexpr size_t kPtsLds = (size_t)2 * kMaxPts * 3 * 64 * sizeof(double);         // 96 KB: the two point sets of a 64-thread block
+
+// 96 KB of dynamic LDS > the 64 KB default: raised once PER DEVICE and per kernel, `done` being that kernel's table (the attribute
+// belongs to the device's copy of the function; a process that evaluates on a second GPU, or whose first call failed transiently,
+// must not inherit a cached answer)
+inline int raise_pts_lds(const void* fn, bool (&done)[64]) {
+    int dev = 0;
+    GATOR_HIP_CHECK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !done[dev]) {
+        GATOR_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPtsLds));
+        if (dev >= 0 && dev < 64) done[dev] = true;
+    }
+    return GATOR_OK;
+}
+
+// The sum of x over the 64 lanes of a wave, the same bits in every lane: a + b == b + a bit for bit, so after each xor step both
+// partners hold one value.
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m);
+    return x;
+}
 
 // 3x3 SVD by one-sided Jacobi (Hestenes) in fp64: G = H V is driven to orthogonal columns; s_i = |G_i|, U_i = G_i / s_i.
 // V is a product of rotations and column swaps, orthogonal whatever the rank.  A column of G under 1e-14 s_0 is rounding noise:
@@ -136,6 +164,24 @@ __device__ void rigid_fit(const Pts& a, const Pts& t, int n, double& c, double (
         for (int cc = 0; cc < 3; ++cc) H[r][cc] /= n;
     var /= n;
     similarity_from_moments(H, var, ca, cb, c, R, tr);
+}
+
+// The error under a fit: the sum over the n points of |c R a + tr - t|, fp64.  RoundF32: the aligned point is rounded to float32
+// first, where the reference's aligned joints are float32 (k_joint_errors: data/PW3D/dataset.py:273-286).
+template <bool RoundF32>
+__device__ __forceinline__ double aligned_error(const Pts& a, const Pts& t, int n, double c, const double (&R)[3][3], const double (&tr)[3]) {
+    double e = 0.0;
+    for (int i = 0; i < n; ++i) {
+        double d2 = 0.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const double v = c * (R[r][0] * a(i, 0) + R[r][1] * a(i, 1) + R[r][2] * a(i, 2)) + tr[r];
+            const double al = RoundF32 ? (double)(float)v : v;
+            d2 += (al - t(i, r)) * (al - t(i, r));
+        }
+        e += sqrt(d2);
+    }
+    return e;
 }
 
 }  // namespace

@@ -20,9 +20,7 @@ namespace {
 
 constexpr int kEuroThreads = 64;      // one lane per (video, channel); consecutive lanes take consecutive channels of one video
 constexpr int kPrefetch = 8;          // PF: frames whose loads are in flight ahead of the chain (gator_amd/temporal.py: PREFETCH)
-constexpr int kSeqThreads = 64;       // k_seq_errors: one lane per frame, the LDS point sets have 64 columns
-constexpr int kMaxPts = 32;
-constexpr size_t kPtsLds = (size_t)2 * kMaxPts * 3 * kSeqThreads * sizeof(double);      // 96 KB, as caller_kernels.hip: k_joint_errors
+constexpr int kSeqThreads = 64;       // k_seq_errors: one lane per frame, the LDS point sets (procrustes.h: kPtsLds) have 64 columns
 
 // lib/smooth_utils.py:27-46 as smooth_pose drives it (:49-72), step for step in fp64: x_hat[0] = x[0], dx_prev = 0, t_e = dt;
 //   a_d = sf(t_e, d_cutoff); dx = (x - x_prev) / t_e; dx_hat = a_d dx + (1 - a_d) dx_prev;
@@ -126,16 +124,7 @@ __global__ __launch_bounds__(kSeqThreads) void k_seq_errors(const Pred* __restri
     }
     double c, R[3][3], tr[3];
     rigid_fit(pa, pt, ne, c, R, tr);
-    double e2 = 0.0;
-    for (int j = 0; j < ne; ++j) {
-        double d2 = 0.0;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const double al = c * (R[r][0] * pa(j, 0) + R[r][1] * pa(j, 1) + R[r][2] * pa(j, 2)) + tr[r];
-            d2 += (al - pt(j, r)) * (al - pt(j, r));
-        }
-        e2 += sqrt(d2);
-    }
+    const double e2 = aligned_error<false>(pa, pt, ne, c, R, tr);
     double* o = rows + (size_t)i * 3;
     o[0] = triple ? acc / ne : __builtin_nan("");
     o[1] = e1 / ne;
@@ -155,24 +144,11 @@ __global__ __launch_bounds__(64) void k_seq_reduce(const double* __restrict__ ro
         a[2] += rows[(size_t)i * 3 + 2];
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) a[k] += __shfl_xor(a[k], m);
+    for (int k = 0; k < 4; ++k) a[k] = wave_sum(a[k]);
     if (threadIdx.x == 0) {
         double* o = sums + (size_t)v * 6;
         o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = (double)(e - s); o[5] = 0.0;
     }
-}
-
-// 96 KB of dynamic LDS > the 64 KB default: raised once per device and per instantiation (caller_kernels.hip: raise_pts_lds)
-int raise_seq_lds(const void* fn, bool (&done)[64]) {
-    int dev = 0;
-    GATOR_HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        GATOR_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPtsLds));
-        if (dev >= 0 && dev < 64) done[dev] = true;
-    }
-    return GATOR_OK;
 }
 
 }  // namespace
@@ -213,11 +189,11 @@ extern "C" int gator_sequence_errors(const void* pred, int32_t pred_f64, const f
     if (blocks > 0x7fffffffLL) return fail(GATOR_EINVAL, "gator_sequence_errors: too many frames for a grid");
     static bool raised_f64_[64] = {}, raised_f32_[64] = {};
     if (pred_f64) {
-        if (int rc = raise_seq_lds((const void*)k_seq_errors<double>, raised_f64_)) return rc;
+        if (int rc = raise_pts_lds((const void*)k_seq_errors<double>, raised_f64_)) return rc;
         k_seq_errors<double><<<(unsigned)blocks, kSeqThreads, kPtsLds, (hipStream_t)stream>>>((const double*)pred, gt, valid, seg_start, n_videos, n_frames,
                                                                                            n_eval, rows);
     } else {
-        if (int rc = raise_seq_lds((const void*)k_seq_errors<float>, raised_f32_)) return rc;
+        if (int rc = raise_pts_lds((const void*)k_seq_errors<float>, raised_f32_)) return rc;
         k_seq_errors<float><<<(unsigned)blocks, kSeqThreads, kPtsLds, (hipStream_t)stream>>>((const float*)pred, gt, valid, seg_start, n_videos, n_frames,
                                                                                           n_eval, rows);
     }

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
+#include "procrustes.h"      // wave_sum
 
 namespace gator {
 namespace {
@@ -152,13 +153,6 @@ __device__ void regress_cam(const gator_coo& g, const float* v, const double T[3
     if (q == 0 && j < g.n_joint)
 #pragma unroll
         for (int k = 0; k < 4; ++k) out[j][k] = a[k];
-}
-
-// The sum of x over the 64 lanes of a wave, the same bits in every lane.
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m);
-    return x;
 }
 
 __global__ __launch_bounds__(kCamThreads) void k_camera_targets(const gator_camera_targets_args a) {

@@ -45,14 +45,12 @@ class JointRegressor:
 
     def __call__(self, verts):
         """verts [B,6890,3] f32 on the device -> joints [B,n_joint,3] (same unit as verts)."""
-        if not verts.is_cuda:
-            raise RuntimeError('JointRegressor: verts must live on a HIP device')
+        _lib.need_device('JointRegressor', verts, what='verts')
         verts = verts.contiguous().float()
         B = verts.shape[0]
         out = torch.empty((B, self.n_joint, 3), device=verts.device, dtype=torch.float32)
-        st = ctypes.c_void_p(torch.cuda.current_stream(verts.device).cuda_stream)
         _lib.check(_lib.load().gator_regress_joints_f32(verts.data_ptr(), B, self.row.data_ptr(), self.col.data_ptr(),
-                                                       self.val.data_ptr(), self.nnz, self.n_joint, out.data_ptr(), st),
+                                                       self.val.data_ptr(), self.nnz, self.n_joint, out.data_ptr(), _lib.stream_ptr(verts.device)),
                    'gator_regress_joints_f32')
         return out
 
@@ -78,14 +76,12 @@ def rigid_align(a, b):
     """Batched similarity (Procrustes) alignment of a onto b, [B,N,3] device tensors (lib/coord_utils.py:127-149:
     rotation by SVD of the covariance with the reflection fix, scale = trace(S)/var(a), translation of the centroids):
     gator_rigid_align_f32, one 3x3 one-sided-Jacobi SVD per sample in fp64."""
-    if not (a.is_cuda and b.is_cuda):
-        raise RuntimeError('rigid_align: inputs must live on a HIP device')
+    _lib.need_device('rigid_align', a, b)
     if a.shape != b.shape or a.dim() != 3 or a.shape[2] != 3:
         raise ValueError('rigid_align: expected two [B,N,3] tensors, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
     a32, b32 = a.contiguous().float(), b.contiguous().float()
     out = torch.empty_like(a32)
-    st = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-    _lib.check(_lib.load().gator_rigid_align_f32(a32.data_ptr(), b32.data_ptr(), a32.shape[0], a32.shape[1], out.data_ptr(), st),
+    _lib.check(_lib.load().gator_rigid_align_f32(a32.data_ptr(), b32.data_ptr(), a32.shape[0], a32.shape[1], out.data_ptr(), _lib.stream_ptr(a.device)),
                'gator_rigid_align_f32')
     return out.to(a.dtype)
 
@@ -99,18 +95,16 @@ def pa_mpjpe(pred_joint, target_joint, eval_joints=H36M_EVAL_JOINTS):
 def joint_errors(pred_joint, target_joint, eval_joints=H36M_EVAL_JOINTS, root=0, pred_scale=1.0):
     """Per-sample (MPJPE, PA-MPJPE) in one launch (gator_joint_errors_f32): pred_joint [B,nj,3] (multiplied by pred_scale on the fly:
     1000 for metres -> mm), target_joint [B,nj,3] -> [B,2].  mpjpe()/pa_mpjpe() above are its two columns averaged over the batch."""
-    if not (pred_joint.is_cuda and target_joint.is_cuda):
-        raise RuntimeError('joint_errors: inputs must live on a HIP device')
+    _lib.need_device('joint_errors', pred_joint, target_joint)
     p, t = pred_joint.contiguous().float(), target_joint.contiguous().float()
     if p.dim() != 3 or p.shape[2] != 3 or p.shape != t.shape:
         raise ValueError('joint_errors: expected two [B,nj,3] tensors, got %s and %s' % (tuple(p.shape), tuple(t.shape)))
     B, nj = p.shape[0], p.shape[1]
     idx = None if eval_joints is None else torch.as_tensor(_checked_eval_joints(eval_joints, nj, 'joint_errors'), dtype=torch.int32, device=p.device)
     out = torch.empty((B, 2), device=p.device, dtype=torch.float32)
-    st = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
-    _lib.check(_lib.load().gator_joint_errors_f32(p.data_ptr(), t.data_ptr(), B, nj, idx.data_ptr() if idx is not None else None,
-                                                  int(idx.numel()) if idx is not None else 0, int(root), float(pred_scale), out.data_ptr(), st),
-               'gator_joint_errors_f32')
+    _lib.check(_lib.load().gator_joint_errors_f32(p.data_ptr(), t.data_ptr(), B, nj, _lib.ptr(idx),
+                                                  int(idx.numel()) if idx is not None else 0, int(root), float(pred_scale), out.data_ptr(),
+                                                  _lib.stream_ptr(p.device)), 'gator_joint_errors_f32')
     return out
 
 
@@ -202,11 +196,10 @@ def _launch_mesh_errors(p, t, root_reg, root, eval_reg, idx, eval_root, pred_sca
     """p, t: contiguous float32 [B,N,3] on one HIP device; idx: int32 device tensor or None; out: float32 [B,5] there, written in place.
     Everything is checked by the callers; nothing here allocates device memory or waits for the device."""
     ev = _coo_struct(eval_reg) if eval_reg is not None else None
-    st = ctypes.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)
     _lib.check(_lib.load().gator_mesh_errors_f32(p.data_ptr(), t.data_ptr(), p.shape[0], p.shape[1], float(pred_scale), float(target_scale),
                                                  ctypes.byref(_coo_struct(root_reg)), root, ctypes.byref(ev) if ev is not None else None, eval_root,
-                                                 idx.data_ptr() if idx is not None else None, int(idx.numel()) if idx is not None else 0,
-                                                 out.data_ptr(), st), 'gator_mesh_errors_f32')
+                                                 _lib.ptr(idx), int(idx.numel()) if idx is not None else 0,
+                                                 out.data_ptr(), _lib.stream_ptr(p.device)), 'gator_mesh_errors_f32')
     return out
 
 
@@ -229,8 +222,7 @@ def mesh_errors(pred_mesh, target_mesh, root_regressor, root=0, eval_regressor=N
         eval_reg = _as_coo(eval_regressor, N, device, who)
         eval_root = _checked_root(eval_root, eval_reg.n_joint, who)
         idx = _checked_eval_set(eval_joints, eval_reg.n_joint, who)
-    if not pred_mesh.is_cuda:
-        raise RuntimeError('mesh_errors: inputs must live on a HIP device')
+    _lib.need_device(who, pred_mesh)
     p, t = pred_mesh.contiguous().float(), target_mesh.contiguous().float()
     idx_t = None if idx is None else torch.as_tensor(idx, dtype=torch.int32, device=device)
     out = torch.empty((p.shape[0], 5), device=device, dtype=torch.float32)

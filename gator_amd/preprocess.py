@@ -6,8 +6,6 @@
 With rot = 0 / flip = 0 (all evaluation paths) the bbox/affine//[W,H] part is a per-axis positive scale + shift and cancels in the
 standardisation, so the kernel computes (xy - mean) / std over the sample's joints (population std) -- checked against the
 reference's own chain on the demo input (tests/golden/demo_preprocess.npz)."""
-import ctypes
-
 import torch
 
 from . import _lib
@@ -15,15 +13,13 @@ from . import _lib
 
 def normalise_pose2d(joints, add_pelvis_neck=False):
     """joints [B,J,2|3] f32 on a HIP device (pixels) -> pose2d [B,J(+2),2] f32, the input of GATOR.forward."""
-    if not joints.is_cuda:
-        raise RuntimeError('normalise_pose2d: joints must live on a HIP device (there is no CPU path)')
+    _lib.need_device('normalise_pose2d', joints, what='joints')
     if joints.dim() != 3 or joints.shape[2] < 2:
         raise ValueError('normalise_pose2d: expected [B,J,2|3], got %s' % (tuple(joints.shape),))
     x = joints.contiguous().float()
     B, J, C = x.shape
     out = torch.empty((B, J + (2 if add_pelvis_neck else 0), 2), device=x.device, dtype=torch.float32)
-    st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(_lib.load().gator_preprocess_pose2d_f32(x.data_ptr(), B, J, C, int(bool(add_pelvis_neck)), out.data_ptr(), st),
+    _lib.check(_lib.load().gator_preprocess_pose2d_f32(x.data_ptr(), B, J, C, int(bool(add_pelvis_neck)), out.data_ptr(), _lib.stream_ptr(x.device)),
                'gator_preprocess_pose2d_f32')
     return out
 
@@ -39,8 +35,7 @@ def preprocess_chain(joints, rot_deg=None, flip=None, flip_pairs=(), add_pelvis_
     """The reference's whole input chain on the device (gator_preprocess_chain_f32): bbox -> process_bbox -> affine with rotation /
     flip -> /[W,H] -> standardise.  joints [B,J,2|3] f32 (pixels); rot_deg [B] f32 or None; flip [B] int32 or None.
     -> (pose2d [B,J(+2),2], valid [B] int32: 0 where process_bbox rejects the box and the reference drops the sample)."""
-    if not joints.is_cuda:
-        raise RuntimeError('preprocess_chain: joints must live on a HIP device (there is no CPU path)')
+    _lib.need_device('preprocess_chain', joints, what='joints')
     pair_list = [(int(u), int(v)) for u, v in flip_pairs]
     if any(u < 0 or v < 0 for u, v in pair_list):       # the kernel skips a pair beyond the sample's joints; a negative one would be a raw offset
         raise ValueError('preprocess_chain: negative joint index in flip_pairs')
@@ -52,9 +47,8 @@ def preprocess_chain(joints, rot_deg=None, flip=None, flip_pairs=(), add_pelvis_
     rot = None if rot_deg is None else torch.as_tensor(rot_deg, dtype=torch.float32, device=dev).contiguous()
     fl = None if flip is None else torch.as_tensor(flip, dtype=torch.int32, device=dev).contiguous()
     pairs = torch.as_tensor(pair_list, dtype=torch.int32, device=dev).reshape(-1, 2).contiguous()
-    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(_lib.load().gator_preprocess_chain_f32(x.data_ptr(), B, J, C, int(bool(add_pelvis_neck)), rot.data_ptr() if rot is not None else None,
-                                                      fl.data_ptr() if fl is not None else None, pairs.data_ptr() if pairs.numel() else None,
-                                                      int(pairs.shape[0]), int(res[0]), int(res[1]), out.data_ptr(), valid.data_ptr(), st),
+    _lib.check(_lib.load().gator_preprocess_chain_f32(x.data_ptr(), B, J, C, int(bool(add_pelvis_neck)), _lib.ptr(rot),
+                                                      _lib.ptr(fl), pairs.data_ptr() if pairs.numel() else None,
+                                                      int(pairs.shape[0]), int(res[0]), int(res[1]), out.data_ptr(), valid.data_ptr(), _lib.stream_ptr(dev)),
                'gator_preprocess_chain_f32')
     return out, valid

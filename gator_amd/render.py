@@ -45,10 +45,6 @@ def demo_rotation(angle=None, axis=None, rotate=False):
     return R
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class MeshRenderer:
     def __init__(self, faces, device='cuda:0', n_verts=None):
         """faces [F,3] integer vertex indices (numpy or tensor); n_verts defaults to the largest index + 1."""
@@ -77,9 +73,6 @@ class MeshRenderer:
             self._h = ctypes.c_void_p()
 
     __del__ = close
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def workspace(self):
         """(bytes held, allocations made since create) -- the test hook of the C ABI."""
@@ -155,8 +148,8 @@ class MeshRenderer:
         n = torch.empty((M, self.n_verts, 3), device=self.device, dtype=torch.float32)
         r = self._rot(rot)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.gator_render_vertices_f32(self._h, _ptr(v), _ptr(c), M, int(H), int(W), r.ctypes.data_as(ctypes.c_void_p) if r is not None else None,
-                                                           _ptr(xy), _ptr(z), _ptr(n), self._stream()), 'gator_render_vertices_f32')
+            _lib.check(self._lib.gator_render_vertices_f32(self._h, _lib.ptr(v), _lib.ptr(c), M, int(H), int(W), r.ctypes.data_as(ctypes.c_void_p) if r is not None else None,
+                                                           _lib.ptr(xy), _lib.ptr(z), _lib.ptr(n), _lib.stream_ptr(self.device)), 'gator_render_vertices_f32')
         return xy, z, n
 
     def rasterise(self, xy_fixed, z, image_index=None, n_images=None, size=(224, 224), cull_backfaces=True):
@@ -170,8 +163,8 @@ class MeshRenderer:
         N = int(n_images) if n_images is not None else M
         keys = torch.empty((max(N, 0), max(int(H), 0), max(int(W), 0)), device=self.device, dtype=torch.int64)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.gator_render_raster(self._h, _ptr(xy), _ptr(zz), idx.ctypes.data_as(ctypes.c_void_p) if idx is not None else None,
-                                                     M, N, int(H), int(W), CULL_BACKFACES if cull_backfaces else 0, _ptr(keys), self._stream()),
+            _lib.check(self._lib.gator_render_raster(self._h, _lib.ptr(xy), _lib.ptr(zz), idx.ctypes.data_as(ctypes.c_void_p) if idx is not None else None,
+                                                     M, N, int(H), int(W), CULL_BACKFACES if cull_backfaces else 0, _lib.ptr(keys), _lib.stream_ptr(self.device)),
                        'gator_render_raster')
         return keys
 
@@ -191,10 +184,10 @@ class MeshRenderer:
         fid = torch.empty((N, H, W), device=self.device, dtype=torch.int32) if return_face_id else None
         dep = torch.empty((N, H, W), device=self.device, dtype=torch.float32) if return_depth else None
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.gator_render_resolve(self._h, _ptr(kk), _ptr(xy), _ptr(nn), _ptr(col),
-                                                      idx.ctypes.data_as(ctypes.c_void_p) if idx is not None else None, M, _ptr(bg), N, H, W,
-                                                      L.ctypes.data_as(ctypes.c_void_p), L.shape[0], float(ambient), _ptr(rgb), _ptr(fid), _ptr(dep),
-                                                      self._stream()), 'gator_render_resolve')
+            _lib.check(self._lib.gator_render_resolve(self._h, _lib.ptr(kk), _lib.ptr(xy), _lib.ptr(nn), _lib.ptr(col),
+                                                      idx.ctypes.data_as(ctypes.c_void_p) if idx is not None else None, M, _lib.ptr(bg), N, H, W,
+                                                      L.ctypes.data_as(ctypes.c_void_p), L.shape[0], float(ambient), _lib.ptr(rgb), _lib.ptr(fid), _lib.ptr(dep),
+                                                      _lib.stream_ptr(self.device)), 'gator_render_resolve')
         out = (rgb,) + ((fid,) if return_face_id else ()) + ((dep,) if return_depth else ())
         return out[0] if len(out) == 1 else out
 
@@ -212,10 +205,10 @@ class MeshRenderer:
         fid = torch.empty(rgb.shape[:3], device=self.device, dtype=torch.int32) if return_face_id else None
         dep = torch.empty(rgb.shape[:3], device=self.device, dtype=torch.float32) if return_depth else None
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.gator_render_f32(self._h, _ptr(v), _ptr(c), _ptr(col), idx.ctypes.data_as(ctypes.c_void_p) if idx is not None else None, M,
-                                                  _ptr(bg), N, H, W, r.ctypes.data_as(ctypes.c_void_p) if r is not None else None,
+            _lib.check(self._lib.gator_render_f32(self._h, _lib.ptr(v), _lib.ptr(c), _lib.ptr(col), idx.ctypes.data_as(ctypes.c_void_p) if idx is not None else None, M,
+                                                  _lib.ptr(bg), N, H, W, r.ctypes.data_as(ctypes.c_void_p) if r is not None else None,
                                                   L.ctypes.data_as(ctypes.c_void_p), L.shape[0], float(ambient), CULL_BACKFACES if cull_backfaces else 0,
-                                                  _ptr(rgb), _ptr(fid), _ptr(dep), self._stream()), 'gator_render_f32')
+                                                  _lib.ptr(rgb), _lib.ptr(fid), _lib.ptr(dep), _lib.stream_ptr(self.device)), 'gator_render_f32')
         out = (rgb,) + ((fid,) if return_face_id else ()) + ((dep,) if return_depth else ())
         return out[0] if len(out) == 1 else out
 

@@ -136,11 +136,10 @@ class SMPLLayer:
         center = -1 if (self.center_idx is None or trans is not None) else int(self.center_idx)
         verts = torch.empty((B, self.num_verts, 3), device=self.device, dtype=torch.float32) if want_verts else None
         joints = torch.empty((B, self.num_joints, 3), device=self.device, dtype=torch.float32) if want_joints else None
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        ptr = _lib.ptr
         with torch.cuda.device(self.device):
-            st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             _lib.check(_lib.load().gator_smpl_forward_f32(self._ctx, ptr(pose), ptr(betas), ptr(trans), B, center, self.out_scale, ptr(verts),
-                                                          ptr(joints), st), 'gator_smpl_forward_f32')
+                                                          ptr(joints), _lib.stream_ptr(self.device)), 'gator_smpl_forward_f32')
         return verts, joints
 
     __call__ = forward

@@ -11,15 +11,13 @@ operations in the same order, with no contracted multiply-add.
 
 Frames are grouped into videos either by `lengths` (consecutive videos, in order) or by `video_indices` (the reference's
 self.video_indices: one index array per video, the frames of a video in temporal order); with neither, the input is one video."""
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
 
 PREFETCH = 8                # csrc/temporal.hip: kPrefetch, the depth of k_one_euro's load ring
-MAX_EVAL_JOINTS = 32        # csrc/temporal.hip: kMaxPts
+MAX_EVAL_JOINTS = 32        # csrc/procrustes.h: kMaxPts
 SEQUENCE_ERROR_COLUMNS = ('accel', 'MPJPE', 'PA-MPJPE')        # the columns of the per-frame rows and of the per-video means
 
 
@@ -89,28 +87,19 @@ def _checked_valid(valid, F, device, who):
     return valid
 
 
-def _need_device(x, who):
-    if not x.is_cuda:
-        raise RuntimeError('%s: inputs must live on a HIP device' % who)
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _launch_one_euro(x, seg, V, min_cutoff, beta, d_cutoff, dt, out):
     """x: contiguous float32 [F,C] on a HIP device, seg: int64 [V+1] there, out: float64 or float32 [F,C] there.  One launch."""
     _lib.check(_lib.load().gator_one_euro_f32(x.data_ptr(), seg.data_ptr(), x.shape[0], V, x.shape[1], float(min_cutoff), float(beta),
                                               float(d_cutoff), float(dt), 1 if out.dtype == torch.float64 else 0, out.data_ptr(),
-                                              _stream(x.device)), 'gator_one_euro_f32')
+                                              _lib.stream_ptr(x.device)), 'gator_one_euro_f32')
     return out
 
 
 def _launch_sequence_errors(p, g, valid, seg, V, rows, sums):
     """p: contiguous float64 or float32 [F,ne,3], g: contiguous float32, valid: uint8 [F] or None, rows [F,3] / sums [V,6] float64.  Two launches."""
     _lib.check(_lib.load().gator_sequence_errors(p.data_ptr(), 1 if p.dtype == torch.float64 else 0, g.data_ptr(),
-                                                 valid.data_ptr() if valid is not None else None, seg.data_ptr(), p.shape[0], V, p.shape[1],
-                                                 rows.data_ptr(), sums.data_ptr(), _stream(p.device)), 'gator_sequence_errors')
+                                                 _lib.ptr(valid), seg.data_ptr(), p.shape[0], V, p.shape[1],
+                                                 rows.data_ptr(), sums.data_ptr(), _lib.stream_ptr(p.device)), 'gator_sequence_errors')
 
 
 def _filter_params(min_cutoff, beta, d_cutoff, dt, who):
@@ -135,7 +124,7 @@ def smooth_pose(pred, lengths=None, video_indices=None, min_cutoff=0.004, beta=0
     F = pred.shape[0]
     seg, order = _segments(F, lengths, video_indices, who)
     par = _filter_params(min_cutoff, beta, d_cutoff, dt, who)
-    _need_device(pred, who)
+    _lib.need_device(who, pred)
     dev = pred.device
     x = pred.reshape(F, -1).float()
     seg_d = torch.from_numpy(seg).to(dev)
@@ -154,7 +143,7 @@ def _errors(pred, gt, lengths, video_indices, valid, smooth, par, who):
     F, ne = pred.shape[0], pred.shape[1]
     seg, order = _segments(F, lengths, video_indices, who)
     valid = _checked_valid(valid, F, pred.device, who)
-    _need_device(pred, who)
+    _lib.need_device(who, pred)
     dev, V = pred.device, len(seg) - 1
     seg_d = torch.from_numpy(seg).to(dev)
     order_d = None if order is None else torch.from_numpy(order).to(dev)

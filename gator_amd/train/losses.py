@@ -52,7 +52,7 @@ class _LossFn(torch.autograd.Function):
                 ve = valid.expand(p.shape)
                 sv = _I64x4(*([0] * (4 - p.dim()) + list(ve.stride())))
             ws = owner.workspace(max(1, p.numel() // 9 + 1), 1)
-            _lib.check(lib.gator_t_coord_loss(p.data_ptr(), t.data_ptr(), valid.data_ptr() if valid is not None else None, sv, _I64x4(*n4), float(weight),
+            _lib.check(lib.gator_t_coord_loss(p.data_ptr(), t.data_ptr(), _lib.ptr(valid), sv, _I64x4(*n4), float(weight),
                                               out.data_ptr(), grad.data_ptr() if need else None, ws.data_ptr(), st), 'gator_t_coord_loss')
         else:
             B, V, _ = p.shape

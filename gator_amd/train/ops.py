@@ -20,13 +20,12 @@ U_AFFINE, U_GELU, U_DGELU, U_EXP, U_RSQRT, U_SQRT, U_RECIP, U_ABS, U_SIGN, U_POW
 
 def stream_of(t):
     """The current stream of t's device, as the C ABI's gator_stream."""
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+    return _lib.stream_ptr(t.device)
 
 
 def _need_device(*ts):
+    _lib.need_device('gator_amd.train', *ts, what='tensors')
     for t in ts:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError('gator_amd.train: tensors must live on a HIP device (there is no CPU path)')
         if t is not None and t.dtype != torch.float32:
             raise RuntimeError('gator_amd.train: float32 only, got %s' % t.dtype)
 
@@ -120,8 +119,8 @@ def raw_gemm(a, b, out=None, bias=None, alpha=1.0, accumulate=False, a_rowsum=No
     ksplit = _ksplit(M, N, K) if n1 * n2 == 1 else 1
     ws = torch.empty(ksplit * (M * N + M), device=a.device, dtype=torch.float32) if ksplit > 1 else None
     _call('gator_t_gemm', a.data_ptr(), b.data_ptr(), out.data_ptr(), M, N, K, _I64x2(sa[2], sa[3]), _I64x2(sb[2], sb[3]), _I64x2(so[2], so[3]),
-          n1, n2, _I64x2(sa[0], sa[1]), _I64x2(sb[0], sb[1]), _I64x2(so[0], so[1]), bias.data_ptr() if bias is not None else None, float(alpha),
-          int(accumulate), ksplit, ws.data_ptr() if ws is not None else None, a_rowsum.data_ptr() if a_rowsum is not None else None, stream_of(a))
+          n1, n2, _I64x2(sa[0], sa[1]), _I64x2(sb[0], sb[1]), _I64x2(so[0], so[1]), _lib.ptr(bias), float(alpha),
+          int(accumulate), ksplit, _lib.ptr(ws), _lib.ptr(a_rowsum), stream_of(a))
     return out
 
 
@@ -227,8 +226,8 @@ def run_group(problems, dev):
     for p, (a4, b4, out4, rowsum, bias) in zip(arr, problems):
         M, K, N = a4.shape[2], a4.shape[3], b4.shape[3]
         p.A, p.B, p.C = a4.data_ptr(), b4.data_ptr(), out4.data_ptr()
-        p.a_rowsum = rowsum.data_ptr() if rowsum is not None else None
-        p.bias = bias.data_ptr() if bias is not None else None
+        p.a_rowsum = _lib.ptr(rowsum)
+        p.bias = _lib.ptr(bias)
         p.M, p.N, p.K = M, N, K
         p.ksplit = _ksplit(M, N, K)
         p.stride_a[0], p.stride_a[1] = a4.stride(2), a4.stride(3)
@@ -616,7 +615,7 @@ class _LayerNorm(torch.autograd.Function):
         y = torch.empty_like(xc)
         mean = torch.empty(rows, device=x.device, dtype=torch.float32)
         rinv = torch.empty(rows, device=x.device, dtype=torch.float32)
-        _call('gator_t_layernorm_fwd', xc.data_ptr(), rows, n, w.data_ptr() if w is not None else None, b.data_ptr() if b is not None else None,
+        _call('gator_t_layernorm_fwd', xc.data_ptr(), rows, n, _lib.ptr(w), _lib.ptr(b),
               float(eps), int(mode), y.data_ptr(), mean.data_ptr(), rinv.data_ptr(), stream_of(x))
         ctx.save_for_backward(xc, mean, rinv, w)
         ctx.eps, ctx.mode, ctx.has_b = eps, mode, b is not None
@@ -639,8 +638,8 @@ class _LayerNorm(torch.autograd.Function):
         dx = torch.empty_like(xc)
         need_w = w is not None and ctx.needs_input_grad[1]
         dyx = torch.empty_like(xc) if need_w else None
-        _call('gator_t_layernorm_bwd', gc.data_ptr(), xc.data_ptr(), mean.data_ptr(), rinv.data_ptr(), w.data_ptr() if w is not None else None, rows, n,
-              float(ctx.eps), int(ctx.mode), dx.data_ptr(), dyx.data_ptr() if need_w else None, add.data_ptr() if add is not None else None, stream_of(xc))
+        _call('gator_t_layernorm_bwd', gc.data_ptr(), xc.data_ptr(), mean.data_ptr(), rinv.data_ptr(), _lib.ptr(w), rows, n,
+              float(ctx.eps), int(ctx.mode), dx.data_ptr(), dyx.data_ptr() if need_w else None, _lib.ptr(add), stream_of(xc))
         gw = _grad_colsum(dyx.view(rows, n), ctx.wslot) if need_w else None
         gb = _grad_colsum(gc.view(rows, n), ctx.bslot) if ctx.has_b and ctx.needs_input_grad[2] else None
         return dx, gw, gb, None, None, None
@@ -686,7 +685,7 @@ class Generator:
             offsets.append(gen.offset if o else 0)
         if not any(on):
             return (0, *offsets, None)
-        return (gen.seed, *offsets, gen.counter.data_ptr() if gen.counter is not None else None)
+        return (gen.seed, *offsets, _lib.ptr(gen.counter))
 
 
 class _Dropout(torch.autograd.Function):
@@ -857,9 +856,9 @@ class _DropFused(torch.autograd.Function):
         out = torch.empty_like(xc)
         mask = torch.empty(xc.shape, device=x.device, dtype=torch.uint8) if (rate > 0 and offset) else None
         fac = torch.empty(xc.shape[0], device=x.device, dtype=torch.float32) if (path_rate > 0 and path_offset) else None
-        _call('gator_t_drop_fused', xc.data_ptr(), rc.data_ptr() if rc is not None else None, n, per, int(gelu), float(rate), ctypes.c_uint64(seed),
-              ctypes.c_uint64(offset), float(path_rate), ctypes.c_uint64(path_offset), counter, out.data_ptr(), mask.data_ptr() if mask is not None else None,
-              fac.data_ptr() if fac is not None else None, stream_of(x))
+        _call('gator_t_drop_fused', xc.data_ptr(), _lib.ptr(rc), n, per, int(gelu), float(rate), ctypes.c_uint64(seed),
+              ctypes.c_uint64(offset), float(path_rate), ctypes.c_uint64(path_offset), counter, out.data_ptr(), _lib.ptr(mask),
+              _lib.ptr(fac), stream_of(x))
         ctx.save_for_backward(xc if gelu else None, mask, fac)
         ctx.cfg = (gelu, rate, res is not None)
         return out
@@ -873,8 +872,8 @@ class _DropFused(torch.autograd.Function):
             dx = gc
         else:
             dx = torch.empty_like(gc)
-            _call('gator_t_drop_fused_bwd', gc.data_ptr(), x.data_ptr() if x is not None else None, mask.data_ptr() if mask is not None else None,
-                  fac.data_ptr() if fac is not None else None, gc.numel(), gc.numel() // gc.shape[0], int(gelu), float(rate), dx.data_ptr(), stream_of(gc))
+            _call('gator_t_drop_fused_bwd', gc.data_ptr(), _lib.ptr(x), _lib.ptr(mask),
+                  _lib.ptr(fac), gc.numel(), gc.numel() // gc.shape[0], int(gelu), float(rate), dx.data_ptr(), stream_of(gc))
         return dx, (gc if has_res else None), None, None, None, None, None, None, None
 
 
@@ -900,7 +899,7 @@ class _BatchNormTrain(torch.autograd.Function):
         mean = torch.empty(C, device=x.device, dtype=torch.float32)
         rinv = torch.empty(C, device=x.device, dtype=torch.float32)
         _call('gator_t_batchnorm_fwd', xc.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), mean.data_ptr(), rinv.data_ptr(),
-              run_mean.data_ptr() if run_mean is not None else None, run_var.data_ptr() if run_var is not None else None, B, C, L, float(eps),
+              _lib.ptr(run_mean), _lib.ptr(run_var), B, C, L, float(eps),
               float(momentum), stream_of(x))
         ctx.save_for_backward(xc, w, mean, rinv)
         ctx.wslot, ctx.bslot = grad_slot(w), grad_slot(b)

@@ -89,7 +89,7 @@ class Adam:
         f = self.p.flat
         _lib.check(_lib.load().gator_t_adam(f.data_ptr(), grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.p.numel,
                                             float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_count,
-                                            self.device_step.data_ptr() if self.device_step is not None else None, ops.stream_of(f)), 'gator_t_adam')
+                                            _lib.ptr(self.device_step), ops.stream_of(f)), 'gator_t_adam')
 
     # ---- checkpoint interchange with the reference (main/train.py:51-58 saves optimizer.state_dict(); base.py:73-77 loads it) ----
     def state_dict(self):

@@ -3,7 +3,8 @@ Round 4 made several changes that were meant to be schedules only and checked th
 as a test: per-sample kernel and sample-tiled kernel, persistent and four-launch MDR forms (B = 5 / 256 / 700), both golden variants.
 A change that is meant to move bits re-records the file (and re-runs the error budget); any other change must leave it green.
 tests/golden/mdr_form_digests.json does the same for the MDR kernels' other forms (tools/ab_digest.py: form_digests): exact split, fp32-input
-MFMA, config 3 and the whole-head kernels, four-launch and persistent, at B = 11."""
+MFMA, config 3 and the whole-head kernels, four-launch and persistent, at B = 11.
+tests/golden/caller_side_digests.json does it for the kernels around the forward (tools/ab_digest.py: caller_digests)."""
 import json
 import os
 
@@ -12,6 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'fp32_digests.json')
 FORMS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'mdr_form_digests.json')
+CALLER_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'caller_side_digests.json')
 
 
 def test_fp32_forward_digests_match_the_recorded_build():
@@ -40,6 +42,21 @@ def test_mdr_form_digests_match_the_recorded_build(form):
     assert len(want) >= 8 and set(got) == set(want)
     bad = {k: (got.get(k), h) for k, h in want.items() if got.get(k) != h}
     assert not bad, 'outputs moved bits against tests/golden/mdr_form_digests.json: %s' % bad
+
+
+def test_caller_side_digests_match_the_recorded_build():
+    """The kernels around the forward (preprocess, camera crop, Procrustes / joint / mesh / sequence errors, camera targets) bit for bit
+    against the build that was recorded before their shared steps moved into csrc/joints2d.h and csrc/procrustes.h: small seeded shapes
+    at the 64-lane block edge, the 32-joint column limit, a rejected box, every rotation and flip, 3 and 32 fitted points, videos
+    shorter than a triple (tools/ab_digest.py: caller_digests)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tools.ab_digest import caller_digests
+    want = json.load(open(CALLER_PATH))['digests']
+    got = caller_digests()
+    assert len(want) >= 100 and set(got) == set(want)
+    bad = {k: (got.get(k), h) for k, h in want.items() if got.get(k) != h}
+    assert not bad, 'outputs moved bits against tests/golden/caller_side_digests.json: %s' % bad
 
 
 def test_byte_lo_weight_stream_equals_the_three_plane_stream_bit_for_bit(monkeypatch):

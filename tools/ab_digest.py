@@ -6,7 +6,9 @@
     move bits, together with the error budget (tests/error_budget.py).
   * `--forms --write tests/golden/mdr_form_digests.json` does the same for form_digests(): the MDR kernels' non-default arithmetic forms
     and whole-head kernels at B = 11, which the fp32 digests above never reach.
-python tools/ab_digest.py [tag] [--forms] [--write path [--commit hash-of-the-recorded-build]]"""
+  * `--caller --write tests/golden/caller_side_digests.json` does the same for caller_digests(): the kernels around the forward
+    (preprocess, camera crop, Procrustes / joint / mesh / sequence errors, camera targets) on small seeded shapes.
+python tools/ab_digest.py [tag] [--forms | --caller] [--write path [--commit hash-of-the-recorded-build]]"""
 import contextlib, hashlib, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -93,9 +95,178 @@ def form_digests(forms=None):
     return out
 
 
+# The caller-side kernels (preprocess / camera crop / Procrustes and joint errors / sequence errors / mesh errors / camera targets): small
+# seeded shapes at the edges of their shared pieces -- the 64-lane block edge, the 32-joint column limit, a rejected box, every rotation
+# and flip, 3 and 32 fitted points, videos shorter than a triple.
+COCO_FLIP_PAIRS = ((1, 2), (3, 4), (5, 6), (7, 8), (9, 10), (11, 12), (13, 14), (15, 16))
+H36M_FLIP_PAIRS = ((1, 4), (2, 5), (3, 6), (14, 11), (15, 12), (16, 13))
+CALLER_B = (1, 64, 65, 130)
+CALLER_JOINTS = ((17, True), (17, False), (30, True))      # (J_in, add pelvis / neck): 19 joints, 17, and 32 = the column limit
+CALLER_ROT = (0.0, 30.0, -90.0, 180.0)
+
+
+def _sha_canon(*tensors):
+    """sha256[:32] of the raw bytes, every NaN first replaced by numpy's one NaN so that no digest depends on a payload."""
+    import numpy as np
+    h = hashlib.sha256()
+    for t in tensors:
+        a = t.detach().cpu().numpy().copy()
+        if a.dtype.kind == 'f':
+            a[np.isnan(a)] = np.nan
+        h.update(a.tobytes())
+    return h.hexdigest()[:32]
+
+
+def _raw_joints(rs, B, J, comps, reject):
+    """Pixel joints of B people in a 640 x 480 image (comps 3: a score column); reject: sample B // 2 has all joints on one point."""
+    import numpy as np
+    centre = rs.rand(B, 1, 2) * np.array([400.0, 250.0]) + np.array([120.0, 110.0])
+    x = centre + (rs.rand(B, J, 2) - 0.5) * (rs.rand(B, 1, 2) * np.array([150.0, 200.0]) + 20.0)
+    if comps == 3:
+        x = np.concatenate([x, rs.rand(B, J, 1)], 2)
+    if reject:
+        x[B // 2, :, :2] = x[B // 2, :1, :2]
+    return torch.from_numpy(x.astype(np.float32)).cuda()
+
+
+def _rotations(rs, B):
+    import numpy as np
+    q, _ = np.linalg.qr(rs.randn(B, 3, 3))
+    q[:, :, 0] *= np.sign(np.linalg.det(q))[:, None]
+    return q
+
+
+def _sparse_regressor(rs, n_joint, nv):
+    import numpy as np
+    d = np.zeros((n_joint, nv), np.float32)
+    for j in range(n_joint):
+        d[j, rs.choice(nv, 6, replace=False)] = rs.dirichlet(np.ones(6)).astype(np.float32)
+    return d
+
+
+def caller_digests():
+    """{'<entry point> <case>': digest} of the raw output bytes of the caller-side entry points, inputs from np.random.RandomState."""
+    import numpy as np
+    from gator_amd import batch, camera, eval as gator_eval, preprocess, temporal
+    f32 = np.float32
+    dev = lambda a, dt=None: torch.from_numpy(np.ascontiguousarray(a)).cuda() if dt is None else torch.from_numpy(np.ascontiguousarray(a)).cuda().to(dt)  # noqa: E731
+    out = {}
+
+    # the 2D joint chain: normalise_pose2d, preprocess_chain, crop_joints
+    for B in CALLER_B:
+        for J, pn in CALLER_JOINTS:
+            for comps in (2, 3):
+                case = 'B=%d J=%d%s comps=%d' % (B, J, '+2' if pn else '', comps)
+                rs = np.random.RandomState(1000 * B + 10 * J + comps + (5 if pn else 0))
+                out['normalise_pose2d ' + case] = _sha_canon(preprocess.normalise_pose2d(_raw_joints(rs, B, J, comps, False), add_pelvis_neck=pn))
+                # one sample whose box is rejected; at B = 1 that is the only sample, so B = 1 runs both ways
+                for reject in ((False, True) if B == 1 else (True,)):
+                    x = _raw_joints(rs, B, J, comps, reject)
+                    got = list(preprocess.preprocess_chain(x, add_pelvis_neck=pn))
+                    # per-sample augmentation: the four rotations cycle fastest, the flip every four samples; B = 1 takes all eight in turn
+                    for shift in (range(8) if B == 1 else (0,)):
+                        i = np.arange(B) + shift
+                        rot, flip = np.asarray(CALLER_ROT, f32)[i % 4], ((i // 4) % 2).astype(np.int32)
+                        got += preprocess.preprocess_chain(x, rot_deg=rot, flip=flip, flip_pairs=COCO_FLIP_PAIRS, add_pelvis_neck=pn)
+                    got += preprocess.preprocess_chain(x, rot_deg=np.zeros(B, f32), flip=np.ones(B, np.int32), flip_pairs=COCO_FLIP_PAIRS,
+                                                       add_pelvis_neck=pn, res=(256, 256))
+                    valid = got[1].cpu().numpy()
+                    assert reject == (int(valid.sum()) == B - 1) and (not reject or valid[B // 2] == 0), (case, valid)
+                    tag = case + (' rejected' if B == 1 and reject else '')
+                    out['preprocess_chain ' + tag] = _sha_canon(*got)
+                    crops = []
+                    for aspect in (1.0, 0.75):
+                        for size in (500, (288, 384)):
+                            crops += camera.crop_joints(x, crop_size=size, box_aspect=aspect, add_pelvis_neck=pn)
+                    assert int(crops[2].sum()) == B - int(reject)
+                    out['crop_joints ' + tag] = _sha_canon(*crops)
+
+    # Procrustes and the joint errors
+    for N in (3, 14, 32):
+        for B in (1, 65):
+            rs = np.random.RandomState(7000 + 100 * N + B)
+            a, b = dev((rs.randn(B, N, 3) * 0.3).astype(f32)), dev((rs.randn(B, N, 3) * 0.3).astype(f32))
+            out['rigid_align N=%d B=%d' % (N, B)] = _sha_canon(gator_eval.rigid_align(a, b))
+            got = []
+            for nj, idx in ((N, None), (N + 3, [int(i) for i in rs.permutation(N + 3)[:N]])):
+                t = (rs.randn(B, nj, 3) * 300.0).astype(f32)
+                p = (t / 1000.0 + rs.randn(B, nj, 3) * 0.03).astype(f32)
+                for root in (0, nj - 1):
+                    got.append(gator_eval.joint_errors(dev(p), dev(t), eval_joints=idx, root=root, pred_scale=1000.0))
+                    got.append(gator_eval.joint_errors(dev(p * f32(1000.0)), dev(t), eval_joints=idx, root=root, pred_scale=1.0))
+            out['joint_errors N=%d B=%d' % (N, B)] = _sha_canon(*got)
+
+    # the per-video errors: videos of 1, 2, 3 and 70 frames in one call
+    lengths = (1, 2, 3, 70)
+    F = sum(lengths)
+    for ne in (3, 14):
+        rs = np.random.RandomState(8000 + ne)
+        g = rs.randn(F, ne, 3) * 200.0
+        p64 = g + np.cumsum(rs.randn(F, ne, 3), 0) * 3.0
+        valid = (rs.rand(F) > 0.15)
+        for dt in (torch.float32, torch.float64):
+            for smooth in (False, True):
+                got = []
+                for v in (None, valid):
+                    got += temporal._errors(dev(p64, dt), dev(g.astype(f32)), lengths, None, v, smooth, [0.004, 0.005, 1.0, 1.0], 'caller_digests')
+                out['sequence_errors ne=%d %s smooth=%d' % (ne, str(dt).split('.')[1], smooth)] = _sha_canon(*got)
+
+    # the whole-mesh errors
+    for N in (50, 300):
+        rs = np.random.RandomState(9000 + N)
+        t = (rs.rand(3, N, 3) - 0.5) * np.array([0.9, 1.7, 0.4])
+        p = t + rs.randn(3, N, 3) * 0.02 + rs.randn(3, 1, 3) * 0.1
+        root_reg, eval_reg = _sparse_regressor(rs, 17, N), _sparse_regressor(rs, 17, N)
+        for ev in (None, eval_reg):
+            got = gator_eval.mesh_errors(dev(p.astype(f32)), dev(t.astype(f32)), root_reg, root=2, eval_regressor=ev, pred_scale=1000.0, target_scale=1000.0)
+            out['mesh_errors N=%d eval=%d' % (N, ev is not None)] = _sha_canon(got)
+
+    # the camera-frame targets (k_camera_targets), with the dataset's own joints so that the fitting error is formed
+    B, N = 2, 50
+    for lift_set, pairs in (('human36', H36M_FLIP_PAIRS), ('coco', COCO_FLIP_PAIRS)):
+        rs = np.random.RandomState(9500 + len(lift_set))
+        verts = ((rs.rand(B, N, 3) - 0.5) * np.array([0.9, 1.7, 0.4])).astype(f32)
+        joints = (rs.randn(B, 24, 3) * 0.3).astype(f32)
+        trans, cam_t = (rs.randn(B, 3) * 0.5).astype(f32), (rs.randn(B, 3) * 0.3 + np.array([0, 0, 4.5])).astype(f32)
+        R = _rotations(rs, B).astype(f32)
+        focal, princpt = (1145.0 + rs.randn(B, 2) * 5).astype(f32), (np.array([512.0, 515.0]) + rs.randn(B, 2) * 3).astype(f32)
+        dh, dc = _sparse_regressor(rs, 17, N), _sparse_regressor(rs, 17, N)
+        reg_h = gator_eval._Coo.from_dense(dh, 'cuda', 'caller_digests')
+        reg_c = gator_eval._Coo.from_dense(dc, 'cuda', 'caller_digests') if lift_set == 'coco' else None
+        mesh_cam = (verts.astype(np.float64) + (trans.astype(np.float64) + cam_t)[:, None]) * 1000.0
+        jc = (np.einsum('jv,bvc->bjc', dh.astype(np.float64), mesh_cam) + rs.randn(B, 17, 3) * 20.0).astype(f32)
+        ji = (jc[:, :, :2] / jc[:, :, 2:] * focal[:, None] + princpt[:, None]).astype(f32)
+        Jl = 19 if lift_set == 'coco' else 17
+        got = []
+        for compensate in (False, True):
+            o = [torch.empty(s, device='cuda') for s in ((B, N, 3), (B, 17, 3), (B, Jl, 3), (B, Jl, 2), (B,), (B, 3))]
+            batch._launch_camera_targets(dev(verts), dev(joints), dev(trans), dev(cam_t), dev(R), compensate, dev(focal), dev(princpt), reg_h, reg_c,
+                                         batch.LIFT_SETS[lift_set], dev(jc), dev(ji), dev(np.asarray([30.0, -90.0], f32)),
+                                         dev(np.asarray([1, 0], np.int32)), dev(np.asarray(pairs, np.int32)), 25.0, 0, *o)
+            got += o
+        out['camera_targets %s B=%d N=%d' % (lift_set, B, N)] = _sha_canon(*got)
+    torch.cuda.synchronize()
+    return out
+
+
+def main_caller():
+    write = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
+    d = caller_digests()
+    for k, h in d.items():
+        print('%-56s %s' % (k, h), flush=True)
+    if write:
+        commit = sys.argv[sys.argv.index('--commit') + 1] if '--commit' in sys.argv else 'unknown'
+        what = ('sha256[:32] of the raw output bytes of the caller-side entry points (tools/ab_digest.py: caller_digests), gfx950, NaNs '
+                'canonicalised, inputs from np.random.RandomState with fixed seeds.  Recorded with the library of commit %s' % commit)
+        with open(write, 'w') as f:
+            json.dump({'what': what, 'digests': d}, f, indent=1)
+
+
 def main():
     if '--forms' in sys.argv:
         return main_forms()
+    if '--caller' in sys.argv:
+        return main_caller()
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
     write = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
     if write in args:
