@@ -326,6 +326,10 @@ extern "C" int gator_c3_state(gator_ctx* c, float* logit_bound) {
     if (!c) return fail(GATOR_EINVAL, "gator_c3_state: null ctx");
     return fused_c3_state(c, logit_bound);
 }
+extern "C" int gator_operand_state(gator_ctx* c, float* tile_ratio) {
+    if (!c) return fail(GATOR_EINVAL, "gator_operand_state: null ctx");
+    return fused_operand_state(c, tile_ratio);
+}
 
 extern "C" int gator_device_status(gator_ctx* c, int32_t sync) {
     if (!c) return fail(GATOR_EINVAL, "gator_device_status: null ctx");

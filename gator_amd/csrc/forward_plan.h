@@ -17,7 +17,7 @@ constexpr int kTiledTokens = 128;       // token slots per workgroup of the samp
 
 // The fused path's environment switches: read once per ctx, at gator_create (fused_api.hip: read_fused_options), which also applies
 // the rules that combine them and gator_config.arithmetic.  What only the weights or the device can tell (the config-3 guard, the
-// byte-lo round trip, the residual checks of the fp16 x 3 weight images) narrows them later by clearing a flag.  plan_forward turns them into launches.
+// byte-lo round trip, the tile-ratio check of the fp16 x 3 weight sets: fused_state.h h3_demote) narrows them later by clearing a flag.  plan_forward turns them into launches.
 struct FusedOptions {
     // encoder
     bool gat_x3 = true;                 // GATOR_GAT_X3 (default 1): GAT linears on split-precision bf16 MFMA; =0: fp32-input MFMA (k_gat only)
@@ -26,7 +26,7 @@ struct FusedOptions {
     bool gat8_lobyte = true;            // GATOR_GAT8_LOBYTE (default 1): k_gat8 streams the byte-lo image of its weights (H3B, gat_roles.hip); =0: the three fp16 planes.
                                         // Needs gat8 and gat8_h4; cleared unless every lo value survives the byte round trip (always, for finite weights)
     bool gat8_tail = true;              // GATOR_GAT8_TAIL (default 1): k_gat8 runs its samples' lifter and MDR joint tokens as its epilogue (round 6); =0: the two
-                                        // launches of gat_tail.hip.  Needs gat8, gat8_h4 and mdr_x3 = 2; cleared if jf128_h3 cannot hold the joint-feature weights;
+                                        // launches of gat_tail.hip.  Needs gat8, gat8_h4 and mdr_x3 = 2; cleared if one scale cannot hold the joint-feature weights (or a set it needs was demoted);
                                         // outside config 3 it also needs gat8_lobyte (forward_plan.h: plan_forward)
     bool gat_tiled_h4 = true;           // GATOR_GAT_TILED_H4 (default 1): the sample-tiled encoder's token-wise products on four partial products; =0: the exact six.  Off under exact arithmetic
     int gat_tiled = -1;                 // GATOR_GAT_TILED: -1 (default) by batch size (forward_plan.h: plan_tiled_samples), 0 never the sample-tiled encoder, 1 always; what GATOR_ENCODER_AUTO restores

@@ -251,12 +251,12 @@ int fused_create_gat(gator_ctx* c, FusedState* f, void* stream) {
         int rc = fused_repack_x3(f->gblk[0].qkv, f->gxbuf, ntiles, stream);
         if (rc) return rc;
         if (f->opt.gat_tiled_h4) {
-            float left = 0.f;
+            float& ratio = f->h3_tile_ratio[GATOR_H3SET_GAT_TILED];
             GATOR_TRY(f->gxbuf_h3.alloc((size_t)ntiles * kTileX3 * sizeof(float)));
             // the scale comes from the nine weight grids of each block (264 tiles), not from the mc / mdT / aoffT / f1b tables behind them
-            rc = fused_repack_h3(f->gblk[0].qkv, f->gxbuf_h3, ntiles, &f->gat_tiled_wshift, &left, stream, (int64_t)blk_tiles, 264);
-            if (rc == GATOR_OK && left > 1e-7f) rc = fail(GATOR_EUNSUPPORTED, "GAT weights span more than fp16 x 3 planes hold exactly: use GATOR_GAT_TILED_H4=0");
+            rc = fused_repack_h3(f->gblk[0].qkv, f->gxbuf_h3, ntiles, &f->gat_tiled_wshift, &ratio, stream, (int64_t)blk_tiles, 264);
             if (rc) return rc;
+            if (!h3_set_holds(ratio)) { f->gxbuf_h3.reset(); h3_demote(f, GATOR_H3SET_GAT_TILED); }      // the exact six products on gxbuf, as under GATOR_GAT_TILED_H4=0
         }
         if (f->opt.gat8) {
             rc = gat8_build_stream(f, stream);
@@ -395,12 +395,12 @@ int fused_create(gator_ctx* c, void* stream) {
             const int64_t ntiles = (dst + 2 * kTile - f->lay[0].wq) / kTile;
             GATOR_TRY(f->wxbuf.alloc((size_t)ntiles * kTileX3 * sizeof(float)));
             if (f->opt.mdr_x3 == 2) {     // three fp16 planes under one power-of-two scale (x3_common.h: the 4-product linears)
-                float left = 0.f;
-                rc = fused_repack_h3(f->lay[0].wq, f->wxbuf, ntiles, &f->mdr_wshift, &left, stream);
-                if (rc == GATOR_OK && left > 1e-7f) rc = fail(GATOR_EUNSUPPORTED, "MDR weights span more than fp16 x 3 planes hold exactly (residual %.2e of the largest weight): use GATOR_MDR_X3=1", left);
-            } else {
-                rc = fused_repack_x3(f->lay[0].wq, f->wxbuf, ntiles, stream);
+                float& ratio = f->h3_tile_ratio[GATOR_H3SET_MDR];
+                rc = fused_repack_h3(f->lay[0].wq, f->wxbuf, ntiles, &f->mdr_wshift, &ratio, stream);
+                if (rc) return rc;
+                if (!h3_set_holds(ratio)) h3_demote(f, GATOR_H3SET_MDR);      // the exact six products, as under GATOR_MDR_X3=1
             }
+            if (f->opt.mdr_x3 != 2) rc = fused_repack_x3(f->lay[0].wq, f->wxbuf, ntiles, stream);
             if (rc) return rc;
         }
         float* hbd = take(64);
@@ -417,11 +417,11 @@ int fused_create(gator_ctx* c, void* stream) {
         if (rc) return rc;
         f->jfeat128_p = d128;
         if (f->opt.mdr_x3 == 2) {      // the same eight tiles as three fp16 planes under their own power-of-two scale (k_gat8's fused tail, gat_roles.hip)
-            float left = 0.f;
+            float& ratio = f->h3_tile_ratio[GATOR_H3SET_JFEAT];
             GATOR_TRY(f->jf128_h3.alloc((size_t)8 * kTileX3 * sizeof(float)));
-            rc = fused_repack_h3(d128, f->jf128_h3, 8, &f->jf128_wshift, &left, stream);
-            if (rc == GATOR_OK && left > 1e-7f) { f->jf128_h3.reset(); f->opt.gat8_tail = false; }      // (the two tail launches stay)
+            rc = fused_repack_h3(d128, f->jf128_h3, 8, &f->jf128_wshift, &ratio, stream);
             if (rc) return rc;
+            if (!h3_set_holds(ratio)) { f->jf128_h3.reset(); h3_demote(f, GATOR_H3SET_JFEAT); }      // (the two tail launches stay)
         }
         const std::vector<float> jw = d2h(w.jfeat_w, 64 * 133);
         std::vector<float> j5(5 * 64);
@@ -749,6 +749,13 @@ int fused_c3_state(const gator_ctx* c, float* bound) {
     if (!f) return fail(GATOR_EUNSUPPORTED, "gator_c3_state: fused ctx only");
     if (bound) *bound = f->c3_logit_bound;
     return f->opt.c3_mdr ? 1 : 0;
+}
+
+int fused_operand_state(const gator_ctx* c, float* tile_ratio) {
+    const FusedState* f = c->fused;
+    for (int i = 0; i < 4; ++i)
+        if (tile_ratio) tile_ratio[i] = f ? f->h3_tile_ratio[i] : 0.f;
+    return f ? f->h3_demoted : 0;
 }
 
 int fused_set_encoder(gator_ctx* c, int mode) {

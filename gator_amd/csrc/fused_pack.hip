@@ -5,6 +5,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 namespace gator {
 namespace {
@@ -34,8 +35,8 @@ __global__ void k_repack_x3(const float* __restrict__ src, __bf16* __restrict__ 
     d[1024] = m;
     d[2048] = (__bf16)(r - (float)m);
 }
-// H3 tile [plane][s][lane][jj] <- three fp16 planes of scale * (fp32 tile element); res: max residual (as float bits)
-__global__ void k_repack_h3(const float* __restrict__ src, _Float16* __restrict__ dst, int64_t total, float scale, unsigned* __restrict__ res) {
+// H3 tile [plane][s][lane][jj] <- three fp16 planes of scale * (fp32 tile element)
+__global__ void k_repack_h3(const float* __restrict__ src, _Float16* __restrict__ dst, int64_t total, float scale) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= total) return;
     const int jj = e & 7, lane = (e >> 3) & 63, s = (e >> 9) & 1;
@@ -44,38 +45,41 @@ __global__ void k_repack_h3(const float* __restrict__ src, _Float16* __restrict_
     const _Float16 h = (_Float16)x;
     const float r = x - (float)h;
     const _Float16 m = (_Float16)r;
-    const float r2 = r - (float)m;
-    const _Float16 l = (_Float16)r2;
     _Float16* d = dst + tile * (2 * kTileX3) + (s * 64 + lane) * 8 + jj;
     d[0] = h;
     d[1024] = m;
-    d[2048] = l;
-    const float left = fabsf(r2 - (float)l);
-    if (left > 0.f) atomicMax(res, __float_as_uint(left));
+    d[2048] = (_Float16)(r - (float)m);
 }
-// max |w| over the tiles with (tile % period) < live (period 0: all of them)
-__global__ void k_absmax_tiles(const float* __restrict__ w, int64_t n, unsigned* __restrict__ out, int64_t period, int64_t live) {
+// out[tile] = max |w| of that tile; one 256-thread block per tile
+__global__ void k_absmax_per_tile(const float* __restrict__ w, float* __restrict__ out) {
+    __shared__ float part[4];
+    const float* t = w + (int64_t)blockIdx.x * kTile;
     float m = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        if (period == 0 || (i / kTile) % period < live) m = fmaxf(m, fabsf(w[i]));
+    for (int i = threadIdx.x; i < kTile; i += 256) m = fmaxf(m, fabsf(t[i]));
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
 }
 }  // namespace
 
-int fused_repack_h3(const float* src_tiles, float* dst_tiles, int64_t ntiles, int* shift, float* residual, void* stream, int64_t period, int64_t live) {
+int fused_repack_h3(const float* src_tiles, float* dst_tiles, int64_t ntiles, int* shift, float* tile_ratio, void* stream, int64_t period, int64_t live) {
     hipStream_t st = (hipStream_t)stream;
     const int64_t total = ntiles * kTile;
-    DevBuf<unsigned> tmp;      // freed on every return path
-    GATOR_TRY(tmp.alloc(2 * sizeof(unsigned)));
-    unsigned* d = tmp;
-    GATOR_HIP_CHECK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned), st));
-    k_absmax_tiles<<<512, 256, 0, st>>>(src_tiles, total, d, period, live);
-    unsigned bits[2] = {0, 0};
-    GATOR_HIP_CHECK(hipMemcpyAsync(bits, d, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    DevBuf<float> tmp;      // freed on every return path
+    GATOR_TRY(tmp.alloc((size_t)ntiles * sizeof(float)));
+    k_absmax_per_tile<<<(unsigned)ntiles, 256, 0, st>>>(src_tiles, tmp.get());
+    GATOR_HIP_CHECK(hipGetLastError());
+    std::vector<float> tmax((size_t)ntiles);
+    GATOR_HIP_CHECK(hipMemcpyAsync(tmax.data(), tmp.get(), (size_t)ntiles * sizeof(float), hipMemcpyDeviceToHost, st));
     GATOR_HIP_CHECK(hipStreamSynchronize(st));
-    float wmax;
-    memcpy(&wmax, &bits[0], sizeof(wmax));
+    float wmax = 0.f, wmin = 0.f;      // the largest tile maximum, and the smallest one of a tile that holds a weight at all
+    for (int64_t t = 0; t < ntiles; ++t) {
+        if (period != 0 && t % period >= live) continue;
+        const float m = tmax[(size_t)t];
+        if (m > wmax) wmax = m;
+        if (m > 0.f && (wmin == 0.f || m < wmin)) wmin = m;
+    }
     int sh = 0;
     if (wmax > 0.f && std::isfinite(wmax)) {
         int e;
@@ -84,14 +88,11 @@ int fused_repack_h3(const float* src_tiles, float* dst_tiles, int64_t ntiles, in
         if (sh > 24) sh = 24;
         if (sh < -16) sh = -16;
     }
-    k_repack_h3<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(src_tiles, (_Float16*)dst_tiles, total, std::ldexp(1.0f, sh), d + 1);
-    GATOR_HIP_CHECK(hipGetLastError());
-    GATOR_HIP_CHECK(hipMemcpyAsync(bits, d, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    GATOR_HIP_CHECK(hipStreamSynchronize(st));
-    float left;
-    memcpy(&left, &bits[1], sizeof(left));
     *shift = sh;
-    *residual = wmax > 0.f ? left / std::ldexp(wmax, sh) : 0.f;
+    *tile_ratio = wmax > 0.f ? wmin / wmax : 1.f;
+    if (!h3_set_holds(*tile_ratio)) return GATOR_OK;      // the caller takes the form without a shared scale
+    k_repack_h3<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(src_tiles, (_Float16*)dst_tiles, total, std::ldexp(1.0f, sh));
+    GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;
 }
 

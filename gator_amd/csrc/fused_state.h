@@ -64,6 +64,10 @@ struct FusedState {
     DevBuf<float> jf128_h3;             // get_joint_feature columns 5..132 as H3 tiles [2][4] of 2^jf128_wshift * w (k_gat8's fused tail)
     int jf128_wshift = 0;
     int mdr_wshift = 0;                 // mdr_x3 = 2: wxbuf holds three fp16 planes of 2^mdr_wshift * w
+    // What the weights decided about the three-plane weight sets (x3_common.h: kH3MinTileRatio; gator_operand_state): the smallest
+    // tile ratio of each set that was looked at (0: not looked at), and which default forms this ctx gave up for the exact ones
+    float h3_tile_ratio[4] = {0.f, 0.f, 0.f, 0.f};      // [GATOR_H3SET_*]
+    int h3_demoted = 0;                 // bit GATOR_H3SET_*: that set's four-product form was demoted (gat8_h4 / gat_tiled_h4 off, mdr_x3 2 -> 1, fused tail off)
     float c3_logit_bound = 0.f;         // bound on |q . k| / sqrt(d_k) of the MDR self-attention in the exp2 domain, from the weights (fused_create)
     DevBuf<void> up_w2;                 // fp16 [ob/2][28][2][tap 3][plane 2][64][8]  scaled hi/lo split of upsample_conv.weight
     float up_w2_unscale = 1.f;          // 2^-(weight shift + activation shift), applied to the finished sums
@@ -106,6 +110,22 @@ struct FusedState {
     const float* jfeat128_p = nullptr;  // its columns 5..132 (feat) packed [2 nb][4 kb]
     const float* posj_T = nullptr;      // [2] T-layout tiles of pos_j_id_embed[1..J]
 };
+
+// A three-plane weight set whose tiles differ too much in magnitude for one scale (x3_common.h: h3_set_holds) is not packed: the ctx gives up the
+// form that reads it for the one the environment switch of that set selects -- slower, never less accurate -- and with it the options that need it
+// (the rules of read_fused_options, applied again).  Recorded for gator_operand_state.
+inline void h3_demote(FusedState* f, int set) {
+    FusedOptions& o = f->opt;
+    f->h3_demoted |= 1 << set;
+    if (set == GATOR_H3SET_GAT8) o.gat8_h4 = false;
+    if (set == GATOR_H3SET_GAT_TILED) o.gat_tiled_h4 = false;
+    if (set == GATOR_H3SET_MDR) o.mdr_x3 = 1;
+    if (set == GATOR_H3SET_JFEAT) o.gat8_tail = false;
+    o.gat8_lobyte = o.gat8_lobyte && o.gat8_h4;
+    o.gat8_tail = o.gat8_tail && o.gat8_h4 && o.mdr_x3 == 2;
+    o.c3_mdr = o.c3_mdr && o.mdr_x3 == 2;
+    o.c3_encoder = o.c3_encoder && o.gat8_h4 && o.gat_tiled_h4;
+}
 
 // fused_pack.hip
 int fused_pack_linear(const float* W, int64_t wsn, int64_t wsk, int N, int K, float* dst, void* stream);   // -> [NB][KB] tiles

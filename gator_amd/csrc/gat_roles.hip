@@ -1467,12 +1467,14 @@ int gat8_build_stream(FusedState* f, void* stream) {
     GATOR_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
     GATOR_TRY(f->g8stream.alloc((size_t)kStreamFloats * sizeof(float)));
     if (f->opt.gat8_h4) {      // the four-product form streams three fp16 planes of 2^shift * w: the fp32 tiles are put in stream order
-        float left = 0.f;  // first, so that the shift comes from exactly the weights the kernel multiplies (not the tables in between)
+        float& ratio = f->h3_tile_ratio[GATOR_H3SET_GAT8];  // first, so that the shift comes from exactly the weights the kernel multiplies (not the tables in between)
         GATOR_TRY(h3.alloc(idx.size() * kTile * sizeof(float)));
         k_gather_tiles<kTile><<<(unsigned)idx.size(), 128, 0, (hipStream_t)stream>>>(f->gblk[0].qkv, d_idx.get(), h3.get());
-        int rc = fused_repack_h3(h3, f->g8stream, (int64_t)idx.size(), &f->gat8_wshift, &left, stream);
-        if (rc == GATOR_OK && left > 1e-7f) rc = fail(GATOR_EUNSUPPORTED, "GAT weights span more than fp16 x 3 planes hold exactly: use GATOR_GAT8_H4=0");
+        int rc = fused_repack_h3(h3, f->g8stream, (int64_t)idx.size(), &f->gat8_wshift, &ratio, stream);
         if (rc) return rc;
+        if (!h3_set_holds(ratio)) h3_demote(f, GATOR_H3SET_GAT8);      // the exact six products on the X3 stream below, as under GATOR_GAT8_H4=0
+    }
+    if (f->opt.gat8_h4) {
         if (f->opt.gat8_lobyte) {      // the byte-lo image of the same stream (H3B): used only if every lo value survives the round trip
             DevBuf<unsigned> d_bad;
             GATOR_TRY(d_bad.alloc(sizeof(unsigned)));

@@ -150,6 +150,7 @@ int fused_set_joint_regressor(gator_ctx* c, const int32_t* row, const int32_t* c
 int fused_forward_joints(gator_ctx* c, const float* pose2d, int B, float* joints, float* pose3d, float* verts, void* stream);
 int fused_set_encoder(gator_ctx* c, int mode);
 int fused_c3_state(const gator_ctx* c, float* bound);
+int fused_operand_state(const gator_ctx* c, float* tile_ratio);      // (a ctx without fused state: nothing demoted)
 void fused_disable_persist(gator_ctx* c);      // from now on the four MDR stages run as four launches on this ctx
 int fused_set_graph_replay(gator_ctx* c, int on);          // returns the number of graph launches so far (>= 0)
 int fused_encoder_for_batch(const gator_ctx* c, int B);      // GATOR_ENCODER_SAMPLE / _TILED: what the ctx's own AUTO policy gives a batch of B

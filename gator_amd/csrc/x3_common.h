@@ -236,10 +236,23 @@ __device__ __forceinline__ f32x16 g2_mma_wa(const G2& W, const X1& a, f32x16 acc
 // fused_pack.hip: fp32 packed tiles [g][lane][4] -> X3 tiles, same tile indices
 int fused_repack_x3(const float* src_tiles, float* dst_tiles, int64_t ntiles, void* stream);
 // ... -> H3 tiles (three fp16 planes of 2^shift * w); *shift is chosen from max|w| over the tiles with (tile % period) < live (the
-// weight grids; period 0 = every tile), so that 2^13 <= max|2^shift w| < 2^14.  The three planes hold 2^shift w down to 2^-24
-// absolute, i.e. every weight to 2^-38 of the largest one ("exact" in this code base means that); *residual is the largest
-// |2^shift w - (hi + mid + lo)| relative to max|2^shift w| -- at most 2^-39 by construction, reported as a sanity value.
-int fused_repack_h3(const float* src_tiles, float* dst_tiles, int64_t ntiles, int* shift, float* residual, void* stream,
+// weight grids; period 0 = every tile), so that 2^13 <= max|2^shift w| < 2^14.  The three planes hold 2^shift w down to fp16's
+// smallest subnormal, 2^-24 absolute (half of it as rounding error), i.e. every weight to 2^-38 of the LARGEST ONE OF THE SET.  That
+// is exact to fp32 only for weights near the largest: a tile whose own max|w| is r times the set's keeps its weights to 2^-38 / r of
+// its largest, 38 - log2(1 / r) bits.  *tile_ratio is the smallest such r over the live tiles that hold a non-zero weight (an all-zero
+// tile is exact at any scale).  The set is packed only if h3_set_holds(*tile_ratio); otherwise dst_tiles is left untouched and the
+// caller takes the form that has no shared scale (the three-way bf16 split: every weight to 2^-24 of ITSELF).
+//
+// kH3MinTileRatio, derived from the formats, not measured: the planes hold a weight to 2^-25 absolute (half of fp16's smallest
+// subnormal) in units where the set's largest weight is at least 2^13, i.e. to 2^-38 max|w_set|.  A tile's typical (rms) weight is about
+// a quarter of the tile's largest (the largest of 1 024 Gaussian draws is 3.2 sigma), so at ratio r it is 2^-2 r max|w_set| and carries
+// a relative error of up to 2^-36 / r.  The bar is 2^-24: one fp32 rounding of the product this weight enters, which the reference's
+// own arithmetic commits on every product it accumulates (and the size of what the four-product form drops, a_lo (w_mid + w_lo)).
+// 2^-36 / r <= 2^-24 gives r >= 2^-12.  The weight dynamic range the default arithmetic supports is therefore 2^12 between the
+// 32 x 32 tiles of one weight set; beyond it the ctx takes the exact forms (tests/test_host_rescale_refs.py restates split and ratio).
+constexpr float kH3MinTileRatio = 0x1p-12f;
+inline bool h3_set_holds(float tile_ratio) { return tile_ratio >= kH3MinTileRatio; }      // (false for NaN)
+int fused_repack_h3(const float* src_tiles, float* dst_tiles, int64_t ntiles, int* shift, float* tile_ratio, void* stream,
                     int64_t period = 0, int64_t live = 0);
 
 }  // namespace gator

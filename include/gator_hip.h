@@ -63,7 +63,14 @@ typedef struct {
  * Operand range of that default: every value that feeds a token-wise linear and every coarse vertex must stay below 4 094 in
  * magnitude (16 x value must fit an fp16 plane); beyond it the plane overflows, the vertices of that forward come out NaN and the
  * NEXT call on the ctx (or gator_device_status) returns GATOR_EDEVICE -- loud, never silently wrong.  Trained checkpoints are
- * orders of magnitude inside (LayerNorm outputs, GELU hiddens, metres).  gator_config.arithmetic = GATOR_ARITH_EXACT_SPLIT (or the environment
+ * orders of magnitude inside (LayerNorm outputs, GELU hiddens, metres).
+ * Weight dynamic range of that default: the three fp16 weight planes of the four-product linears share ONE power-of-two scale per weight
+ * set (k_gat8's stream, the sample-tiled encoder's grids, the MDR layers + head, get_joint_feature), which holds every weight to 2^-38 of
+ * the set's LARGEST one -- exact to fp32 only while the 32 x 32 tiles of a set stay within 2^12 of each other in max|w|.  gator_create
+ * measures that; a set beyond it is not packed and its products run on the exact three-way bf16 split for this ctx (slower, never less
+ * accurate; gator_operand_state reports it).  A function-preserving rescaling of a checkpoint (q against k, v against proj, fc1 against
+ * fc2 by 2^k: what weight decay does) therefore never changes the result beyond fp32 noise (tests/test_gpu_rescaled_weights.py).
+ * gator_config.arithmetic = GATOR_ARITH_EXACT_SPLIT (or the environment
  * variables it stands for, read by gator_create) selects the forms without a rounded operand and without that limit (GATOR_MDR_X3=1 GATOR_UPSAMPLE_X3=1 GATOR_GAT8_H4=0 GATOR_GAT_TILED_H4=0: exact
  * three-way bf16 split, six products) or the fp32-input MFMA form of a stage (GATOR_GAT_X3 / GATOR_MDR_X3 / GATOR_UPSAMPLE_X3 = 0);
  * all forms are the same accuracy class and under test (tests/test_gpu_x3.py; statistics: profiles/r04_error_budget.md). */
@@ -143,6 +150,17 @@ int gator_forward_bf16(gator_ctx* ctx, const float* pose2d, int32_t batch, float
  * switches the guard off.  Returns 1 if the MDR layers run on one plane under gator_forward_bf16, 0 if not (guard, GATOR_C3_MDR=0 or a ctx without the
  * default operand forms), negative on error; *logit_bound (may be NULL) receives the bound. */
 int gator_c3_state(gator_ctx* ctx, float* logit_bound);
+/* What gator_create decided from the weights about the default arithmetic's three-plane weight sets (weight dynamic range, above).  The four
+ * sets share one power-of-two scale each; a set whose smallest 32 x 32 tile is below 2^-12 of its largest is not packed, and the ctx runs the
+ * products that would have read it on the exact three-way bf16 split instead (slower, never less accurate).  Returns a bitmask of the sets that
+ * were demoted (bit GATOR_H3SET_*; 0 for a ctx that uses none of them: exact arithmetic, GATOR_IMPL_BASIC), negative on error; tile_ratio[4]
+ * (may be NULL) receives each set's smallest ratio of a non-zero tile's max|w| to the set's max|w|, 0 for a set that was not looked at. */
+typedef enum { GATOR_H3SET_GAT8 = 0,      /* k_gat8's weight stream; demoted: the exact six products (as GATOR_GAT8_H4=0), no fused tail */
+               GATOR_H3SET_GAT_TILED = 1, /* the sample-tiled encoder's grids; demoted: as GATOR_GAT_TILED_H4=0 */
+               GATOR_H3SET_MDR = 2,       /* the three MDR layers and the head; demoted: as GATOR_MDR_X3=1, no fused tail */
+               GATOR_H3SET_JFEAT = 3      /* get_joint_feature for k_gat8's fused tail; demoted: the two tail launches (as GATOR_GAT8_TAIL=0) */
+} gator_h3set;
+int gator_operand_state(gator_ctx* ctx, float* tile_ratio);
 int gator_upsample_bf16(gator_ctx* ctx, const float* vert431, int32_t batch, float* verts, void* stream);
 
 /* Stage entry points (parity tests; same semantics as the reference sub-modules):
