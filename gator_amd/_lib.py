@@ -51,6 +51,25 @@ class CameraTargetsArgs(ctypes.Structure):     # include/gator_hip.h: gator_came
                                         'joint_img_out', 'fit_error', 'valid')]
 
 
+NOISE_COCO, NOISE_STATS, NOISE_DETECTIONS = 0, 1, 2      # include/gator_hip.h: GATOR_NOISE_*
+NOISE_COCO_JOINTS = 17
+
+
+class CocoNoiseModel(ctypes.Structure):        # include/gator_hip.h: gator_coco_noise_model (a host struct)
+    _fields_ = [('var', ctypes.c_double * 17), ('log_ks', ctypes.c_double * 3), ('jitter_prob', ctypes.c_double * 17 * 2),
+                ('miss_prob', ctypes.c_double * 17 * 3), ('inv_prob', ctypes.c_double * 17), ('partner', ctypes.c_int32 * 17),
+                ('n_jitter', ctypes.c_int32), ('n_miss', ctypes.c_int32), ('n_inv', ctypes.c_int32), ('n_good', ctypes.c_int32),
+                ('tier_valid', ctypes.c_int32 * 2), ('reserved', ctypes.c_int32)]
+
+
+class PreprocessNoiseArgs(ctypes.Structure):   # include/gator_hip.h: gator_preprocess_noise_args (device pointers; coco: host)
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'batch', 'n_joints', 'comps', 'mode', 'n_pairs', 'res_w', 'res_h')] + \
+        [('seed', ctypes.c_uint64), ('step', ctypes.c_int64), ('sample_offset', ctypes.c_int64)] + \
+        [(n, ctypes.c_void_p) for n in ('step_dev', 'joints', 'joint_valid', 'detections', 'rot_deg', 'flip', 'flip_pairs')] + \
+        [('coco', ctypes.POINTER(CocoNoiseModel))] + \
+        [(n, ctypes.c_void_p) for n in ('stats', 'pose2d', 'valid', 'noisy_crop', 'area', 'decisions')]
+
+
 LIFT_HUMAN36, LIFT_COCO = 0, 1                  # include/gator_hip.h: GATOR_LIFT_*
 ABI_VERSION = 2                                # include/gator_hip.h: GATOR_ABI_VERSION this binding was written against
 EDEVICE, EDEVICE_DEFERRED = -7, -8
@@ -97,6 +116,7 @@ SIGNATURES = {
     'gator_sequence_errors': (_I, [_P, _I, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
     'gator_batch_prepare_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     'gator_camera_targets_f32': (_I, [ctypes.POINTER(CameraTargetsArgs), _P]),
+    'gator_preprocess_noise_f32': (_I, [ctypes.POINTER(PreprocessNoiseArgs), _P]),
     'gator_crop_joints_f32':(_I, [_P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
     'gator_fit_camera_f32': (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _I, _P, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P]),
     'gator_smpl_create': (_I, [_P, ctypes.POINTER(_P)]),

@@ -4,9 +4,10 @@
   root_to_camera(pose, R)            the root orientation composed with the camera rotation        -> gator_batch_prepare_f32
   camera_frame_batch(layer, ...)     (inputs, targets, meta), the triple the datasets return       -> gator_batch_prepare_f32,
                                      the layer, gator_camera_targets_f32, preprocess.preprocess_chain
+                                     or, with noise=, gator_amd.noise.noisy_input
 
-The kernels are csrc/train_batch.hip.  Every output is a pure function of the inputs; the detector noise (lib/noise_utils.py) is not
-built here.  There is no CPU path."""
+The kernels are csrc/train_batch.hip.  Every output is a pure function of the inputs -- with noise=, of the inputs, noise_seed and
+noise_step: the detector noise (lib/noise_utils.py, generate_syn_error) is gator_amd.noise's.  There is no CPU path."""
 import ctypes
 
 import numpy as np
@@ -125,7 +126,7 @@ def _checked_pairs(flip_pairs, n_lift, who):
 
 def camera_frame_batch(layer, pose, shape, *, trans=None, cam_R=None, cam_t=None, compensate_root=False, focal, princpt, regressor_h36m,
                        regressor_coco=None, input_joint_name='human36', joint_cam=None, joint_img=None, fitting_thr=float('inf'),
-                       rot_deg=None, flip=None, flip_pairs=(), res=(288, 384)):
+                       rot_deg=None, flip=None, flip_pairs=(), res=(288, 384), noise=None, noise_seed=0, noise_step=0):
     """The deterministic part of a training dataset's __getitem__ for a batch on the device -> (inputs, targets, meta), the triple the
     datasets return (data/Human36M/dataset.py:403-407):
 
@@ -147,12 +148,16 @@ def camera_frame_batch(layer, pose, shape, *, trans=None, cam_R=None, cam_t=None
     rot_deg [B], flip [B], flip_pairs: the augmentation, applied to lift_pose3d (j3d_processing, lib/aug_utils.py:67-83) and to the 2D
     input -- never to the mesh, as in the reference.
 
-    The detector noise (lib/noise_utils.synthesize_pose, generate_syn_error; replace_joint_img) is NOT built.  meta['joint_img'] is the
-    pixel-space input before the crop -- where the reference adds it -- so a noise step can perturb it and call
-    preprocess.preprocess_chain(noisy, rot_deg, flip, flip_pairs, res=res) for its own 'pose2d'.
+    noise: a gator_amd.noise.CocoDetectorNoise or ErrorStatsNoise (use_gt_input: False, the reference's replace_joint_img): the
+    reference adds the detector noise AFTER the crop affine, in crop pixels, before the flip -- not in image pixels -- so
+    inputs['pose2d'] is then noise.noisy_input(meta['joint_img'], noise, seed=noise_seed, step=noise_step, rot_deg=.., flip=..,
+    flip_pairs=.., res=res), bit for bit; meta['joint_img'] stays the clean pixel-space input and meta['joint_crop_noisy'] [B,Jl,2]
+    holds the perturbed crop-space joints.  noise_step: an int or a one-element int64 tensor on the device (see noisy_input; row b is
+    sample b of the stream -- a sharded caller calls noisy_input itself with its sample_offset).  With noise=None (the default)
+    nothing changes.
 
     Launches: gator_batch_prepare_f32, the layer's two (metres, no translation, no centring), gator_camera_targets_f32 writing the mesh
-    into the layer's vertex buffer in place, and preprocess_chain.  Nothing waits for the device."""
+    into the layer's vertex buffer in place, and preprocess_chain (or noisy_input's two or three).  Nothing waits for the device."""
     who = 'camera_frame_batch'
     for name in ('num_verts', 'num_joints', 'num_betas', 'forward'):
         if not hasattr(layer, name):
@@ -210,6 +215,14 @@ def camera_frame_batch(layer, pose, shape, *, trans=None, cam_R=None, cam_t=None
         raise ValueError('%s: res must be (width, height)' % who)
     if res[0] < 1 or res[1] < 1:
         raise ValueError('%s: res %s must be positive' % (who, (res,)))
+    if noise is not None:
+        from . import noise as gator_noise
+        if not isinstance(noise, (gator_noise.CocoDetectorNoise, gator_noise.ErrorStatsNoise)):
+            raise ValueError('%s: noise must be a gator_amd.noise.CocoDetectorNoise or ErrorStatsNoise, got %s' % (who, type(noise).__name__))
+        if isinstance(noise, gator_noise.CocoDetectorNoise) and Jl < gator_noise.COCO_JOINTS:
+            raise ValueError('%s: CocoDetectorNoise needs the %d COCO joints first, the lift set has %d' % (who, gator_noise.COCO_JOINTS, Jl))
+        if isinstance(noise, gator_noise.ErrorStatsNoise) and noise.n_joints != Jl:
+            raise ValueError('%s: the error table has %d joints, the lift set %d' % (who, noise.n_joints, Jl))
     _lib.need_device(who, pose)
 
     with torch.cuda.device(dev):
@@ -233,9 +246,15 @@ def camera_frame_batch(layer, pose, shape, *, trans=None, cam_R=None, cam_t=None
         valid = torch.empty((B, 3), device=dev, dtype=torch.float32)
         _launch_camera_targets(verts, joints, trans, cam_t, R, compensate_root, focal, princpt, reg_h, reg_c, LIFT_SETS[input_joint_name],
                                joint_cam, joint_img, rot, fl, pairs, thr, SMPL_ROOT, verts, reg3d, lift3d, img, fit, valid)
-        pose2d, input_valid = preprocess.preprocess_chain(img, rot, fl, pair_list, res=res)
+        if noise is None:
+            pose2d, input_valid = preprocess.preprocess_chain(img, rot, fl, pair_list, res=res)
+        else:
+            pose2d, input_valid, crop_noisy = gator_noise.noisy_input(img, noise, seed=noise_seed, step=noise_step, rot_deg=rot, flip=fl,
+                                                                      flip_pairs=pair_list, res=res)
     inputs = {'pose2d': pose2d}
     targets = {'mesh': verts, 'lift_pose3d': lift3d, 'reg_pose3d': reg3d}
     meta = {'mesh_valid': valid[:, 0].reshape(B, 1, 1).expand(B, NV, 1), 'lift_pose3d_valid': valid[:, 1].reshape(B, 1, 1).expand(B, Jl, 1),
             'reg_pose3d_valid': valid[:, 2].reshape(B, 1, 1).expand(B, Jh, 1), 'fit_error': fit, 'input_valid': input_valid, 'joint_img': img}
+    if noise is not None:
+        meta['joint_crop_noisy'] = crop_noisy
     return inputs, targets, meta

@@ -459,6 +459,85 @@ int gator_batch_prepare_f32(const float* pose, const float* R, const float* beta
                             int32_t root_idx, float* pose_out, float* betas_out, void* stream);
 int gator_camera_targets_f32(const gator_camera_targets_args* args, void* stream);
 
+/* The training input with the detector's errors on it (use_gt_input: False, every *_train_*.yml of the reference): the input chain of
+ * gator_preprocess_chain_f32 with the datasets' replace_joint_img step in its place (data/Human36M/dataset.py:369-389, 421-453) --
+ * tight box -> process_bbox -> crop affine with rotation -> float32 crop joints -> NOISE in crop pixels -> flip_2d_joint on the
+ * float32 joints -> /[W,H] -> standardise.  gator_amd/csrc/detector_noise.hip; gator_amd.noise; DESIGN.md "Detector noise".
+ *
+ * mode GATOR_NOISE_COCO: lib/noise_utils.synthesize_pose on joints 0..16 (n_joints >= 17; later rows, the pelvis and neck of a 19-joint
+ *   input, keep their clean values), with `area` = the product of the side lengths of the tight box's corners after the affine
+ *   (dataset.py:425-431).  It is the reference's algorithm candidate for candidate -- per joint 500 jitter, 2000 miss around each
+ *   centre, 500 inversion and 125 good candidates (the model's n_* fields), accepted under the reference's distance masks, the k-th
+ *   accepted one taken, one of the five cases chosen with the tier's probabilities renormalised over the cases that found a point --
+ *   with numpy's generators replaced by the stream below.  near_joints is empty and num_overlap 0 as at every call site: no swap case.
+ *   A joint's centres are its own current position and, when it has a partner whose joint_valid > 0, the partner's current position:
+ *   the lower joint of a pair is perturbed first and the higher one sees the perturbed (possibly zeroed) lower one.  Invalid joints are
+ *   perturbed too; the number of valid joints among 0..16 picks the tier.  A joint whose cases all come up empty becomes (0, 0).
+ *   fp64 throughout, no contracted multiply-add; the chosen point is rounded to float32 once, when it is stored.
+ * mode GATOR_NOISE_STATS: generate_syn_error (dataset.py:143-155, 440-446) from stats [n_joints,5] float64 = (mean x, mean y, std x,
+ *   std y, weight) per joint: noise = float32(mean + std z), z by Box-Muller (z_x = sqrt(-2 ln u1) cos(2 pi u2), z_y = .. sin ..),
+ *   applied where float32(weight) > u3, as float32: crop + noise / 256 * [W, H].
+ * mode GATOR_NOISE_DETECTIONS: the test split's branch: `detections` [batch, n_joints, comps] (a detector's joints in image pixels)
+ *   go through the affine of the box of `joints` in their place.  Nothing is drawn.
+ *
+ * The stream.  Key = seed.  The word of draw site (set, joint j, index i) of sample b is output word k of the Philox4x32 block
+ * (GATOR_PHILOX_ROUNDS = 7 rounds, the dropout masks' generator) with the counter
+ *     c0 = i,   c1 = j | set << 8,   c2 = low 32 bits of (sample_offset + b),   c3 = low 32 bits of step
+ * and a uniform is (word + 0.5) * 2^-32 in fp64, an index into n items (word * n) >> 32 in 64-bit integers.  Sets:
+ *     0 jitter, 1 miss around the joint, 2 miss around the partner, 3 inversion, 4 good:  candidate i, word 0 -> angle = 2 pi u,
+ *                                                                                         word 1 -> r = lo + (hi - lo) u
+ *     5 picks:  i = 0: words 0..3 -> the index among the accepted jitter / miss (n_miss0 + n_miss1 / 4 entries) / inversion / good
+ *               points;  i = 1: word 0 -> the case (numpy's choice: the normalised cumulative sum searched from the right)
+ *     6 the reference's resampled quarter of the partner's miss points:  entry i of that list, word 0 -> an index into the n_miss1 points
+ *     7 stats:  i = 0: words 0, 1 -> u1, u2 of Box-Muller, word 2 -> u3
+ * A sample's row depends on (seed, step, sample_offset + b) and its own inputs only: the same bits whatever the batch or its sharding.
+ * step_dev (DEVICE int64, or NULL) replaces `step` when given: a captured graph draws fresh noise per replay when the caller advances it.
+ *
+ * All array pointers are device pointers; `coco` is a HOST pointer, copied at the call.  joints [batch, n_joints, comps] float32, image
+ * pixels (x and y first); joint_valid [batch, n_joints] float32 or NULL (all valid); rot_deg [batch], flip [batch] int32, each may be
+ * NULL; flip_pairs [n_pairs,2] int32 (a pair beyond n_joints is skipped).  Outputs: pose2d [batch, n_joints, 2]; valid [batch] int32 (0
+ * where process_bbox rejects the box: that sample's pose2d and noisy_crop are zeros); noisy_crop [batch, n_joints, 2] float32, the
+ * perturbed joints in crop pixels before the flip; area [batch] float64 (required for GATOR_NOISE_COCO, else may be NULL); decisions
+ * [batch,17,8] int32 or NULL (GATOR_NOISE_COCO): the accepted counts of sets 0..4, the case (0 jitter, 1 miss, 2 inversion, 4 good, -1
+ * zeroed), the picked index, and for a miss taken from the partner's points the index into them (else -1).
+ * Two launches (three for GATOR_NOISE_COCO) on `stream`; no allocation, no synchronisation, no atomics; capturable.  batch == 0 is
+ * GATOR_OK.  GATOR_EINVAL with a text, before any launch: NULL args or a required pointer, struct_size not this header's, n_joints
+ * outside 1..32, comps < 2, a resolution < 1, an unknown mode, GATOR_NOISE_COCO with fewer than 17 joints, without model or area, or with
+ * a model whose partner table is no involution inside 0..16 or whose counts lie outside 1..2^20, GATOR_NOISE_STATS without stats,
+ * GATOR_NOISE_DETECTIONS without detections, sample_offset < 0 or sample_offset + batch > 2^32. */
+#define GATOR_NOISE_COCO 0
+#define GATOR_NOISE_STATS 1
+#define GATOR_NOISE_DETECTIONS 2
+#define GATOR_NOISE_COCO_JOINTS 17
+typedef struct {                     /* the rule table of synthesize_pose, as data (gator_amd.noise.CocoDetectorNoise fills it) */
+    double var[GATOR_NOISE_COCO_JOINTS];            /* (2 sigma_j)^2 */
+    double log_ks[3];                               /* log(0.10), log(0.50), log(0.85): dist = sqrt(-2 area var log_ks) */
+    double jitter_prob[2][GATOR_NOISE_COCO_JOINTS]; /* n_valid <= tier_valid[1], else */
+    double miss_prob[3][GATOR_NOISE_COCO_JOINTS];   /* n_valid <= tier_valid[0], <= tier_valid[1], else */
+    double inv_prob[GATOR_NOISE_COCO_JOINTS];
+    int32_t partner[GATOR_NOISE_COCO_JOINTS];       /* the symmetric joint, -1 for none */
+    int32_t n_jitter, n_miss, n_inv, n_good;        /* candidates per set */
+    int32_t tier_valid[2];                          /* 5, 10 */
+    int32_t reserved;
+} gator_coco_noise_model;
+typedef struct {
+    int32_t struct_size; /* = sizeof of this struct in the caller's header */
+    int32_t batch, n_joints, comps, mode, n_pairs, res_w, res_h;
+    uint64_t seed;
+    int64_t step, sample_offset;
+    const int64_t* step_dev;
+    const float *joints, *joint_valid, *detections, *rot_deg;
+    const int32_t *flip, *flip_pairs;
+    const gator_coco_noise_model* coco; /* HOST */
+    const double* stats;
+    float* pose2d;
+    int32_t* valid;
+    float* noisy_crop;
+    double* area;
+    int32_t* decisions;
+} gator_preprocess_noise_args;
+int gator_preprocess_noise_f32(const gator_preprocess_noise_args* args, void* stream);
+
 /* The demo's mesh overlay (demo/renderer.py) on the device: a batched software rasteriser for the weak-perspective camera
  * (gator_amd/csrc/render.hip derives the geometry; DESIGN.md "Renderer").  For a vertex (x, y, z) of the model's output and
  * cam = (sx, sy, tx, ty):  column = (1 + sx (x + tx)) / 2 * W,  row = (1 + sy (y + ty)) / 2 * H,  depth = z (smaller is nearer, fragments
