@@ -23,7 +23,7 @@ struct FusedOptions {
     bool gat_x3 = true;                 // GATOR_GAT_X3 (default 1): GAT linears on split-precision bf16 MFMA; =0: fp32-input MFMA (k_gat only)
     bool gat8 = true;                   // GATOR_GAT8 (default 1): the one-sample-per-workgroup encoder is the two-role kernel k_gat8; =0: k_gat.  Needs gat_x3
     bool gat8_h4 = true;                // GATOR_GAT8_H4 (default 1): k_gat8's token-wise products on four partial products (x3_common.h); =0: the exact six.  Off under exact arithmetic
-    bool gat8_lobyte = true;            // GATOR_GAT8_LOBYTE (default 1): k_gat8 streams the byte-lo image of its weights (H3B, gat_roles.hip); =0: the three fp16 planes.
+    bool gat8_lobyte = true;            // GATOR_GAT8_LOBYTE (default 1): k_gat8 streams the byte-lo image of its weights (H3B, gat8_forms.h); =0: the three fp16 planes.
                                         // Needs gat8 and gat8_h4; cleared unless every lo value survives the byte round trip (always, for finite weights)
     bool gat8_tail = true;              // GATOR_GAT8_TAIL (default 1): k_gat8 runs its samples' lifter and MDR joint tokens as its epilogue (round 6); =0: the two
                                         // launches of gat_tail.hip.  Needs gat8, gat8_h4 and mdr_x3 = 2; cleared if one scale cannot hold the joint-feature weights (or a set it needs was demoted);

@@ -271,17 +271,16 @@ int fused_create_gat(gator_ctx* c, FusedState* f, void* stream) {
     f->g_m1T = upload(mt);
     fill_tile(mt.data(), [&](int t, int j) { return (t < J && j < J) ? m2[(size_t)t * J + j] : 0.f; });
     f->g_m2T = upload(mt);
-    {   // per-block small vectors, concatenated in the order of gat_fused.hip's V_* enum (2048 floats per block)
-        std::vector<float> vv((size_t)kDepth * 2048);
+    {   // per-block small vectors, each at its offset of the block's table (fused_state.h: V_*)
+        std::vector<float> vv((size_t)kDepth * V_TOTAL);
         for (int i = 0; i < kDepth; ++i) {
             const GatBlockW& r = w.blk[i];
-            const struct { const float* p; int n; } parts[] = {{r.n1w, 128}, {r.n1b, 128}, {r.qkv_b, 384}, {r.proj_b, 128}, {r.gcn_bias, 128},
-                                                               {r.xl0_b, 128}, {r.xlb_b, 128}, {r.n2w, 128}, {r.n2b, 128}, {r.fc1_b, 512}, {r.fc2_b, 128}};
-            size_t off = (size_t)i * 2048;
+            const struct { const float* p; int at, n; } parts[] = {
+                {r.n1w, V_N1W, 128}, {r.n1b, V_N1B, 128}, {r.qkv_b, V_QKVB, 384}, {r.proj_b, V_PROJB, 128}, {r.gcn_bias, V_GCNB, 128}, {r.xl0_b, V_LIN0B, 128},
+                {r.xlb_b, V_BACKB, 128}, {r.n2w, V_N2W, 128}, {r.n2b, V_N2B, 128}, {r.fc1_b, V_FC1B, 512}, {r.fc2_b, V_FC2B, 128}};
             for (auto& pt : parts) {
                 const std::vector<float> h = d2h(pt.p, pt.n);
-                std::copy(h.begin(), h.end(), vv.begin() + off);
-                off += pt.n;
+                std::copy(h.begin(), h.end(), vv.begin() + (size_t)i * V_TOTAL + pt.at);
             }
         }
         f->g_vecs = upload(vv);
@@ -416,7 +415,7 @@ int fused_create(gator_ctx* c, void* stream) {
         rc = fused_pack_linear(w.jfeat_w + 5, 133, 1, 64, 128, d128, stream);
         if (rc) return rc;
         f->jfeat128_p = d128;
-        if (f->opt.mdr_x3 == 2) {      // the same eight tiles as three fp16 planes under their own power-of-two scale (k_gat8's fused tail, gat_roles.hip)
+        if (f->opt.mdr_x3 == 2) {      // the same eight tiles as three fp16 planes under their own power-of-two scale (k_gat8's fused tail, gat8_tail.h)
             float& ratio = f->h3_tile_ratio[GATOR_H3SET_JFEAT];
             GATOR_TRY(f->jf128_h3.alloc((size_t)8 * kTileX3 * sizeof(float)));
             rc = fused_repack_h3(d128, f->jf128_h3, 8, &f->jf128_wshift, &ratio, stream);

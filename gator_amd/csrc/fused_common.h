@@ -23,6 +23,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define GATOR_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ int kap(int r) { return (r & 3) + 8 * (r >> 2); }
+constexpr float kLog2e = 1.4426950408889634f;
 
 __device__ __forceinline__ f32x16 zero16() {
     f32x16 z;
@@ -113,17 +114,25 @@ __device__ __forceinline__ void dot16x2(const f32x16& A0, const f32x16& B0, f32x
     }
 }
 
-// per-channel vector (bias / norm weight) in T-layout: v[r] = vec[base + kap(r) + 4h]
-__device__ __forceinline__ f32x16 load_chanvec_T(const float* __restrict__ vec, int base, int h) {
+// per-channel vector (bias / norm weight) in T-layout: v[r] = vec[off + kap(r) + 4h], 4 b128 reads with two distinct addresses each
+// (against 32 scalar loads + 16 v_mov + 16 v_cndmask for the scalar-cache form below -- in k_mdr_layer 30 such vectors per tile
+// were 9 % of the kernel's VALU work).  Two names for one body: load_chanvec_T reads a vector nobody writes while the kernel
+// runs (weights in global memory) and says so with __restrict__; chanvec_lds reads a table the workgroup staged itself (LDS, or any
+// pointer without that promise).  The qualifier is the only difference, and it is not free to drop or add: k_gat8's fused tail
+// uses both, and comes out with other instructions under either single form.
+template <class PTR>
+__device__ __forceinline__ f32x16 chanvec_at(PTR vec, int off, int h) {
     f32x16 v;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(vec + base + 8 * g + 4 * h);
+        const f32x4 t = *reinterpret_cast<const f32x4*>(vec + off + 8 * g + 4 * h);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[4 * g + j] = t[j];
     }
     return v;
 }
+__device__ __forceinline__ f32x16 chanvec_lds(const float* vec, int off, int h) { return chanvec_at<const float*>(vec, off, h); }
+__device__ __forceinline__ f32x16 load_chanvec_T(const float* __restrict__ vec, int off, int h) { return chanvec_at<const float* __restrict__>(vec, off, h); }
 
 // a block stored as 4 float4 per lane ([g][lane][4]); same form for T- and C-layout blocks
 __device__ __forceinline__ f32x16 load_block(const float* __restrict__ p, int lane) {
@@ -148,6 +157,18 @@ __device__ __forceinline__ void store_block(float* __restrict__ p, int lane, con
     }
 }
 
+// a T-layout block of token t as 32 consecutive channels of a row-major row: `row` = the row's first channel of the block; this lane
+// half's four float4 (channels 8g + 4h ..)
+__device__ __forceinline__ void store_row_block(float* row, int h, const f32x16& v) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        f32x4 t;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) t[j] = v[4 * g + j];
+        *reinterpret_cast<f32x4*>(row + 8 * g + 4 * h) = t;
+    }
+}
+
 // erf to < 1 ulp (N. Juffa's two-range minimax form), both ranges evaluated and selected branch-free: ~23 VALU ops against
 // ~60 for the branchy library erff, which costs both sides whenever a wave's lanes straddle |x| = 1.
 __device__ __forceinline__ float erf_fast(float a) {
@@ -159,7 +180,7 @@ __device__ __forceinline__ float erf_fast(float a) {
     r = fmaf(r, t, -6.34846687e-1f);
     r = fmaf(r, t, -1.28717512e-1f);
     r = fmaf(r, t, -t);
-    const float big = copysignf(1.0f - __builtin_amdgcn_exp2f(r * 1.4426950408889634f), a);
+    const float big = copysignf(1.0f - __builtin_amdgcn_exp2f(r * kLog2e), a);
     float q = -5.96761703e-4f;
     q = fmaf(q, s, 4.99119423e-3f);
     q = fmaf(q, s, -2.67681349e-2f);
@@ -181,55 +202,46 @@ __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erf
 // slots per element instead of ~18 for the two-range erf form above (gelu_f), which stays for scalar uses.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x2 gelu_f2(f32x2 x) {
-    const f32x2 a = x * 0.70710678118654752440f;
-    f32x2 t;
-    t[0] = fminf(fabsf(a[0]), 4.3f);
-    t[1] = fminf(fabsf(a[1]), 4.3f);
-    f32x2 r = pk_fma(f32x2(-4.435285315e-05f), t, f32x2(4.369443071e-04f));
-    r = pk_fma(r, t, f32x2(-1.460381877e-03f));
-    r = pk_fma(r, t, f32x2(-8.251648338e-04f));
-    r = pk_fma(r, t, f32x2(2.830188636e-02f));
-    r = pk_fma(r, t, f32x2(-1.485066472e-01f));
-    r = pk_fma(r, t, f32x2(-9.184098145e-01f));
-    r = pk_fma(r, t, f32x2(-1.627909326e+00f));
-    r = pk_fma(r, t, f32x2(-9.999999783e-01f));
-    f32x2 e;
-    e[0] = __builtin_amdgcn_exp2f(r[0]);
-    e[1] = __builtin_amdgcn_exp2f(r[1]);
-    const f32x2 up = 1.0f - e;
-    f32x2 phi;
-    phi[0] = x[0] < 0.f ? e[0] : up[0];
-    phi[1] = x[1] < 0.f ? e[1] : up[1];
-    return x * phi;
+// coefficient k of R, highest power first
+__device__ __forceinline__ constexpr float gelu_coef(int k) {
+    constexpr float c[9] = {-4.435285315e-05f, 4.369443071e-04f, -1.460381877e-03f, -8.251648338e-04f, 2.830188636e-02f, -1.485066472e-01f,
+                            -9.184098145e-01f, -1.627909326e+00f, -9.999999783e-01f};
+    return c[k];
 }
-// y * k + x as packed FMAs (y: a 4-product linear's raw output, k = 1 / lin_s: a power of two, so this is exactly x + value)
-__device__ __forceinline__ f32x16 fma16(const f32x16& y, float k, const f32x16& x) { return __builtin_elementwise_fma(y, f32x16(k), x); }
-
-// The same for a tile that holds S x its value (k = 1 / S, a power of two): returns S x GELU(value).  k only rescales the constant
-// of the first multiplication, so every rounding is the one gelu_f2 makes on the unscaled value.
-__device__ __forceinline__ f32x2 gelu_f2_scaled(f32x2 x, float k) {
+// head and tail of the evaluation: t of a pair that holds 1 / k x its values (k = 1, or a power of two: it only rescales the constant of
+// the first multiplication, so every rounding is the one made on the unscaled value), exp2 of R, and x * Phi(x) from it
+__device__ __forceinline__ f32x2 gelu_arg(f32x2 x, float k) {
     const f32x2 a = x * (0.70710678118654752440f * k);
     f32x2 t;
     t[0] = fminf(fabsf(a[0]), 4.3f);
     t[1] = fminf(fabsf(a[1]), 4.3f);
-    f32x2 r = pk_fma(f32x2(-4.435285315e-05f), t, f32x2(4.369443071e-04f));
-    r = pk_fma(r, t, f32x2(-1.460381877e-03f));
-    r = pk_fma(r, t, f32x2(-8.251648338e-04f));
-    r = pk_fma(r, t, f32x2(2.830188636e-02f));
-    r = pk_fma(r, t, f32x2(-1.485066472e-01f));
-    r = pk_fma(r, t, f32x2(-9.184098145e-01f));
-    r = pk_fma(r, t, f32x2(-1.627909326e+00f));
-    r = pk_fma(r, t, f32x2(-9.999999783e-01f));
+    return t;
+}
+__device__ __forceinline__ f32x2 pk_exp2(f32x2 r) {
     f32x2 e;
     e[0] = __builtin_amdgcn_exp2f(r[0]);
     e[1] = __builtin_amdgcn_exp2f(r[1]);
+    return e;
+}
+__device__ __forceinline__ f32x2 gelu_mul_phi(f32x2 x, f32x2 e) {
     const f32x2 up = 1.0f - e;
     f32x2 phi;
     phi[0] = x[0] < 0.f ? e[0] : up[0];
     phi[1] = x[1] < 0.f ? e[1] : up[1];
     return x * phi;
 }
+// One pair at a time, for a pair that holds S x its values (k = 1 / S, a power of two): returns S x GELU(value)
+__device__ __forceinline__ f32x2 gelu_f2_scaled(f32x2 x, float k) {
+    const f32x2 t = gelu_arg(x, k);
+    f32x2 r = pk_fma(f32x2(gelu_coef(0)), t, f32x2(gelu_coef(1)));
+#pragma unroll
+    for (int i = 2; i < 9; ++i) r = pk_fma(r, t, f32x2(gelu_coef(i)));
+    return gelu_mul_phi(x, pk_exp2(r));
+}
+__device__ __forceinline__ f32x2 gelu_f2(f32x2 x) { return gelu_f2_scaled(x, 1.0f); }
+// y * k + x as packed FMAs (y: a 4-product linear's raw output, k = 1 / lin_s: a power of two, so this is exactly x + value)
+__device__ __forceinline__ f32x16 fma16(const f32x16& y, float k, const f32x16& x) { return __builtin_elementwise_fma(y, f32x16(k), x); }
+
 __device__ __forceinline__ void gelu_tile_scaled(f32x16& v, float k) {
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
@@ -248,6 +260,64 @@ __device__ __forceinline__ void gelu_tile(f32x16& v) {
         p = gelu_f2(p);
         v[r] = p[0]; v[r + 1] = p[1];
     }
+}
+// The same over the first NP register pairs of a tile (true-scale values), the pairs advanced together level by level: the same
+// operations per element, so the same bits; only the instruction order differs.  One pair after the other is a chain of 12 dependent
+// packed operations per pair: right where a second wave fills the slots, wrong for a wave that is alone with its dependency chains
+// (k_gat8's helper waves).
+template <int NP>
+__device__ __forceinline__ void gelu_pairs(f32x16& v) {
+    f32x2 x[NP], t[NP], r[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        x[p][0] = v[2 * p]; x[p][1] = v[2 * p + 1];
+        t[p] = gelu_arg(x[p], 1.0f);
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) r[p] = pk_fma(f32x2(gelu_coef(0)), t[p], f32x2(gelu_coef(1)));
+#pragma unroll
+    for (int k = 2; k < 9; ++k) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) r[p] = pk_fma(r[p], t[p], f32x2(gelu_coef(k)));
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) r[p] = pk_exp2(r[p]);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const f32x2 y = gelu_mul_phi(x[p], r[p]);
+        v[2 * p] = y[0]; v[2 * p + 1] = y[1];
+    }
+}
+
+// Row reductions over a token's channels (token on the lane, its two lane halves combined) and the LayerNorm statistics made from
+// them: 128 channels as four blocks, 64 (the MDR joint tokens) as two.
+__device__ __forceinline__ float row_sum(const f32x16& a, const f32x16& b) {
+    float s = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s += a[r] + b[r];
+    return s + xhalf(s);
+}
+__device__ __forceinline__ float row_sum(const f32x16 (&x)[4]) {
+    float s = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s += (x[0][r] + x[1][r]) + (x[2][r] + x[3][r]);
+    return s + xhalf(s);
+}
+// nn.LayerNorm(128), two-pass: x <- its deviations from the token's mean; returns 1 / sqrt(variance + 1e-5)
+__device__ __forceinline__ float ln_center128(f32x16 (&x)[4]) {
+    const float mean = row_sum(x) * (1.0f / 128.0f);
+    f32x16 sq[4];
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) { x[kb] = x[kb] - mean; sq[kb] = x[kb] * x[kb]; }
+    return 1.0f / sqrtf(row_sum(sq) * (1.0f / 128.0f) + 1e-5f);
+}
+// nn.LayerNorm(64): d0, d1 <- their deviations from the token's mean; returns 1 / sqrt(variance + 1e-5)
+__device__ __forceinline__ float ln_center64(f32x16& d0, f32x16& d1) {
+    const float mean = row_sum(d0, d1) * (1.0f / 64.0f);
+    d0 = d0 - mean;
+    d1 = d1 - mean;
+    return 1.0f / sqrtf(row_sum(d0 * d0, d1 * d1) * (1.0f / 64.0f) + 1e-5f);
 }
 
 // Per-channel vector in T-layout through the SCALAR cache: the value depends only on (register, lane half), so the 8
@@ -290,17 +360,23 @@ __device__ __forceinline__ f32x16 chanvec_select(const SVec& s, int h) {
     return v;
 }
 
-// per-channel vector from the workgroup's LDS table (k_mdr_layer): 4 ds_read_b128 with two distinct addresses each, against 32
-// scalar loads + 16 v_mov + 16 v_cndmask for the scalar-cache form -- 30 such vectors per tile were 9 % of the kernel's VALU work
-__device__ __forceinline__ f32x16 chanvec_lds(const float* V, int off, int h) {
-    f32x16 v;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(V + off + 8 * g + 4 * h);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[4 * g + j] = t[j];
-    }
-    return v;
+// LDS-DMA of BYTES (4 or 16) per lane, each lane from its own address: global -> LDS without registers; `lds_dst` is the wave's window
+// (M0; the low 32 bits of a generic LDS address are the LDS byte offset).  Issued through inline asm ON PURPOSE: hipcc counts the
+// builtin form in its vmcnt bookkeeping and, because the copy writes LDS, drains it (s_waitcnt vmcnt(0)) before the next LDS access or
+// the next copy -- measured in k_gat_tiled: 0.48 of the kernel's 1.2 ms at B=1024 was that wait.  The asm form is invisible to that
+// bookkeeping: whoever reads the bytes waits for them explicitly (k_gat_tiled: begin_group); the L2 warm-ups of k_gat and k_gat8 land
+// in a window nobody reads.
+template <int BYTES>
+__device__ __forceinline__ void glds(const float* gsrc, const float* lds_dst) {
+    static_assert(BYTES == 4 || BYTES == 16, "one dword or four per lane");
+    unsigned keep;
+    const unsigned dst = (unsigned)(unsigned long long)lds_dst;
+    if constexpr (BYTES == 16)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
+    else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
 }
 
 // XCD-aware bijective remap of a 1-D grid: blocks that share an XCD (equal blockIdx % 8) get CONTIGUOUS logical ids,

@@ -16,6 +16,11 @@ struct MdrLayerP {                      // packed weights of one LBF layer (devi
     const float *wq, *wk, *wv, *proj, *fc1, *fc2, *sa[4];
 };
 
+// A GATBlock's small vectors (LayerNorm weights, biases) as one table of V_TOTAL floats, FusedState::g_vecs + block * V_TOTAL: the
+// offsets the encoder kernels read at and fused_create_gat packs at
+enum { V_N1W = 0, V_N1B = 128, V_QKVB = 256, V_PROJB = 640, V_GCNB = 768, V_LIN0B = 896, V_BACKB = 1024, V_N2W = 1152,
+       V_N2B = 1280, V_FC1B = 1408, V_FC2B = 1920, V_TOTAL = 2048 };
+
 struct GatBlockPk {                     // packed tiles of one GATBlock
     const float *qkv, *proj, *w0, *w1, *lin0, *lin1, *back, *fc1, *fc2;
     const float *mc, *mdT, *aoffT, *f1b; // M (channel on lane), diag(A).M (TOKEN on lane), offdiag(A)^T B-operand tile, hop-2 bias term
@@ -57,8 +62,8 @@ struct FusedState {
     DevBuf<float> gxbuf;                // X3 tiles of the GAT block weights, tile-for-tile image of gbuf from gblk[0].qkv on
     DevBuf<float> gxbuf_h3;             // the same grids as three fp16 planes of 2^gat_tiled_wshift * w (k_gat_tiled's four-product form)
     int gat_tiled_wshift = 0;
-    DevBuf<float> g8stream;             // the same tiles as four per-wave streams in consumption order (gat_roles.hip)
-    DevBuf<float> g8stream_b;           // ... and its byte-lo image (H3B tiles, 5 KiB: gat_roles.hip), what k_gat8<true, LR, false, true> streams
+    DevBuf<float> g8stream;             // the same tiles as four per-wave streams in consumption order (gat8_forms.h, gat8_stream.hip)
+    DevBuf<float> g8stream_b;           // ... and its byte-lo image (H3B tiles, 5 KiB: gat8_forms.h), what k_gat8<true, LR, false, true> streams
     int gat8_wshift = 0;                // its weight stream holds three fp16 planes of 2^gat8_wshift * w
     DevBuf<float> wxbuf;                // X3 tiles of the MDR layer + head weights, tile-for-tile image of wbuf from lay[0].wq on
     DevBuf<float> jf128_h3;             // get_joint_feature columns 5..132 as H3 tiles [2][4] of 2^jf128_wshift * w (k_gat8's fused tail)
@@ -138,9 +143,10 @@ int launch_upsample(const FusedState* f, const gator_ctx* c, const FusedWs& ws, 
 int gat_prepare_device();
 int gat_ensure_blk_tap(gator_ctx* c, FusedState* f, int B);
 int launch_gat(gator_ctx* c, FusedState* f, const GatForm& form, const float* pose2d, int B, float* x_out, float* feat, void* stream, int B_total, int tap_row0);      // B samples: rows tap_row0 .. of a batch of B_total
+// gat8_stream.hip
+int gat8_build_stream(FusedState* f, void* stream);
 // gat_roles.hip
 int gat8_prepare_device();
-int gat8_build_stream(FusedState* f, void* stream);
 int launch_gat8(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pose2d, int B, float* pose3d, void* stream);      // k_gat8<p.gat8> on samples p.n_tiled .. B of the whole batch's pose2d / pose3d
 // gat_tiled.hip
 int gat_tiled_prepare_device();

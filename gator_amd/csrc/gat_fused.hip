@@ -17,13 +17,11 @@
 namespace gator {
 namespace {
 
-constexpr float kLog2eG = 1.4426950408889634f;
-
 struct GatBlockP {   // per-GATBlock packed tiles + reference-layout vectors
     const float *qkv, *proj, *w0, *w1, *lin0, *lin1, *back, *fc1, *fc2;      // packed [NB][KB] tile grids (fp32 tiles, or X3 tiles)
     const float* back32;                                                       // linearback always also as fp32 tiles (its 16-wide k tail)
     const float *mc, *mdT, *aoffT, *f1b;                                       // packed tables: M (channel on lane), diag(A).M (token on lane), offdiag(A)^T, hop-2 bias
-    const float* vecs;                                                         // V_TOTAL floats, order above
+    const float* vecs;                                                         // V_TOTAL floats (fused_state.h: V_*)
 };
 
 struct GatArgs {
@@ -42,28 +40,8 @@ struct GatArgs {
 #endif
 };
 
-// Per-block small vectors (LayerNorm weights, biases) are staged in LDS one block ahead: 2048 floats in this order.
+// Per-block small vectors (LayerNorm weights, biases; fused_state.h: V_*) are staged in LDS one block ahead.
 // A global load issued at its point of use would queue behind the weight prefetch in flight (vmcnt is in-order).
-enum { V_N1W = 0, V_N1B = 128, V_QKVB = 256, V_PROJB = 640, V_GCNB = 768, V_LIN0B = 896, V_BACKB = 1024, V_N2W = 1152,
-       V_N2B = 1280, V_FC1B = 1408, V_FC2B = 1920, V_TOTAL = 2048 };
-// per-channel vector in T-layout from LDS: v[r] = V[off + kap(r) + 4h]  (two distinct addresses per ds_read_b128: broadcast)
-__device__ __forceinline__ f32x16 load_chanvec_L(const float* V, int off, int h) {
-    f32x16 v;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(V + off + 8 * g + 4 * h);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[4 * g + j] = t[j];
-    }
-    return v;
-}
-
-__device__ __forceinline__ float row_sum128(const f32x16 (&x)[4]) {
-    float s = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += (x[0][r] + x[1][r]) + (x[2][r] + x[3][r]);
-    return s + xhalf(s);
-}
 
 // nn.LayerNorm(128); reads the residual stream X (4 tiles in LDS), result in registers
 template <bool GELU>
@@ -72,16 +50,16 @@ __device__ __forceinline__ void layernorm128(const float* X, const float* w, con
     f32x16 x[4];
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) x[kb] = load_block(X + kb * kTile, lane);
-    const float mean = row_sum128(x) * (1.0f / 128.0f);
+    const float mean = row_sum(x) * (1.0f / 128.0f);
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) x[kb] = x[kb] - mean;
     f32x16 sq[4];
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) sq[kb] = x[kb] * x[kb];
-    const float rstd = 1.0f / sqrtf(row_sum128(sq) * (1.0f / 128.0f) + 1e-5f);
+    const float rstd = 1.0f / sqrtf(row_sum(sq) * (1.0f / 128.0f) + 1e-5f);
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
-        y[kb] = x[kb] * rstd * load_chanvec_L(w, 32 * kb, h) + load_chanvec_L(b, 32 * kb, h);
+        y[kb] = x[kb] * rstd * chanvec_lds(w, 32 * kb, h) + chanvec_lds(b, 32 * kb, h);
         if (GELU) {
             gelu_tile(y[kb]);
         }
@@ -184,15 +162,7 @@ __device__ __forceinline__ f32x16 lin4l(Grp<true>& g, const float* T, int lane, 
 }
 
 // TAIL = false: the kernel ends with `feat`; the lifter and the MDR joint tokens run as batched launches (gat_tail.hip)
-constexpr int kGatLdsFloatsX3 = 4 * kTile + 16 * kTileX3 + 2048;
-
-// LDS-DMA through inline asm (hipcc drains the builtin form with vmcnt(0) before the next LDS access, see gat_tiled.hip)
-__device__ __forceinline__ void glds16(const float* gsrc, const float* lds_dst) {
-    unsigned keep;
-    const unsigned dst = (unsigned)(unsigned long long)lds_dst;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-}
+constexpr int kGatLdsFloatsX3 = 4 * kTile + 16 * kTileX3 + V_TOTAL;
 
 template <bool X3K, bool TAIL>
 __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
@@ -283,7 +253,7 @@ __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
         const int left = a.pf_block - rank * a.pf_share;
         float* dummy = lds + kGatLdsFloatsX3;
         for (int off = 0; off < a.pf_share; off += 4096)
-            if (off + t * 16 < left) glds16(reinterpret_cast<const float*>(src + off + t * 16), dummy + wave * 256);   // (M0 = the wave's 1 KB window)
+            if (off + t * 16 < left) glds<16>(reinterpret_cast<const float*>(src + off + t * 16), dummy + wave * 256);   // (M0 = the wave's 1 KB window)
     };
     l2_warm(a.blk[0].qkv);
 
@@ -298,7 +268,7 @@ __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
             vn0 = reinterpret_cast<const f32x4*>(wn.vecs)[t];
             vn1 = reinterpret_cast<const f32x4*>(wn.vecs)[256 + t];
             GATOR_PIN();
-            const f32x16 bq = load_chanvec_L(V, V_QKVB + 32 * wave, h), bk = load_chanvec_L(V, V_QKVB + 128 + 32 * wave, h);
+            const f32x16 bq = chanvec_lds(V, V_QKVB + 32 * wave, h), bk = chanvec_lds(V, V_QKVB + 128 + 32 * wave, h);
             const float vb = V[V_QKVB + 256 + 32 * wave + (lane & 31)];
             typename Op<X3K>::T y[4];
             {
@@ -331,8 +301,8 @@ __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const bool ok = kap(r) + 4 * h < J;
-                    sa[r] = ok ? (sa[r] * 0.25f + ba[r]) * kLog2eG : -1e30f;             // q k^T * head_dim**-0.5 + bias
-                    sb[r] = ok ? (sb[r] * 0.25f + bb[r]) * kLog2eG : -1e30f;
+                    sa[r] = ok ? (sa[r] * 0.25f + ba[r]) * kLog2e : -1e30f;             // q k^T * head_dim**-0.5 + bias
+                    sb[r] = ok ? (sb[r] * 0.25f + bb[r]) * kLog2e : -1e30f;
                     ma = fmaxf(ma, sa[r]);
                     mb = fmaxf(mb, sb[r]);
                 }
@@ -363,7 +333,7 @@ __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
             // ---- MGCN (modules.py:243-255): h_k = y @ W[k]; out = diag(A)(M.h0) + offdiag(A)(M.h1) + bias ----
             const f32x16 mdt = load_block(w.mdT + (size_t)wave * kTile, lane), mct = load_block(w.mc + (size_t)wave * kTile, lane);
             const f32x16 aoff = load_block(w.aoffT, lane);
-            const f32x16 bg = load_chanvec_L(V, V_GCNB + 32 * wave, h), bp = load_chanvec_L(V, V_PROJB + 32 * wave, h);
+            const f32x16 bg = chanvec_lds(V, V_GCNB + 32 * wave, h), bp = chanvec_lds(V, V_PROJB + 32 * wave, h);
             GATOR_PIN();
             f32x16 h0 = lin4r<false>(G, y, zero16(), w.w1, wave * 4, lane);        // token on the lane: its term is token-wise
             GATOR_PIN();
@@ -389,7 +359,7 @@ __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
         const WTile wb4 = load_wtile(w.back32, wave * 5 + 4, lane);
         const f32x16 m1 = load_block(a.m1T, lane), m2 = load_block(a.m2T, lane), f1bias = load_block(w.f1b, lane);
         const float b0 = V[V_LIN0B + 32 * wave + (lane & 31)];
-        const f32x16 bback = load_chanvec_L(V, V_BACKB + 32 * wave, h);
+        const f32x16 bback = chanvec_lds(V, V_BACKB + 32 * wave, h);
         GATOR_PIN();
         __syncthreads();
         GAT_STAMP(3)
@@ -433,24 +403,24 @@ __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
 #pragma unroll
                 for (int kb = 0; kb < 4; ++kb) y2[kb] = mkop<X3K>(yf[kb]);
             }
-            f32x16 hd = lin4r<false>(G, y2, load_chanvec_L(V, V_FC1B + 32 * (4 * wave + 0), h), w.fc1, (4 * wave + 1) * 4, lane);
+            f32x16 hd = lin4r<false>(G, y2, chanvec_lds(V, V_FC1B + 32 * (4 * wave + 0), h), w.fc1, (4 * wave + 1) * 4, lane);
             GATOR_PIN();
             gelu_tile(hd);
             stop<X3K>(HB + (4 * wave + 0) * TA, lane, hd);
-            hd = lin4r<false>(G, y2, load_chanvec_L(V, V_FC1B + 32 * (4 * wave + 1), h), w.fc1, (4 * wave + 2) * 4, lane);
+            hd = lin4r<false>(G, y2, chanvec_lds(V, V_FC1B + 32 * (4 * wave + 1), h), w.fc1, (4 * wave + 2) * 4, lane);
             GATOR_PIN();
             gelu_tile(hd);
             stop<X3K>(HB + (4 * wave + 1) * TA, lane, hd);
-            hd = lin4r<false>(G, y2, load_chanvec_L(V, V_FC1B + 32 * (4 * wave + 2), h), w.fc1, (4 * wave + 3) * 4, lane);
+            hd = lin4r<false>(G, y2, chanvec_lds(V, V_FC1B + 32 * (4 * wave + 2), h), w.fc1, (4 * wave + 3) * 4, lane);
             GATOR_PIN();
             gelu_tile(hd);
             stop<X3K>(HB + (4 * wave + 2) * TA, lane, hd);
-            hd = lin4r<false>(G, y2, load_chanvec_L(V, V_FC1B + 32 * (4 * wave + 3), h), w.fc2, wave * 16 + 0, lane);
+            hd = lin4r<false>(G, y2, chanvec_lds(V, V_FC1B + 32 * (4 * wave + 3), h), w.fc2, wave * 16 + 0, lane);
             GATOR_PIN();
             gelu_tile(hd);
             stop<X3K>(HB + (4 * wave + 3) * TA, lane, hd);
         }
-        const f32x16 bfc2 = load_chanvec_L(V, V_FC2B + 32 * wave, h);
+        const f32x16 bfc2 = chanvec_lds(V, V_FC2B + 32 * wave, h);
         GAT_STAMP(6)
         __syncthreads();
         GAT_STAMP(7)
@@ -468,14 +438,7 @@ __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
             xw += (c0 + c1) + (c2 + c3);
             store_block(X + wave * kTile, lane, xw);     // every wave finished reading X (LN2) before the HB barrier
             if (a.blk_tap && (lane & 31) < J) {          // debug tap (off in timed runs): this wave's channel block of the block output
-                float* dst = a.blk_tap + (((size_t)bi * a.tapB + b) * J + (lane & 31)) * kC + 32 * wave + 4 * h;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v4;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v4[j] = xw[4 * g + j];
-                    *reinterpret_cast<f32x4*>(dst + 8 * g) = v4;
-                }
+                store_row_block(a.blk_tap + (((size_t)bi * a.tapB + b) * J + (lane & 31)) * kC + 32 * wave, h, xw);
             }
         }
         __syncthreads();
@@ -487,23 +450,15 @@ __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
         f32x16 x[4];
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) x[kb] = load_block(X + kb * kTile, lane);
-        const float mean = row_sum128(x) * (1.0f / 128.0f);
+        const float mean = row_sum(x) * (1.0f / 128.0f);
         f32x16 sq[4];
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) { x[kb] = x[kb] - mean; sq[kb] = x[kb] * x[kb]; }
-        const float rstd = 1.0f / sqrtf(row_sum128(sq) * (1.0f / 128.0f) + 1e-5f);
+        const float rstd = 1.0f / sqrtf(row_sum(sq) * (1.0f / 128.0f) + 1e-5f);
         f32x16 mine = (xw - mean) * rstd * load_chanvec_S(a.norm_w, 32 * wave, h) + load_chanvec_S(a.norm_b, 32 * wave, h);
         gelu_tile(mine);      // each wave finishes only its own channel block
         store_block(R + wave * kTile, lane, mine);
-        if (tok < J) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v4[j] = mine[4 * g + j];
-                *reinterpret_cast<f32x4*>(a.feat + ((size_t)b * J + tok) * kC + 32 * wave + 8 * g + 4 * h) = v4;
-            }
-        }
+        if (tok < J) store_row_block(a.feat + ((size_t)b * J + tok) * kC + 32 * wave, h, mine);
     }
     if constexpr (!TAIL) return;
     GAT_STAMP(18)
@@ -565,7 +520,7 @@ __global__ __launch_bounds__(256, 1) void k_gat(const GatArgs a) {
 
 }  // namespace
 
-constexpr size_t kGatLds = (20 * kTile + 2048) * sizeof(float);                   // 88 KB
+constexpr size_t kGatLds = (20 * kTile + V_TOTAL) * sizeof(float);                   // 88 KB
 constexpr size_t kGatLdsX3 = (kGatLdsFloatsX3 + 1024) * sizeof(float);            // 120 KB + the 4 KB landing window of the L2 warm-up
 
 // The four forms of k_gat with their dynamic LDS, named once: the opt-in and the launch both read this table
@@ -614,7 +569,7 @@ int launch_gat(gator_ctx* c, FusedState* f, const GatForm& form, const float* po
         q.back = sel(p.back); q.fc1 = sel(p.fc1); q.fc2 = sel(p.fc2);
         q.back32 = p.back;
         q.mc = p.mc; q.mdT = p.mdT; q.aoffT = p.aoffT; q.f1b = p.f1b;
-        q.vecs = f->g_vecs + (size_t)i * 2048;
+        q.vecs = f->g_vecs + (size_t)i * V_TOTAL;
     }
     a.x_out = x_out; a.feat = feat;
     a.pf_share = a.pf_n = a.pf_block = 0;

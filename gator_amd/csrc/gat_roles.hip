@@ -38,51 +38,19 @@
 #include "fused_common.h"
 #include "fused_state.h"
 #include "x3_common.h"
+#include "gat8_forms.h"
+#include "gat8_rows.h"
+#include "gat8_tail.h"
 
 #include <algorithm>
 #include <cmath>
-#include <type_traits>
 #include <cstdlib>
 #include <vector>
 
 namespace gator {
 namespace {
 
-constexpr float kLog2e8 = 1.4426950408889634f;
-constexpr int kNT = 5;                                  // weight tiles in flight per product wave.  6 (one dummy tile per block, +28 VGPRs) was measured:
-                                                        // no change (188 - 192 us either way on one box), so the stream is not short of bytes in flight
-constexpr int kUseTiles = 65;                           // q k v h0 h1 proj lin0 (4 each) + lin1 (1) + back (4) + fc1 (16) + fc2 (16)
-constexpr int kPadTiles = (kNT - kUseTiles % kNT) % kNT;       // dummy tiles behind a block so that every block starts at slot 0
-constexpr int kBlkTiles = kUseTiles + kPadTiles;
-// tile offsets of the units inside a block (their slot = offset mod kNT, compile-time)
-enum { OFF_Q = 0, OFF_K = 4, OFF_V = 8, OFF_H0 = 12, OFF_H1 = 16, OFF_PROJ = 20, OFF_LIN0 = 24, OFF_LIN1 = 28, OFF_BACK = 29, OFF_FC1 = 33, OFF_FC2 = 49 };
-constexpr int kWaveTiles = kBlkTiles * kDepth;          // per product wave
-constexpr int kStreamFloats = (4 * kWaveTiles + kNT) * kTileX3;
-constexpr int kTileH3B = 2 * 512 + 256;                // floats of a byte-lo tile: hi and mid planes as in H3 (1 KiB per k-step each), lo as one byte per weight
-constexpr int kStreamFloatsB = (4 * kWaveTiles + kNT) * kTileH3B;
-
-// offsets into a block's vector table (fused_api.hip packs them in this order, 2048 floats per block)
-enum { V_N1W = 0, V_N1B = 128, V_QKVB = 256, V_PROJB = 640, V_GCNB = 768, V_LIN0B = 896, V_BACKB = 1024, V_N2W = 1152,
-       V_N2B = 1280, V_FC1B = 1408, V_FC2B = 1920 };
-
 struct Gat8Blk { const float *back32, *mc, *mdT, *aoffT, *f1b, *vecs; };
-// Epilogue of k_gat8<..., TAIL = true> (round 6): what gat_tail.hip's two launches do for the batch, done by the workgroup that owns
-// the sample and has its feat on chip.
-struct Gat8Tail {
-    const float *lifter_w, *lifter_b;       // lifter.weight [3J][128J] as the reference stores it, bias [3J]  (GAT.py:151-152)
-    float* x_out;                           // [B][3J] = pose3d [B][J][3] (mm)
-    float* jkv;                             // nullptr: lifter only (stand-alone GAT entry point)
-    unsigned* mdr_ctr;                      // non-null: zero k_mdr_persist's tickets / completion counts of the forward (as k_gat_joint does)
-    int ctr_B;                              //           ... of a forward of ctr_B samples (mdr_ctr_words)
-    const float *jf5, *jf_h3, *jf_b, *posj_T;      // get_joint_feature: columns 0..4 as [5][64], columns 5..132 as H3 tiles [2][4], bias; pos_j tiles
-    const float *j_n1w[3], *j_n1b[3], *j_wk_h3[3], *j_wv_h3[3];      // per LBF layer: norm1, wk / wv as H3 tiles [2][2] (the MDR layers' own weight image)
-    float jf_inv, kv_inv;                          // 1 / (16 x 2^weight shift) of the two H3 weight sets (x3_common.h: four-product linears)
-#ifdef GATOR_DIAG
-    unsigned long long* tstamps;                   // [8 waves][8] s_memtime stamps of workgroup B/2's epilogue (GATOR_GAT_STAMPS)
-#endif
-    int warm_n;                                    // L2 warm-up of the epilogue's weights: workgroups per XCD that share it (0: off)
-};
-
 struct Gat8Args {
     int B, J;
     const float* pose2d;
@@ -102,21 +70,6 @@ struct Gat8Args {
     int dbg;                         // GATOR_GAT8_DBG: 1 = helpers only keep the barriers (what do the product waves cost alone?)
 #endif
 };
-
-// LDS map (floats)
-constexpr int kA = 0;                                   // 4 operand tiles
-constexpr int kBq = kA + 4 * kTileX3;                   // 12 operand tiles
-constexpr int kR = kBq + 12 * kTileX3;                  // R0 (4 raw tiles) | R1 (4 raw tiles)
-constexpr int kXo = kR + 8 * kTile;                     // 4 fp32 tiles
-constexpr int kDummy = kXo + 4 * kTile;                 // 4 x 1 KiB landing window of the L2 warm-up (never read)
-constexpr int kStat = kDummy + 1024;                     // [4 helper waves][32 tokens][mean, M2] of the wave's 32 channels (LayerNorm statistics)
-constexpr int kGat8LdsFloats = kStat + 256;             // 149 KiB
-#ifdef GATOR_DIAG
-constexpr int kDiagStamps = 2 * kDepth * 23 * 2 + kDepth * 8;      // u64 cycle stamps, kept in LDS while the kernel runs (a global
-constexpr int kDiagLdsFloats = 2 * kDiagStamps;                    // store waits ~0.5k cycles behind the product waves' stream and
-#else                                                               // would be measured as work of the step it sits in)
-constexpr int kDiagLdsFloats = 0;
-#endif
 
 #ifdef GATOR_DIAG
 // diagnostic library only (python -m gator_amd.build --diag; GATOR_GAT_STAMPS=1): per role, block and step the cycles spent working
@@ -147,7 +100,7 @@ constexpr int kDiagLdsFloats = 0;
 #endif
 
 // A helper wave is alone with its own dependency chains (its SIMD partner issues MFMAs, nobody fills its latency slots), so the
-// reductions are trees of independent partial sums and the GELU walks its polynomial level by level over all eight register pairs.
+// reductions are trees of independent partial sums and the GELU walks its polynomial level by level (fused_common.h: gelu_pairs).
 __device__ __forceinline__ float rsum128(const f32x16 (&x)[4]) {
     float p[4];
 #pragma unroll
@@ -158,133 +111,6 @@ __device__ __forceinline__ float rsum128(const f32x16 (&x)[4]) {
     }
     const float s = (p[0] + p[1]) + (p[2] + p[3]);
     return s + xhalf(s);
-}
-
-// gelu_f2 (fused_common.h) over a whole register tile, the eight pairs advanced together: same operations per element, so the same
-// bits; only the instruction order differs (one pair after the other is a chain of 12 dependent packed operations, 8 times)
-__device__ __forceinline__ void gelu_tile8(f32x16& v) {     // (operates on true-scale values in both forms)
-    f32x2 x[8], t[8], r[8];
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        x[p][0] = v[2 * p]; x[p][1] = v[2 * p + 1];
-        const f32x2 a = x[p] * 0.70710678118654752440f;
-        t[p][0] = fminf(fabsf(a[0]), 4.3f);
-        t[p][1] = fminf(fabsf(a[1]), 4.3f);
-    }
-    const float c[8] = {4.369443071e-04f, -1.460381877e-03f, -8.251648338e-04f, 2.830188636e-02f, -1.485066472e-01f, -9.184098145e-01f,
-                        -1.627909326e+00f, -9.999999783e-01f};
-#pragma unroll
-    for (int p = 0; p < 8; ++p) r[p] = pk_fma(f32x2(-4.435285315e-05f), t[p], f32x2(c[0]));
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-#pragma unroll
-        for (int p = 0; p < 8; ++p) r[p] = pk_fma(r[p], t[p], f32x2(c[k]));
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        r[p][0] = __builtin_amdgcn_exp2f(r[p][0]);
-        r[p][1] = __builtin_amdgcn_exp2f(r[p][1]);
-    }
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        const f32x2 up = 1.0f - r[p];
-        f32x2 phi;
-        phi[0] = x[p][0] < 0.f ? r[p][0] : up[0];
-        phi[1] = x[p][1] < 0.f ? r[p][1] : up[1];
-        const f32x2 y = x[p] * phi;
-        v[2 * p] = y[0]; v[2 * p + 1] = y[1];
-    }
-}
-
-// The MLP's hidden tiles in the four-product form.  fc1 leaves its accumulator in C layout (channel on the lane, token rows in the
-// registers), so the GELU and the split run over the LR registers that hold tokens instead of all 16 -- in T layout 15 of a tile's
-// 32 token lanes are padding at J = 17 and every instruction pays for them.  fc2 wants the hidden activations as an operand with k =
-// channel, i.e. the transpose of what a C-layout lane holds, and the operand goes through LDS anyway: lane (c, h) writes its value of
-// token t as ONE half into chunk (plane, s = c >> 4, lane' = t + 32 ((c >> 2) & 1)), element 4 ((c >> 3) & 1) + (c & 3).  The chunk
-// index is XOR-ed with s + 2 (lane' >> 5) so that the 64 lanes of one such store hit 32 different banks (unswizzled: 8); the fc2
-// units read the tile with the same XOR (x2_load_swz).  Token rows that do not exist are not written: their halves keep whatever
-// finite operand the tile held before, which only ever reaches the same padding token's outputs.
-__device__ __forceinline__ X2 x2_load_swz(const float* __restrict__ tile, int lane) {
-    const f16x8* q = reinterpret_cast<const f16x8*>(tile);
-    X2 o;
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) o.p[pl][s] = q[(pl * 2 + s) * 64 + (lane ^ (s + 2 * (lane >> 5)))];
-    return o;
-}
-struct HidAddr { int base, off[4]; };                  // byte offsets of a C-layout lane into a hidden operand tile
-__device__ __forceinline__ HidAddr hid_addr(int lane) {
-    const int c = lane & 31, hh = lane >> 5, s = c >> 4, kh = (c >> 2) & 1, jj = 4 * ((c >> 3) & 1) + (c & 3), swz = s + 2 * kh;
-    HidAddr a;
-    a.base = s * 1024 + (4 * hh + 32 * kh) * 16 + jj * 2;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) a.off[q] = (q ^ swz) * 16;
-    return a;
-}
-// two planes of 16 x v[r] for the token rows r < LR, scattered into the operand tile
-template <int LR>
-__device__ __forceinline__ void hid_store(float* tile, const HidAddr& ha, const f32x16& v) {
-    char* lb = reinterpret_cast<char*>(tile) + ha.base;
-#pragma unroll
-    for (int r = 0; r < LR; ++r) {
-        const float x = v[r] * 16.0f;
-        const _Float16 hi = (_Float16)x;
-        const _Float16 lo = (_Float16)(x - (float)hi);
-        char* pr = lb + ha.off[r & 3] + (r >> 2) * 128;
-        *reinterpret_cast<_Float16*>(pr) = hi;
-        *reinterpret_cast<_Float16*>(pr + 2048) = lo;
-    }
-}
-// gelu_tile8 over the first NP register pairs only
-template <int NP>
-__device__ __forceinline__ void gelu_pairs(f32x16& v) {
-    f32x2 x[NP], t[NP], r[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        x[p][0] = v[2 * p]; x[p][1] = v[2 * p + 1];
-        const f32x2 a = x[p] * 0.70710678118654752440f;
-        t[p][0] = fminf(fabsf(a[0]), 4.3f);
-        t[p][1] = fminf(fabsf(a[1]), 4.3f);
-    }
-    const float c[8] = {4.369443071e-04f, -1.460381877e-03f, -8.251648338e-04f, 2.830188636e-02f, -1.485066472e-01f, -9.184098145e-01f,
-                        -1.627909326e+00f, -9.999999783e-01f};
-#pragma unroll
-    for (int p = 0; p < NP; ++p) r[p] = pk_fma(f32x2(-4.435285315e-05f), t[p], f32x2(c[0]));
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) r[p] = pk_fma(r[p], t[p], f32x2(c[k]));
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        r[p][0] = __builtin_amdgcn_exp2f(r[p][0]);
-        r[p][1] = __builtin_amdgcn_exp2f(r[p][1]);
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const f32x2 up = 1.0f - r[p];
-        f32x2 phi;
-        phi[0] = x[p][0] < 0.f ? r[p][0] : up[0];
-        phi[1] = x[p][1] < 0.f ? r[p][1] : up[1];
-        const f32x2 y = x[p] * phi;
-        v[2 * p] = y[0]; v[2 * p + 1] = y[1];
-    }
-}
-// the first ceil(LR / 4) register groups of a block
-template <int LR>
-__device__ __forceinline__ f32x16 load_block_rows(const float* __restrict__ p, int lane) {
-    const f32x4* q = reinterpret_cast<const f32x4*>(p) + lane;
-    f32x16 v = zero16();
-#pragma unroll
-    for (int g = 0; g < (LR + 3) / 4; ++g) {
-        const f32x4 t = q[g * 64];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[4 * g + j] = t[j];
-    }
-    return v;
 }
 
 // nn.LayerNorm(128) of the residual stream X (4 fp32 tiles in LDS): statistics over all four tiles, result for this wave's own
@@ -334,494 +160,19 @@ __device__ __forceinline__ f32x16 ln_stats(const float* ST, const f32x16& xw, co
     return (xw - mean) * rstd * wv + bv;
 }
 
-// ---- token rows that do not exist.  A tile whose REGISTERS run over tokens (C layout: v[r] <-> token kap(r) + 4h; S^T and P^T with
-// the key on the row) has live data only in registers r < LR: tokens 0 .. J-1 with J = 17 / 19 sit in r <= 8 / 10.  The rows behind
-// them hold products against zero operand rows or masked scores (probability exactly 0): every instruction spent on them is wasted,
-// and the helper waves are the long side of most steps.  LR (even: 10 for J <= 18, 12 for J <= 20; 16 = every row, the six-product form) is a template
-// parameter of the kernel; skipping dead rows changes no bit of a live value (sums lose terms that are exactly +0).
-template <int LR>
-__device__ __forceinline__ X2 x2_split_rows(const f32x16& v) {     // x2_split with zero halves for the dead rows
-    X2 o;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (8 * s + j < LR) {
-                const float x = v[8 * s + j];
-                const _Float16 hh = (_Float16)x;
-                o.p[0][s][j] = hh;
-                o.p[1][s][j] = (_Float16)(x - (float)hh);
-            } else {
-                o.p[0][s][j] = (_Float16)0.f;
-                o.p[1][s][j] = (_Float16)0.f;
-            }
-        }
-    return o;
-}
-// (a + b) + (c + d) over the live registers of group q, the association of the full tree (a dead term is an exact +0)
-template <int LR, class F>
-__device__ __forceinline__ float tree4(int q, F f) {
-    const int n = LR - 4 * q;          // live registers in this group
-    if (n <= 0) return 0.f;
-    if (n == 1) return f(4 * q);
-    if (n == 2) return f(4 * q) + f(4 * q + 1);
-    if (n == 3) return (f(4 * q) + f(4 * q + 1)) + f(4 * q + 2);
-    return (f(4 * q) + f(4 * q + 1)) + (f(4 * q + 2) + f(4 * q + 3));
-}
-// dot16 (fused_common.h) over the live k rows only: the same two chains (even / odd registers)
-template <int LR>
-__device__ __forceinline__ f32x16 dot16_rows(const f32x16& A, const f32x16& B, f32x16 init) {
-    f32x16 e = init, o = zero16();
-#pragma unroll
-    for (int r = 0; r < LR; r += 2) {
-        e = GATOR_MFMA(A[r], B[r], e);
-        o = GATOR_MFMA(A[r + 1], B[r + 1], o);
-    }
-    return e + o;
-}
-
-// ---- product wave: one unit = the K = 128 contraction of one 32-channel output block (4 weight tiles) --------------------------
-// CL = false: weights as A operand -> T-layout accumulator (token on the lane); CL = true: activations as A -> C-layout.
-// Slot indices are compile-time (S0 = tile offset of the unit inside its block, mod kNT); every slot is refilled with the tile
-// kNT positions further down the wave's stream right after the MFMAs that read it are queued.
-// LDS-DMA through inline asm (hipcc drains the builtin form with vmcnt(0) before the next LDS access, see gat_tiled.hip): used
-// only to pull lines into this XCD's L2 - the bytes land in a window nobody reads, no registers are held
-__device__ __forceinline__ void glds4(const float* gsrc, const float* lds_dst) {      // one dword per lane, per-lane source address
-    unsigned keep;
-    const unsigned dst = (unsigned)(unsigned long long)lds_dst;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-}
-
-// One tile product with the refill of its weight slot woven in: a plane's load (tile kNT positions further down the stream) is
-// issued right behind the LAST MFMA that reads that plane, so it issues in the shadow of the next MFMA.  Issued as a burst behind
-// the twelve MFMAs (k_gat's form) the six 1 KiB loads hold the in-order wave at the memory pipeline's issue rate while the matrix
-// pipe idles: measured here as 3.2k cycles per 4-tile unit against 1.5k of MFMA time.  sched_barrier pins the order.
-template <bool CL>
-__device__ __forceinline__ void tile_mma_refill(X3& w, const X3& b, f32x16& acc, f32x16& /* six-product form: one accumulator */, const float* __restrict__ wp, int lane) {
-    const bf16x8* q = reinterpret_cast<const bf16x8*>(wp) + lane;
-#define GAT8_MM(wpl, bpl, s) acc = CL ? GATOR_MFMA_BF16(b.p[bpl][s], w.p[wpl][s], acc) : GATOR_MFMA_BF16(w.p[wpl][s], b.p[bpl][s], acc)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        GAT8_MM(2, 0, s);                                  // lo*hi
-        __builtin_amdgcn_sched_barrier(0);
-        w.p[2][s] = q[(2 * 2 + s) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-        GAT8_MM(0, 2, s);                                  // hi*lo
-        GAT8_MM(1, 1, s);                                  // mid*mid
-        GAT8_MM(1, 0, s);                                  // mid*hi
-        __builtin_amdgcn_sched_barrier(0);
-        w.p[1][s] = q[(1 * 2 + s) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-        GAT8_MM(0, 1, s);                                  // hi*mid
-        GAT8_MM(0, 0, s);                                  // hi*hi
-        __builtin_amdgcn_sched_barrier(0);
-        w.p[0][s] = q[(0 * 2 + s) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#undef GAT8_MM
-}
-// The four-product form (x3_common.h: weights exact on three fp16 planes, activations on two): w_hi a_lo | w_lo a_hi, w_mid a_hi,
-// w_hi a_hi -- 8 MFMAs per tile; the refill of a plane still follows the last MFMA that reads it.  The three cross products go to
-// their OWN accumulator `acs` (2^-11 of the result: its roundings do not matter), so the main one is rounded twice per tile instead of
-// eight times -- every MFMA rounds its accumulator at the accumulator's magnitude, and in-product accumulation is where the path's
-// fp32 noise comes from (x3_common.h, x2_mma).  unit4 adds the two once, in the product wave's idle vector slots.
-template <bool CL>
-__device__ __forceinline__ void tile_mma_refill(H3& w, const X2& b, f32x16& acc, f32x16& acs, const float* __restrict__ wp, int lane) {
-    const f16x8* q = reinterpret_cast<const f16x8*>(wp) + lane;
-#define GAT8_MM(wpl, bpl, s, AC) AC = CL ? GATOR_MFMA_F16(b.p[bpl][s], w.p[wpl][s], AC) : GATOR_MFMA_F16(w.p[wpl][s], b.p[bpl][s], AC)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        GAT8_MM(0, 1, s, acs);                             // w hi  * a lo
-        GAT8_MM(2, 0, s, acs);                             // w lo  * a hi
-        __builtin_amdgcn_sched_barrier(0);
-        w.p[2][s] = q[(2 * 2 + s) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-        GAT8_MM(1, 0, s, acs);                             // w mid * a hi
-        __builtin_amdgcn_sched_barrier(0);
-        w.p[1][s] = q[(1 * 2 + s) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-        GAT8_MM(0, 0, s, acc);                             // w hi  * a hi
-        __builtin_amdgcn_sched_barrier(0);
-        w.p[0][s] = q[(0 * 2 + s) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#undef GAT8_MM
-}
-// The one-plane form (BASELINE config 3, the 16-bit operand mode: DESIGN.md 4e): activations on their hi plane only, weights on their hi and mid
-// planes -- w_mid a_hi | w_hi a_hi, four MFMAs per tile, and the lo plane of the weight stream (a third of its bytes) is never loaded.
-// Same tile geometry, same stream; a type of its own so that the overloads below pick the form.
-struct H3P2 { f16x8 p[2][2]; };      // [plane hi/mid][k-step]: 16 VGPRs
-template <bool CL>
-__device__ __forceinline__ void tile_mma_refill(H3P2& w, const X2& b, f32x16& acc, f32x16& acs, const float* __restrict__ wp, int lane) {
-    const f16x8* q = reinterpret_cast<const f16x8*>(wp) + lane;
-#define GAT8_MM(wpl, s, AC) AC = CL ? GATOR_MFMA_F16(b.p[0][s], w.p[wpl][s], AC) : GATOR_MFMA_F16(w.p[wpl][s], b.p[0][s], AC)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        GAT8_MM(1, s, acs);                                // w mid * a hi
-        __builtin_amdgcn_sched_barrier(0);
-        w.p[1][s] = q[(1 * 2 + s) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-        GAT8_MM(0, s, acc);                                // w hi  * a hi
-        __builtin_amdgcn_sched_barrier(0);
-        w.p[0][s] = q[(0 * 2 + s) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#undef GAT8_MM
-}
-// The byte-lo form of the four-product stream (round 5; default, GATOR_GAT8_LOBYTE=0 keeps H3): the same three fp16 planes, but the lo
-// plane travels as ONE BYTE per weight.  lo = fp16(w - hi - mid) is zero or a single power of two between 2^-24 and 2^-10 (the
-// residual of two 11-bit roundings of a 24-bit significand is at most one unit of w's last place), so the top byte of
-// fp16(2^24 lo) -- sign, five exponent bits, two mantissa bits -- holds it exactly; the product wave rebuilds the fp16 value with
-// two v_perm_b32 and two v_pk_mul_f16 (x 2^-24, exact: fp16 denormals are on) per four weights in the shadow of the MFMA before,
-// and multiplies the SAME bits in the SAME order: results are bit for bit those of the H3 stream (tests/test_gpu_digest.py), a
-// sixth of the stream's bytes never crosses the L2 -> CU path that bounds this kernel.  gat8_build_stream checks
-// on the device, with this very expansion, that every weight's lo survives the round trip, and keeps the H3 stream if one does not.
-struct H3B { f16x8 p[2][2]; uint4 lo; };     // [plane hi/mid][k-step] + 16 lo bytes (k-step 0: x y, k-step 1: z w): 20 VGPRs
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f16x8 lo_expand(unsigned d0, unsigned d1) {
-    const f16x2_t sc = {(_Float16)5.9604644775390625e-08f, (_Float16)5.9604644775390625e-08f};      // 2^-24
-    union { unsigned u[4]; f16x2_t h[4]; f16x8 v; } o;
-    o.u[0] = __builtin_amdgcn_perm(d0, d0, 0x010c000cu);      // (byte 0, byte 1) -> the high bytes of two halves
-    o.u[1] = __builtin_amdgcn_perm(d0, d0, 0x030c020cu);
-    o.u[2] = __builtin_amdgcn_perm(d1, d1, 0x010c000cu);
-    o.u[3] = __builtin_amdgcn_perm(d1, d1, 0x030c020cu);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o.h[i] = o.h[i] * sc;
-    return o.v;
-}
-template <bool CL>
-__device__ __forceinline__ void tile_mma_refill(H3B& w, const X2& b, f32x16& acc, f32x16& acs, const float* __restrict__ wp, int lane) {
-    const f16x8* q = reinterpret_cast<const f16x8*>(wp) + lane;
-#define GAT8_MM(wv, bpl, s, AC) AC = CL ? GATOR_MFMA_F16(b.p[bpl][s], (wv), AC) : GATOR_MFMA_F16((wv), b.p[bpl][s], AC)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        GAT8_MM(w.p[0][s], 1, s, acs);                     // w hi  * a lo
-        const f16x8 lo = lo_expand(s == 0 ? w.lo.x : w.lo.z, s == 0 ? w.lo.y : w.lo.w);
-        GAT8_MM(lo, 0, s, acs);                            // w lo  * a hi
-        __builtin_amdgcn_sched_barrier(0);
-        if (s == 1) w.lo = reinterpret_cast<const uint4*>(wp + 1024)[lane];
-        __builtin_amdgcn_sched_barrier(0);
-        GAT8_MM(w.p[1][s], 0, s, acs);                     // w mid * a hi
-        __builtin_amdgcn_sched_barrier(0);
-        w.p[1][s] = q[(1 * 2 + s) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-        GAT8_MM(w.p[0][s], 0, s, acc);                     // w hi  * a hi
-        __builtin_amdgcn_sched_barrier(0);
-        w.p[0][s] = q[(0 * 2 + s) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#undef GAT8_MM
-}
-// floats from one tile of a wave's stream to the next
-template <class WT> struct StreamTile { static constexpr int floats = kTileX3; };
-template <> struct StreamTile<H3B> { static constexpr int floats = kTileH3B; };
 // one k-step of the two-plane product (x3_common.h: x2_mma does both): lo*hi | hi*lo | hi*hi
 __device__ __forceinline__ f32x16 x2_mma_step(const X2& A, const X2& B, int s, f32x16 acc) {
     acc = GATOR_MFMA_F16(A.p[1][s], B.p[0][s], acc);
     acc = GATOR_MFMA_F16(A.p[0][s], B.p[1][s], acc);
     return GATOR_MFMA_F16(A.p[0][s], B.p[0][s], acc);
 }
-// operand / weight tile access of the two forms
-__device__ __forceinline__ void ld_tile(X3& o, const float* p, int lane) { o = x3_load(p, lane); }
-__device__ __forceinline__ void ld_tile(X2& o, const float* p, int lane) { o = x2_load(p, lane); }
-__device__ __forceinline__ void ld_tile(H3& o, const float* p, int lane) { o = h3_load(p, lane); }
-__device__ __forceinline__ void ld_tile(H3P2& o, const float* p, int lane) {
-    const f16x8* q = reinterpret_cast<const f16x8*>(p) + lane;
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) o.p[pl][s2] = q[(pl * 2 + s2) * 64];
-}
-__device__ __forceinline__ void ld_tile(H3B& o, const float* p, int lane) {
-    const f16x8* q = reinterpret_cast<const f16x8*>(p) + lane;
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) o.p[pl][s2] = q[(pl * 2 + s2) * 64];
-    o.lo = reinterpret_cast<const uint4*>(p + 1024)[lane];
-}
-template <bool SWZ> __device__ __forceinline__ void ld_opnd(X3& o, const float* p, int lane) { o = x3_load(p, lane); }
-template <bool SWZ> __device__ __forceinline__ void ld_opnd(X2& o, const float* p, int lane) { o = SWZ ? x2_load_swz(p, lane) : x2_load(p, lane); }
-
-// ---- product wave: one unit = the K = 128 contraction of one 32-channel output block (4 weight tiles) --------------------------
-// CL = false: weights as A operand -> T-layout accumulator (token on the lane); CL = true: activations as A -> C-layout.
-// Slot indices are compile-time (S0 = tile offset of the unit inside its block, mod kNT).
-// `b` = the unit's first operand tile, already requested: where that tile was complete two barriers ago (Y for k / v / h0 / h1, Y2
-// for the later fc1 units, the hidden blocks for fc2) the caller reads it BEFORE the barrier that opens the step, so the matrix
-// pipe does not idle through an LDS round trip after every barrier.
-template <int S0, bool CL, bool SWZ = false, class WT, class OT>
-__device__ __forceinline__ void unit4(WT (&W)[kNT], const float* __restrict__& wp, OT b, const float* o1, const float* o2, const float* o3,
-                                      float* raw, int lane) {
-    const float* ops[4] = {o1, o1, o2, o3};
-    f32x16 acc = zero16(), acs = zero16();
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-        OT bn = b;
-        if (kb < 3) ld_opnd<SWZ>(bn, ops[kb + 1], lane);
-        tile_mma_refill<CL>(W[(S0 + kb) % kNT], b, acc, acs, wp, lane);
-        wp += StreamTile<WT>::floats;
-        b = bn;
-    }
-    if constexpr (!std::is_same<WT, X3>::value) acc = acc + acs;
-    store_block(raw, lane, acc);
-}
-// one tile: partial hop-2 linear (linears[1], 128 -> 16) over k block `w` of SB; C-layout
-template <int S0, class OT, class WT>
-__device__ __forceinline__ void unit1(WT (&W)[kNT], const float* __restrict__& wp, const float* o0, float* raw, int lane) {
-    f32x16 acc = zero16(), acs = zero16();
-    OT b;
-    ld_tile(b, o0, lane);
-    tile_mma_refill<true>(W[S0 % kNT], b, acc, acs, wp, lane);
-    wp += StreamTile<WT>::floats;
-    if constexpr (!std::is_same<WT, X3>::value) acc = acc + acs;
-    store_block(raw, lane, acc);
-}
-
-// consume the kPadTiles dummy tiles behind a block: their slots get the tiles kNT positions further down (the next block's)
-template <int S0, class WT>
-__device__ __forceinline__ void skip_pad(WT (&W)[kNT], const float* __restrict__& wp, int lane) {
-#pragma unroll
-    for (int i = 0; i < kPadTiles; ++i) {
-        ld_tile(W[(S0 + i) % kNT], wp, lane);
-        wp += StreamTile<WT>::floats;
-    }
-}
-
-
-// ---- epilogue (TAIL): lifter Linear(128J -> 3J) (GAT.py:151-152), MDR joint tokens and the three layers' cross-attention K / V
-// operand tiles (MDR.py:130-134,37-38,65) -- formerly k_gat_lifter + k_gat_joint (gat_tail.hip: 5.7 + 16.4 us and two launch
-// boundaries at B = 256, with ~2 MFLOP per sample between them; those launches stay for the sample-tiled encoder).  This workgroup owns
-// the sample and ends with its feat on chip:
-//   lifter       a 3J x 128J matrix-vector product: 444 KB (J = 17) of fp32 weights per sample that nobody on the CU can share, i.e.
-//                a stream like the rest of this kernel.  All eight waves walk rows o = wave + 8 r as coalesced 1 KiB loads (lane l owns
-//                k = 256 i + 4 l), exact fp32 FMAs against feat held in registers (read once from the T-layout tiles in X), one DPP
-//                reduction per row.  (The product waves idle from barrier 20 of the last block on, but rows fetched ahead there would live beside the five
-//                weight-stream tiles the block loop carries: 140 - 430 B per lane of scratch.  They stage the small operands instead.)  Fixed order: results do not depend on the batch.
-//   joint tokens jf = Linear(133 -> 64)(cat(pose2d, pose3d / 1000, feat)) + pos_j: the 128 feat columns do not need pose3d, so product waves
-//                0 / 1 (whose share of the rows is the smaller one) contract them behind their last rows; the five other columns are FMAs
-//                once pose3d is known.  Then LayerNorm per layer and the 12 (layer, K | V, channel block) jobs, two on each of the other
-//                six waves, their weight tiles requested behind the last lifter rows (same operand tiles out as k_gat_joint: two fp16
-//                planes of 16 x value).  These token-wise linears run as every other one of the
-//                default arithmetic does -- weights exact on three fp16 planes, activations on two, four partial products -- instead of
-//                k_gat_joint's fp32-input MFMAs: measured with the MFMAs cut out, the 32-MFMA fp32 chains of the K / V jobs
-//                alone were 6.5 us of the epilogue's 15.
-// LDS: the operand tiles A | Bq are dead after barrier 20 of the last block.
-constexpr int kTP = kA;                                 // the joint tokens without their pose3d columns (2 channel blocks, token on the lane)
-constexpr int kTPosj = kTP + 2 * kTile;                 // pos_j tiles (2)
-constexpr int kTVJ = kTPosj + 2 * kTile;                // per-channel vectors
-constexpr int kTXO = kTVJ + 768;                        // pose3d of the sample (3J <= 64 floats)
-enum { TVJ_JFB = 0, TVJ_JF5 = 64, TVJ_N1W = 384, TVJ_N1B = 576, TVJ_TOTAL = 768 };      // jf bias | jf columns 0..4 [5][64] | norm1 w / b [3 layers][64]
-static_assert(kTXO + 64 <= kR, "the epilogue's LDS lives in the dead operand tiles");
-
-__device__ __forceinline__ float dpp_add(float s, int ctrl_tag) {
-    const int u = __builtin_bit_cast(int, s);
-    int m;
-    if (ctrl_tag == 0) m = __builtin_amdgcn_update_dpp(u, u, 0xB1, 0xf, 0xf, false);            // quad_perm [1,0,3,2]
-    else if (ctrl_tag == 1) m = __builtin_amdgcn_update_dpp(u, u, 0x4E, 0xf, 0xf, false);       // quad_perm [2,3,0,1]
-    else if (ctrl_tag == 2) m = __builtin_amdgcn_update_dpp(u, u, 0x141, 0xf, 0xf, false);      // row_half_mirror
-    else m = __builtin_amdgcn_update_dpp(u, u, 0x140, 0xf, 0xf, false);                         // row_mirror
-    return s + __builtin_bit_cast(float, m);
-}
-// sum over the 64 lanes, the same value (and the same association) in every lane
-__device__ __forceinline__ float wave_sum64(float s) {
-    s = dpp_add(s, 0); s = dpp_add(s, 1); s = dpp_add(s, 2); s = dpp_add(s, 3);      // every lane: the total of its row of 16
-    const int u = __builtin_bit_cast(int, s);
-    const float t0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(u, 0)), t1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(u, 16)),
-                t2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(u, 32)), t3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(u, 48));
-    return (t0 + t1) + (t2 + t3);
-}
-// one row of the lifter weight: NI - 1 full 1 KiB chunks and a half chunk (K = 128 J = 256 (NI - 1) + 128 for J = 17, 19)
-template <int NI>
-struct LiftRow { f32x4 w[NI]; };
-template <int NI>
-__device__ __forceinline__ void lift_load(LiftRow<NI>& r, const float* __restrict__ wrow, int lane, bool live) {
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < NI; ++i) r.w[i] = (live && (i < NI - 1 || lane < 32)) ? *reinterpret_cast<const f32x4*>(wrow + 256 * i + 4 * lane) : z;
-}
-template <int NI>
-__device__ __forceinline__ float lift_dot(const LiftRow<NI>& r, const f32x4 (&f)[NI]) {
-    f32x2 acc = {0.f, 0.f};                               // two chains of packed FMAs (components 0, 2 | 1, 3), fixed order
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        acc = pk_fma(f32x2{r.w[i][0], r.w[i][1]}, f32x2{f[i][0], f[i][1]}, acc);
-        acc = pk_fma(f32x2{r.w[i][2], r.w[i][3]}, f32x2{f[i][2], f[i][3]}, acc);
-    }
-    return wave_sum64(acc[0] + acc[1]);
-}
-constexpr int kLiftPre = 2;          // rows per batch; two batches in registers (one being multiplied, one in flight)
-
-#ifdef GATOR_DIAG
-#define GAT8_TSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (tl.tstamps && b == 32 && lane == 0) tl.tstamps[v8 * 8 + (k)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define GAT8_TSTAMP(k)
-#endif
-// HELPER: the calling wave is helper w (holds channel block w of feat in `y`); else product wave w.
-template <int LR, bool HELPER>
-__device__ __forceinline__ void gat8_tail(const Gat8Tail& tl, const float* pose2d, float* lds, int b, int J, int w, int lane) {
-    constexpr int NI = LR == 10 ? 9 : 10;
-    const int h = lane >> 5, tok = lane & 31, tkj = tok < J ? tok : 0;
-    const int v8 = HELPER ? w : 4 + w;                        // row phase of this wave (phases 0 .. 2 own one row more: the helpers', who have nothing else here)
-    const int K = kC * J, R = 3 * J;
-    const float* X = lds + kXo;                               // feat as four T-layout tiles, zero for the tokens that do not exist (stored before barrier 22)
-    float* P = lds + kTP;
-    const float* VJ = lds + kTVJ;
-    float* XO = lds + kTXO;
-    const bool joint = tl.jkv != nullptr;
-    // who does what besides its lifter rows: product waves 0 / 1 the feat columns of the joint-token linear (channel block w, all of K = 128);
-    // the other six waves two K / V jobs each
-    const bool jf_wave = !HELPER && w < 2 && joint;
-    // K / V jobs (layer li, k | v, channel block nb) = 2 pair + nb, pair = 2 li + kv: helper w both blocks of pair w, product wave w block
-    // w & 1 of pair 4 + (w >> 1) -- three jobs on every SIMD, and a wave's jobs share their operand (one layer's LayerNorm)
-    const int pair = HELPER ? w : 4 + (w >> 1), li = pair >> 1, kv = pair & 1;
-    const int job0 = HELPER ? 2 * w : 8 + w, njob = HELPER ? 2 : 1;
-    GAT8_TSTAMP(0);
-    const float bias_r = (lane < 8 && v8 + 8 * lane < R) ? tl.lifter_b[v8 + 8 * lane] : 0.f;      // lane r: the bias of row v8 + 8 r
-    const float* wbase = tl.lifter_w + (size_t)v8 * K;
-    // rows r = 0 .. 7 of this wave in batches of kLiftPre, the next batch in flight while the current one is multiplied
-    constexpr int NB = 8 / kLiftPre;
-    LiftRow<NI> cur[kLiftPre], nxt[kLiftPre];
-#pragma unroll
-    for (int q = 0; q < kLiftPre; ++q) lift_load(cur[q], wbase + (size_t)(8 * q) * K, lane, v8 + 8 * q < R);
-    GAT8_TSTAMP(1);
-    f32x4 f[NI];                                              // feat[k], k = 256 i + 4 lane: token 2 i + (lane >> 5), channels 4 (lane & 31) ..
-    {
-        const int c = 4 * (lane & 31);
-        const float* fx = X + (c >> 5) * kTile + (((c & 31) >> 3) * 64 + 32 * ((c >> 2) & 1)) * 4;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int j = 2 * i + (lane >> 5);
-            f[i] = *reinterpret_cast<const f32x4*>(fx + (j < J ? j : 0) * 4);
-        }
-    }
-    auto job_tile = [&](int job, int i) {
-        const int li = job >> 2, kv = (job >> 1) & 1, nb = job & 1;
-        return h3_load((kv ? tl.j_wv_h3[li] : tl.j_wk_h3[li]) + (size_t)(nb * 2 + i) * kTileX3, lane);
-    };
-    // the weights of what follows the lifter are requested behind the last batch of rows, so that they ride in the same stream
-    H3 wt[4];                                                 // jf wave: its channel block's four k tiles; K / V wave: [job][k block]
-    float p2x = 0.f, p2y = 0.f;
-    float res = 0.f;
-#pragma unroll
-    for (int bt = 0; bt < NB; ++bt) {
-        if (bt + 1 < NB) {
-#pragma unroll
-            for (int q = 0; q < kLiftPre; ++q) {
-                const int r = (bt + 1) * kLiftPre + q;
-                lift_load(nxt[q], wbase + (size_t)(8 * r) * K, lane, v8 + 8 * r < R);
-            }
-        }
-        auto tail_tiles = [&](int i0) {       // two of the four weight tiles of what follows (requested while the last rows are multiplied)
-            if (jf_wave) {
-#pragma unroll
-                for (int kb = i0; kb < i0 + 2; ++kb) wt[kb] = h3_load(tl.jf_h3 + (size_t)(w * 4 + kb) * kTileX3, lane);
-            } else if (i0 < 2 * njob) {
-#pragma unroll
-                for (int i = i0; i < i0 + 2; ++i) wt[i] = job_tile(job0 + (i >> 1), i & 1);
-            }
-        };
-        if (bt + 1 == NB && joint) {
-            tail_tiles(0);
-            p2x = pose2d[((size_t)b * J + tkj) * 2];
-            p2y = pose2d[((size_t)b * J + tkj) * 2 + 1];
-        }
-#pragma unroll
-        for (int q = 0; q < kLiftPre; ++q) {
-            const int r = bt * kLiftPre + q;
-            const float tot = lift_dot(cur[q], f);
-            res = lane == r ? tot : res;
-            if (bt + 1 == NB && q == 0 && joint) { __builtin_amdgcn_sched_barrier(0); tail_tiles(2); }      // (this row's registers are free now)
-        }
-        if (bt + 1 < NB) {
-#pragma unroll
-            for (int q = 0; q < kLiftPre; ++q) cur[q] = nxt[q];
-        }
-    }
-    GAT8_TSTAMP(2);
-    // x_out[o] = bias[o] + sum_k W[o][k] feat[k]
-    if (lane < 8 && v8 + 8 * lane < R) {
-        const float xo = res + bias_r;
-        tl.x_out[(size_t)b * R + v8 + 8 * lane] = xo;
-        XO[v8 + 8 * lane] = xo;
-    }
-    if (!joint) return;
-    if (jf_wave) {
-        // jf without its pose3d columns: bias + pos_j + feat columns (GATOR.py:19, MDR.py:130-134), channel block w, token on the lane
-        f32x16 acc = zero16(), acs = zero16();
-        const f32x16 init = chanvec_lds(VJ, TVJ_JFB + 32 * w, h) + load_block(lds + kTPosj + w * kTile, lane);
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            const X2 fx2 = x2_split(load_block(X + kb * kTile, lane) * 16.0f);
-            acs = h3_mma_wa_small(wt[kb], fx2, acs);
-            acc = h3_mma_wa_main(wt[kb], fx2, acc);
-        }
-        store_block(P + w * kTile, lane, fma16(acc + acs, tl.jf_inv, init));
-        wt[0] = job_tile(job0, 0);                             // (its own K / V job's tiles, in flight across the barrier)
-        wt[1] = job_tile(job0, 1);
-    }
-    GAT8_TSTAMP(3);
-    __syncthreads();
-    GAT8_TSTAMP(4);
-    // jf = that + columns 0..4 (pose2d, pose3d / 1000)
-    f32x16 jf[2];
-    {
-        const float pin[5] = {p2x, p2y, XO[tkj * 3] / 1000.f, XO[tkj * 3 + 1] / 1000.f, XO[tkj * 3 + 2] / 1000.f};
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-            f32x16 acc = load_block(P + nb * kTile, lane);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) acc += chanvec_lds(VJ, TVJ_JF5 + i * 64 + 32 * nb, h) * pin[i];
-            jf[nb] = acc;
-        }
-    }
-    auto rs = [&](const f32x16& p, const f32x16& q) {
-        float s = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s += p[r] + q[r];
-        return s + xhalf(s);
-    };
-    const float mean = rs(jf[0], jf[1]) * (1.0f / 64.0f);
-    const f32x16 d0 = jf[0] - mean, d1 = jf[1] - mean;
-    const float rstd = 1.0f / sqrtf(rs(d0 * d0, d1 * d1) * (1.0f / 64.0f) + 1e-5f);
-    GAT8_TSTAMP(5);
-    // per LBF layer: k = wk(LN1(jf)), v = wv(LN1(jf)) as MFMA operand tiles (two fp16 planes of 16 x value: mdr_ops.h, cross_attention_head / JointX2)
-    const f32x16 fz0 = d0 * rstd * chanvec_lds(VJ, TVJ_N1W + 64 * li, h) + chanvec_lds(VJ, TVJ_N1B + 64 * li, h);
-    const f32x16 fz1 = d1 * rstd * chanvec_lds(VJ, TVJ_N1W + 64 * li + 32, h) + chanvec_lds(VJ, TVJ_N1B + 64 * li + 32, h);
-    const X2 z0 = x2_split(fz0 * 16.0f), z1 = x2_split(fz1 * 16.0f);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        if (q >= njob) break;
-        const int nb = (job0 + q) & 1;
-        float* out = tl.jkv + (((size_t)b * 3 + li) * 4 + kv * 2 + nb) * kTile;
-        const H3 &k0 = wt[2 * q], &k1 = wt[2 * q + 1];
-        f32x16 r0 = zero16(), r1 = zero16();                   // r1: the cross products of both k blocks, r0: the hi x hi ones (x3_common.h on the order)
-        if (kv == 0) {
-            r1 = h3_mma_wa_small(k1, z1, h3_mma_wa_small(k0, z0, r1));
-            r0 = h3_mma_wa_main(k1, z1, h3_mma_wa_main(k0, z0, r0));
-            r0 += r1;
-            if (tok >= J) r0 = zero16();                       // joints >= J: zero rows (masked in the softmax anyway)
-        } else {
-            r1 = h3_mma_aw_small(z1, k1, h3_mma_aw_small(z0, k0, r1));
-            r0 = h3_mma_aw_main(z1, k1, h3_mma_aw_main(z0, k0, r0));
-            r0 += r1;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) r0[r] = (kap(r) + 4 * h < J) ? r0[r] : 0.f;
-        }
-        x2_store(out, lane, x2_split(r0 * (16.0f * tl.kv_inv)));
-        GAT8_TSTAMP(6 + q);
-    }
-}
 
 // H4: the token-wise products on four partial products (weights H3, operands X2; raw tiles carry 1 / a.lin_inv) instead of six
 template <bool H4, int LR, bool H2 = false, bool LB = false, bool TAIL = false>
 __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
     static_assert(H4 || !TAIL, "the fused tail writes two-plane K / V tiles: four-product forms only");
-    static_assert(H4 || !H2, "the one-plane form is a variant of the four-product form");
-    static_assert((H4 && !H2) || !LB, "the byte-lo stream is a form of the four-product stream");
-    typedef typename std::conditional<LB, H3B, typename std::conditional<H2, H3P2, typename std::conditional<H4, H3, X3>::type>::type>::type WT;
-    constexpr int kWF = StreamTile<WT>::floats;                 // floats per tile of the weight stream
-    typedef typename std::conditional<H4, X2, X3>::type OT;
+    using F = Gat8Stream<H4, H2, LB>;                           // the form of the weight stream (gat8_forms.h)
+    constexpr int kWF = F::kTileFloats;                         // floats per tile of the weight stream
     const float inv = H4 ? a.lin_inv : 1.0f;
     // operand tile of a true-scale register tile; pick-up of a raw product tile with what is added to it
     // Token lanes that do not exist (15 of a tile's 32 at J = 17) store ZERO operands: no live value changes (a token's row never
@@ -898,10 +249,10 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
     // two sequences differ (a barrier only one role executes hangs the GPU); keep that test in the CPU suite.
     if (is_prod) {
         // =========================================== product waves ===========================================================
-        WT W[kNT];                                                          // the head of the weight stream (held back until here: five tiles
+        typename F::W W[kNT];                                                          // the head of the weight stream (held back until here: five tiles
         const float* __restrict__ wp = a.wstream + (size_t)w * kWaveTiles * kWF;         // live across the embedding would spill)
 #pragma unroll
-        for (int s = 0; s < kNT; ++s) { ld_tile(W[s], wp, lane); wp += kWF; }
+        for (int s = 0; s < kNT; ++s) { W[s] = F::load(wp, lane); wp += kWF; }
         asm volatile("" ::: "memory");
 #ifdef GATOR_DIAG
         unsigned long long* st_lds = reinterpret_cast<unsigned long long*>(lds + kGat8LdsFloats);
@@ -917,72 +268,67 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
             bi_ = bi;
 #endif
             const float *Y0 = A, *Y1 = A + kTileX3, *Y2 = A + 2 * kTileX3, *Y3 = A + 3 * kTileX3;
-            OT pre;
-            ld_tile(pre, Y0, lane);
-            unit4<OFF_Q % kNT, false>(W, wp, pre, Y1, Y2, Y3, R0w, lane);             // q  (T)
-            ld_tile(pre, Y0, lane);
+            typename F::O pre;
+            pre = F::load_opnd(Y0, lane);
+            unit4<F, gat8_slot(U_Q), false>(W, wp, pre, Y1, Y2, Y3, R0w, lane);             // q  (T)
+            pre = F::load_opnd(Y0, lane);
             GAT8_BAR(1);
-            unit4<OFF_K % kNT, false>(W, wp, pre, Y1, Y2, Y3, R1w, lane);             // k  (T)
-            ld_tile(pre, Y0, lane);
+            unit4<F, gat8_slot(U_K), false>(W, wp, pre, Y1, Y2, Y3, R1w, lane);             // k  (T)
+            pre = F::load_opnd(Y0, lane);
             GAT8_BAR(2);
-            unit4<OFF_V % kNT, true>(W, wp, pre, Y1, Y2, Y3, R0w, lane);              // v  (C)
-            ld_tile(pre, Y0, lane);
+            unit4<F, gat8_slot(U_V), true>(W, wp, pre, Y1, Y2, Y3, R0w, lane);              // v  (C)
+            pre = F::load_opnd(Y0, lane);
             GAT8_BAR(3);
-            unit4<OFF_H0 % kNT, false>(W, wp, pre, Y1, Y2, Y3, R1w, lane);             // h0 = y W[0]  (T: its MGCN term is token-wise)
-            ld_tile(pre, Y0, lane);
+            unit4<F, gat8_slot(U_H0), false>(W, wp, pre, Y1, Y2, Y3, R1w, lane);             // h0 = y W[0]  (T: its MGCN term is token-wise)
+            pre = F::load_opnd(Y0, lane);
             GAT8_BAR(4);
-            unit4<OFF_H1 % kNT, true>(W, wp, pre, Y1, Y2, Y3, R0w, lane);              // h1 = y W[1]  (C)
+            unit4<F, gat8_slot(U_H1), true>(W, wp, pre, Y1, Y2, Y3, R0w, lane);              // h1 = y W[1]  (C)
             GAT8_BAR(5);
-            ld_tile(pre, Bq, lane);
-            unit4<OFF_PROJ % kNT, false>(W, wp, pre, Bq + kTileX3, Bq + 2 * kTileX3, Bq + 3 * kTileX3, R1w, lane);                   // proj(AT)
+            pre = F::load_opnd(Bq, lane);
+            unit4<F, gat8_slot(U_PROJ), false>(W, wp, pre, Bq + kTileX3, Bq + 2 * kTileX3, Bq + 3 * kTileX3, R1w, lane);                   // proj(AT)
             GAT8_BAR(6);
             GAT8_BAR(7);                                                    // helpers: SB = proj + attention bias + MGCN
-            ld_tile(pre, Bq + 4 * kTileX3, lane);
-            unit4<OFF_LIN0 % kNT, true>(W, wp, pre, Bq + 5 * kTileX3, Bq + 6 * kTileX3, Bq + 7 * kTileX3, R0w, lane);                // linears[0](SB)  (C)
-            unit1<OFF_LIN1 % kNT, OT>(W, wp, Bq + (4 + w) * kTileX3, X + w * kTile, lane);                                              // linears[1], k block w
+            pre = F::load_opnd(Bq + 4 * kTileX3, lane);
+            unit4<F, gat8_slot(U_LIN0), true>(W, wp, pre, Bq + 5 * kTileX3, Bq + 6 * kTileX3, Bq + 7 * kTileX3, R0w, lane);                // linears[0](SB)  (C)
+            unit1<F, gat8_slot(U_LIN1)>(W, wp, Bq + (4 + w) * kTileX3, X + w * kTile, lane);                                              // linears[1], k block w
             GAT8_BAR(8);
             GAT8_BAR(9);                                                    // helpers: hop aggregations -> FB
-            ld_tile(pre, Bq + 8 * kTileX3, lane);
-            unit4<OFF_BACK % kNT, false>(W, wp, pre, Bq + 9 * kTileX3, Bq + 10 * kTileX3, Bq + 11 * kTileX3, R1w, lane);             // linearback(FB), k < 128
+            pre = F::load_opnd(Bq + 8 * kTileX3, lane);
+            unit4<F, gat8_slot(U_BACK), false>(W, wp, pre, Bq + 9 * kTileX3, Bq + 10 * kTileX3, Bq + 11 * kTileX3, R1w, lane);             // linearback(FB), k < 128
             GAT8_BAR(10);
             GAT8_BAR(11);                                                   // helpers: residual
             GAT8_BAR(12);                                                   // helpers: Y2 = LN2(x)
-            ld_tile(pre, Y0, lane);
-            unit4<(OFF_FC1 + 0) % kNT, H4>(W, wp, pre, Y1, Y2, Y3, R0w, lane);             // fc1, hidden block 4w
-            ld_tile(pre, Y0, lane);
+            pre = F::load_opnd(Y0, lane);
+            unit4<F, gat8_slot(U_FC1, 0), H4>(W, wp, pre, Y1, Y2, Y3, R0w, lane);             // fc1, hidden block 4w
+            pre = F::load_opnd(Y0, lane);
             GAT8_BAR(13);
-            unit4<(OFF_FC1 + 4) % kNT, H4>(W, wp, pre, Y1, Y2, Y3, R1w, lane);             //      4w + 1
-            ld_tile(pre, Y0, lane);
+            unit4<F, gat8_slot(U_FC1, 4), H4>(W, wp, pre, Y1, Y2, Y3, R1w, lane);             //      4w + 1
+            pre = F::load_opnd(Y0, lane);
             GAT8_BAR(14);
-            unit4<(OFF_FC1 + 8) % kNT, H4>(W, wp, pre, Y1, Y2, Y3, R0w, lane);             //      4w + 2
-            ld_tile(pre, Y0, lane);
+            unit4<F, gat8_slot(U_FC1, 8), H4>(W, wp, pre, Y1, Y2, Y3, R0w, lane);             //      4w + 2
+            pre = F::load_opnd(Y0, lane);
             GAT8_BAR(15);
-            unit4<(OFF_FC1 + 12) % kNT, H4>(W, wp, pre, Y1, Y2, Y3, R1w, lane);             //      4w + 3
-            ld_opnd<H4>(pre, Bq, lane);                                    // (hidden blocks 4w' were complete at barrier 14)
+            unit4<F, gat8_slot(U_FC1, 12), H4>(W, wp, pre, Y1, Y2, Y3, R1w, lane);             //      4w + 3
+            pre = F::template load_opnd<H4>(Bq, lane);                                    // (hidden blocks 4w' were complete at barrier 14)
             GAT8_BAR(16);
             // fc2: unit u contracts over hidden blocks {4w' + u}: tiles 3w' + u of B for u < 3, tile w' of A for u = 3
-            unit4<(OFF_FC2 + 0) % kNT, false, H4>(W, wp, pre, Bq + 3 * kTileX3, Bq + 6 * kTileX3, Bq + 9 * kTileX3, R0w, lane);
-            ld_opnd<H4>(pre, Bq + 1 * kTileX3, lane);
+            unit4<F, gat8_slot(U_FC2, 0), false, H4>(W, wp, pre, Bq + 3 * kTileX3, Bq + 6 * kTileX3, Bq + 9 * kTileX3, R0w, lane);
+            pre = F::template load_opnd<H4>(Bq + 1 * kTileX3, lane);
             GAT8_BAR(17);
-            unit4<(OFF_FC2 + 4) % kNT, false, H4>(W, wp, pre, Bq + 4 * kTileX3, Bq + 7 * kTileX3, Bq + 10 * kTileX3, R1w, lane);
-            ld_opnd<H4>(pre, Bq + 2 * kTileX3, lane);
+            unit4<F, gat8_slot(U_FC2, 4), false, H4>(W, wp, pre, Bq + 4 * kTileX3, Bq + 7 * kTileX3, Bq + 10 * kTileX3, R1w, lane);
+            pre = F::template load_opnd<H4>(Bq + 2 * kTileX3, lane);
             GAT8_BAR(18);
-            unit4<(OFF_FC2 + 8) % kNT, false, H4>(W, wp, pre, Bq + 5 * kTileX3, Bq + 8 * kTileX3, Bq + 11 * kTileX3, R0w, lane);
-            ld_opnd<H4>(pre, Y0, lane);                                    // (hidden blocks 4w' + 3, complete at barrier 17)
+            unit4<F, gat8_slot(U_FC2, 8), false, H4>(W, wp, pre, Bq + 5 * kTileX3, Bq + 8 * kTileX3, Bq + 11 * kTileX3, R0w, lane);
+            pre = F::template load_opnd<H4>(Y0, lane);                                    // (hidden blocks 4w' + 3, complete at barrier 17)
             GAT8_BAR(19);
-            unit4<(OFF_FC2 + 12) % kNT, false, H4>(W, wp, pre, Y1, Y2, Y3, R1w, lane);
-            skip_pad<(OFF_FC2 + 16) % kNT>(W, wp, lane);                          // the block's dummy tiles: refill their slots, no product
+            unit4<F, gat8_slot(U_FC2, 12), false, H4>(W, wp, pre, Y1, Y2, Y3, R1w, lane);
+            skip_pad<F, gat8_slot(U_COUNT)>(W, wp, lane);                          // the block's dummy tiles: refill their slots, no product
             GAT8_BAR(20);
             if constexpr (TAIL) {
                 if (bi + 1 == kDepth) {      // idle from here on: stage the epilogue's vectors and pos_j tiles (the operand tiles are dead), fetch the first lifter rows
                     if (a.tl.jkv) {
                         const Gat8Tail& tl = a.tl;
-                        if (t < TVJ_TOTAL / 4) {
-                            const int off = 4 * t;
-                            const float* src = off < TVJ_JF5 ? tl.jf_b + off : off < TVJ_N1W ? tl.jf5 + (off - TVJ_JF5)
-                                               : off < TVJ_N1B ? tl.j_n1w[(off - TVJ_N1W) >> 6] + (off & 63) : tl.j_n1b[(off - TVJ_N1B) >> 6] + (off & 63);
-                            reinterpret_cast<f32x4*>(lds + kTVJ)[t] = *reinterpret_cast<const f32x4*>(src);
-                        }
+                        if (t < VJ_TOTAL / 4) joint_stage_vecs(tl, lds + kTVJ, t);
                         for (int e = t; e < 2 * kTile / 4; e += 256)
                             reinterpret_cast<f32x4*>(lds + kTPosj)[e] = reinterpret_cast<const f32x4*>(tl.posj_T)[e];
                     }
@@ -1005,7 +351,7 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
         return;
     }
     if (a.dbg & 16) {      // barriers + the L2 warm-up of the weight streams only: what the product waves cost with warm weights
-        __syncthreads();
+        __syncthreads();       // (warm_weights of the block loop, written again: shared as a function it moves every form's instructions)
         for (int bi = 0; bi < kDepth; ++bi)
             for (int n = 1; n <= 22; ++n) {
                 if ((n == 2 || n == 19) && bi + 1 < kDepth && a.pf_loads > 0) {
@@ -1013,7 +359,7 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
                     const int share = a.pf_loads * 8192, first = ((b >> 3) % a.pf_n) * share, lim = kBlkTiles * kWF * 4 - 128;
                     const int i0 = n == 2 ? 0 : (a.pf_loads + 1) / 2, i1 = n == 2 ? (a.pf_loads + 1) / 2 : a.pf_loads;
                     for (int i = i0; i < i1; ++i)
-                        glds4(reinterpret_cast<const float*>(wsrc + min(first + i * 8192 + lane * 128, lim)), lds + kDummy + w * 256);
+                        glds<4>(reinterpret_cast<const float*>(wsrc + min(first + i * 8192 + lane * 128, lim)), lds + kDummy + w * 256);
                 }
                 __syncthreads();
             }
@@ -1051,7 +397,7 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
             const char* wsrc = reinterpret_cast<const char*>(a.wstream + ((size_t)w * kWaveTiles + (size_t)(bi + 1) * kBlkTiles) * kWF);
             const int share = a.pf_loads * 8192, first = ((b >> 3) % a.pf_n) * share, lim = kBlkTiles * kWF * 4 - 128;
             for (int i = i0; i < i1; ++i)
-                glds4(reinterpret_cast<const float*>(wsrc + min(first + i * 8192 + lane * 128, lim)), dummy);
+                glds<4>(reinterpret_cast<const float*>(wsrc + min(first + i * 8192 + lane * 128, lim)), dummy);
         };
         // ---- step 1: constants of the attention (nothing to pick up yet)
         const f32x16 bq = load_chanvec_T(vec, V_QKVB + 32 * w, h), bk = load_chanvec_T(vec, V_QKVB + 128 + 32 * w, h);
@@ -1072,7 +418,7 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
                 auto touch = [&](const float* base, int bytes) {
                     const int share = ((bytes / parts + 127) / 128) * 128;
                     for (int off = lane * 128; off < share; off += 8192)
-                        glds4(reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + min(idx * share + off, bytes - 128)), dummy);
+                        glds<4>(reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + min(idx * share + off, bytes - 128)), dummy);
                 };
                 touch(a.tl.lifter_w, 3 * J * kC * J * 4);
                 if (a.tl.jkv) {
@@ -1109,8 +455,8 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
             for (int r = 0; r < 16; ++r) {
                 if (r < LR) {
                     const bool ok = kap(r) + 4 * h < J;
-                    sa[r] = ok ? (sa[r] * sscale + ba[r]) * kLog2e8 : -1e30f;        // q k^T * head_dim**-0.5 + hop/path bias
-                    sb[r] = ok ? (sb[r] * sscale + bb[r]) * kLog2e8 : -1e30f;
+                    sa[r] = ok ? (sa[r] * sscale + ba[r]) * kLog2e : -1e30f;        // q k^T * head_dim**-0.5 + hop/path bias
+                    sb[r] = ok ? (sb[r] * sscale + bb[r]) * kLog2e : -1e30f;
                 } else {
                     sa[r] = 0.f;
                     sb[r] = 0.f;
@@ -1299,7 +645,7 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
                 GAT8_SUB(3);
             } else {
                 f32x16 hd = pick(raw, lane, fb.v);
-                gelu_tile8(hd);
+                gelu_pairs<8>(hd);
                 st_opnd(dst, lane, hd);
             }
         };
@@ -1323,10 +669,10 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
         if (warm) warm_weights((a.pf_loads + 1) / 2, a.pf_loads);
         if (warm) {                                  // this helper's share of the next block's tables and vectors, one lane per line
             const int l32 = lane & 31;
-            glds4(h == 0 ? nx.mdT + (size_t)w * kTile + l32 * 32 : nx.mc + (size_t)w * kTile + l32 * 32, dummy);
-            if (w == 0) glds4(nx.vecs + lane * 32, dummy);
-            if (w == 1) glds4(h == 0 ? nx.aoffT + l32 * 32 : nx.f1b + l32 * 32, dummy);
-            glds4(nx.back32 + (size_t)(w * 5 + 4) * kTile + (lane & 15) * 32, dummy);
+            glds<4>(h == 0 ? nx.mdT + (size_t)w * kTile + l32 * 32 : nx.mc + (size_t)w * kTile + l32 * 32, dummy);
+            if (w == 0) glds<4>(nx.vecs + lane * 32, dummy);
+            if (w == 1) glds<4>(h == 0 ? nx.aoffT + l32 * 32 : nx.f1b + l32 * 32, dummy);
+            glds<4>(nx.back32 + (size_t)(w * 5 + 4) * kTile + (lane & 15) * 32, dummy);
         }
         GAT8_BAR(19);
         f32x16 c23 = load_block(R0w, lane);
@@ -1341,14 +687,7 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
         xw += c01 + c23;
         tile_stats(xw, lds + kStat + w * 64, lane);
         if (a.blk_tap && tok < J) {          // debug tap (off in timed runs): this wave's channel block of the block output
-            float* dst = a.blk_tap + (((size_t)bi * a.tapB + b) * J + tok) * kC + 32 * w + 4 * h;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 v4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v4[j] = xw[4 * g + j];
-                *reinterpret_cast<f32x4*>(dst + 8 * g) = v4;
-            }
+            store_row_block(a.blk_tap + (((size_t)bi * a.tapB + b) * J + tok) * kC + 32 * w, h, xw);
         }
         GAT8_BAR(21);
         // ---- step 22: Y = LN1(x) for the next block; after the last block LN -> GELU -> feat (GAT.py:148-150)
@@ -1357,16 +696,8 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
             if (!last) {
                 st_opnd(A + w * kTileX3, lane, y);
             } else {
-                gelu_tile8(y);
-                if (tok < J) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        f32x4 v4;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v4[j] = y[4 * g + j];
-                        *reinterpret_cast<f32x4*>(a.feat + ((size_t)b * J + tok) * kC + 32 * w + 8 * g + 4 * h) = v4;
-                    }
-                }
+                gelu_pairs<8>(y);
+                if (tok < J) store_row_block(a.feat + ((size_t)b * J + tok) * kC + 32 * w, h, y);
                 if constexpr (TAIL) {        // feat stays on chip for the epilogue: channel block w as a T-layout tile (X is free since step 9);
                     if (tok >= J) y = zero16();      // zero for the token lanes that do not exist (they are operand columns of the joint-token linear)
                     store_block(X + w * kTile, lane, y);
@@ -1379,52 +710,23 @@ __global__ __launch_bounds__(512, 2) void k_gat8(const Gat8Args a) {
     if constexpr (TAIL) gat8_tail<LR, true>(a.tl, a.pose2d, lds, b, J, w, lane);
 }
 
-// one workgroup per destination tile: dst tile i <- src tile idx[i]  (TILE floats: 6 KiB X3 tiles or 4 KiB fp32 tiles)
-template <int TILE>
-__global__ void k_gather_tiles(const float* __restrict__ src, const int* __restrict__ idx, float* __restrict__ dst) {
-    const f32x4* s = reinterpret_cast<const f32x4*>(src + (size_t)idx[blockIdx.x] * TILE);
-    f32x4* d = reinterpret_cast<f32x4*>(dst + (size_t)blockIdx.x * TILE);
-    for (int e = threadIdx.x; e < TILE / 4; e += blockDim.x) d[e] = s[e];
-}
-// H3 stream -> byte-lo stream, one wave per tile: hi and mid planes copied, lo packed as the top byte of fp16(2^24 lo); *bad counts
-// the weights whose lo does not come back bit for bit from the product wave's own expansion (lo_expand)
-__global__ void k_h3_to_h3b(const float* __restrict__ src, float* __restrict__ dst, unsigned* __restrict__ bad) {
-    const int lane = threadIdx.x;
-    const f16x8* q = reinterpret_cast<const f16x8*>(src + (size_t)blockIdx.x * kTileX3) + lane;
-    f16x8* d = reinterpret_cast<f16x8*>(dst + (size_t)blockIdx.x * kTileH3B) + lane;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) d[i * 64] = q[i * 64];
-    unsigned pk[4] = {0, 0, 0, 0};
-    unsigned nbad = 0;
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-        const f16x8 lo = q[(4 + s2) * 64];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const _Float16 up = (_Float16)((float)lo[j] * 16777216.0f);
-            pk[s2 * 2 + (j >> 2)] |= (unsigned)(__builtin_bit_cast(unsigned short, up) >> 8) << (8 * (j & 3));
-        }
-        const f16x8 back = lo_expand(pk[s2 * 2], pk[s2 * 2 + 1]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            nbad += __builtin_bit_cast(unsigned short, (_Float16)back[j]) != __builtin_bit_cast(unsigned short, (_Float16)lo[j]);
-    }
-    reinterpret_cast<uint4*>(dst + (size_t)blockIdx.x * kTileH3B + 1024)[lane] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-    if (nbad) atomicAdd(bad, nbad);
-}
-
 }  // namespace
 
 constexpr size_t kGat8Lds = (size_t)(kGat8LdsFloats + kDiagLdsFloats) * sizeof(float);
 
-// The eleven forms of k_gat8, named once: the dynamic-LDS opt-in and the launch both read this table
+// The eleven forms of k_gat8, named once with what the host needs to know of their weight stream (gat8_forms.h): the dynamic-LDS
+// opt-in and the launch both read this table
 using Gat8Kernel = void (*)(const Gat8Args);
-const struct { Gat8Form form; Gat8Kernel kernel; } kGat8Kernels[] = {
-    {{false, 16, false, false, false}, k_gat8<false, 16>}, {{true, 10, false, false, false}, k_gat8<true, 10>}, {{true, 12, false, false, false}, k_gat8<true, 12>},
-    {{true, 10, true, false, false}, k_gat8<true, 10, true>}, {{true, 12, true, false, false}, k_gat8<true, 12, true>},
-    {{true, 10, false, true, false}, k_gat8<true, 10, false, true>}, {{true, 12, false, true, false}, k_gat8<true, 12, false, true>},
-    {{true, 10, true, false, true}, k_gat8<true, 10, true, false, true>}, {{true, 12, true, false, true}, k_gat8<true, 12, true, false, true>},
-    {{true, 10, false, true, true}, k_gat8<true, 10, false, true, true>}, {{true, 12, false, true, true}, k_gat8<true, 12, false, true, true>}};
+struct Gat8Entry { Gat8Form form; Gat8Kernel kernel; int tile_floats; bool byte_lo; };
+template <bool H4, int LR, bool H2 = false, bool LB = false, bool TAIL = false>
+constexpr Gat8Entry gat8_entry() {
+    using F = Gat8Stream<H4, H2, LB>;
+    return {{H4, LR, H2, LB, TAIL}, k_gat8<H4, LR, H2, LB, TAIL>, F::kTileFloats, F::kByteLo};
+}
+const Gat8Entry kGat8Kernels[] = {
+    gat8_entry<false, 16>(), gat8_entry<true, 10>(), gat8_entry<true, 12>(), gat8_entry<true, 10, true>(), gat8_entry<true, 12, true>(),
+    gat8_entry<true, 10, false, true>(), gat8_entry<true, 12, false, true>(), gat8_entry<true, 10, true, false, true>(),
+    gat8_entry<true, 12, true, false, true>(), gat8_entry<true, 10, false, true, true>(), gat8_entry<true, 12, false, true, true>()};
 
 int gat8_prepare_device() {
     for (const auto& e : kGat8Kernels)
@@ -1434,67 +736,6 @@ int gat8_prepare_device() {
 
 // The per-wave weight streams: the X3 tile grids of fused_create_gat (gxbuf, tile-for-tile image of gbuf from gblk[0].qkv on)
 // re-ordered into the order product wave w consumes them, block after block.
-int gat8_build_stream(FusedState* f, void* stream) {
-    if (!f->opt.gat_x3 || !f->gxbuf) return GATOR_OK;
-    std::vector<int> idx((size_t)4 * kWaveTiles + kNT, 0);
-    auto tile_of = [&](const float* grid) { return (int)((grid - f->gblk[0].qkv) / kTile); };
-    for (int w = 0; w < 4; ++w) {
-        int* o = idx.data() + (size_t)w * kWaveTiles;
-        for (int bi = 0; bi < kDepth; ++bi) {
-            const GatBlockPk& p = f->gblk[bi];
-            const int qkv = tile_of(p.qkv), w0 = tile_of(p.w0), w1 = tile_of(p.w1), proj = tile_of(p.proj), lin0 = tile_of(p.lin0), lin1 = tile_of(p.lin1),
-                      back = tile_of(p.back), fc1 = tile_of(p.fc1), fc2 = tile_of(p.fc2);
-            for (int kb = 0; kb < 4; ++kb) *o++ = qkv + (w * 4 + kb);                  // q
-            for (int kb = 0; kb < 4; ++kb) *o++ = qkv + ((4 + w) * 4 + kb);            // k
-            for (int kb = 0; kb < 4; ++kb) *o++ = qkv + ((8 + w) * 4 + kb);            // v
-            for (int kb = 0; kb < 4; ++kb) *o++ = w0 + (w * 4 + kb);                   // MGCN W[0]
-            for (int kb = 0; kb < 4; ++kb) *o++ = w1 + (w * 4 + kb);                   // MGCN W[1]
-            for (int kb = 0; kb < 4; ++kb) *o++ = proj + (w * 4 + kb);                 // attention proj
-            for (int kb = 0; kb < 4; ++kb) *o++ = lin0 + (w * 4 + kb);                 // X_Feat linears[0]
-            *o++ = lin1 + w;                                                           // X_Feat linears[1], k block w
-            for (int kb = 0; kb < 4; ++kb) *o++ = back + (w * 5 + kb);                 // linearback, k < 128
-            for (int j = 0; j < 4; ++j)
-                for (int kb = 0; kb < 4; ++kb) *o++ = fc1 + ((4 * w + j) * 4 + kb);    // fc1, hidden block 4w + j
-            for (int u = 0; u < 4; ++u)
-                for (int wq = 0; wq < 4; ++wq) *o++ = fc2 + (w * 16 + 4 * wq + u);     // fc2, hidden blocks {4w' + u}
-            for (int i = 0; i < kPadTiles; ++i) *o++ = qkv;                             // dummy: loaded into a slot, never multiplied
-        }
-        if (o - idx.data() != (ptrdiff_t)(w + 1) * kWaveTiles) return fail(GATOR_EINVAL, "gat8_build_stream: tile count");
-    }
-    DevBuf<int> d_idx;      // temporaries: freed on every return path
-    DevBuf<float> h3;
-    GATOR_TRY(d_idx.alloc(idx.size() * sizeof(int)));
-    GATOR_HIP_CHECK(hipMemcpyAsync(d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
-    GATOR_TRY(f->g8stream.alloc((size_t)kStreamFloats * sizeof(float)));
-    if (f->opt.gat8_h4) {      // the four-product form streams three fp16 planes of 2^shift * w: the fp32 tiles are put in stream order
-        float& ratio = f->h3_tile_ratio[GATOR_H3SET_GAT8];  // first, so that the shift comes from exactly the weights the kernel multiplies (not the tables in between)
-        GATOR_TRY(h3.alloc(idx.size() * kTile * sizeof(float)));
-        k_gather_tiles<kTile><<<(unsigned)idx.size(), 128, 0, (hipStream_t)stream>>>(f->gblk[0].qkv, d_idx.get(), h3.get());
-        int rc = fused_repack_h3(h3, f->g8stream, (int64_t)idx.size(), &f->gat8_wshift, &ratio, stream);
-        if (rc) return rc;
-        if (!h3_set_holds(ratio)) h3_demote(f, GATOR_H3SET_GAT8);      // the exact six products on the X3 stream below, as under GATOR_GAT8_H4=0
-    }
-    if (f->opt.gat8_h4) {
-        if (f->opt.gat8_lobyte) {      // the byte-lo image of the same stream (H3B): used only if every lo value survives the round trip
-            DevBuf<unsigned> d_bad;
-            GATOR_TRY(d_bad.alloc(sizeof(unsigned)));
-            GATOR_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(unsigned), (hipStream_t)stream));
-            GATOR_TRY(f->g8stream_b.alloc((size_t)kStreamFloatsB * sizeof(float)));
-            k_h3_to_h3b<<<(unsigned)idx.size(), 64, 0, (hipStream_t)stream>>>(f->g8stream.get(), f->g8stream_b.get(), d_bad.get());
-            GATOR_HIP_CHECK(hipGetLastError());
-            unsigned nbad = 0;
-            GATOR_HIP_CHECK(hipMemcpyAsync(&nbad, d_bad, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream));
-            GATOR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-            if (nbad) { f->opt.gat8_lobyte = false; f->g8stream_b.reset(); }
-        }
-    } else {
-        k_gather_tiles<kTileX3><<<(unsigned)idx.size(), 128, 0, (hipStream_t)stream>>>(f->gxbuf.get(), d_idx.get(), f->g8stream.get());
-    }
-    GATOR_HIP_CHECK(hipGetLastError());
-    GATOR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    return GATOR_OK;
-}
-
 #ifdef GATOR_DIAG
 // GATOR_GAT_STAMPS: the stamp buffers of one launch, zeroed before it, read back (synchronously) and printed behind it
 constexpr int kGat8Stamps = 2 * kDepth * 23 * 2 + kDepth * 8;
@@ -1552,10 +793,10 @@ static int gat8_diag_report(Gat8Diag& d, int B) {
 #endif
 
 int launch_gat8(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pose2d, int B_total, float* pose3d, void* stream) {
-    Gat8Kernel kernel = nullptr;
-    for (const auto& e : kGat8Kernels)
-        if (e.form == p.gat8) kernel = e.kernel;
-    if (!kernel) return fail(GATOR_EINVAL, "k_gat8: no such form");
+    const Gat8Entry* e = nullptr;
+    for (const auto& k : kGat8Kernels)
+        if (k.form == p.gat8) e = &k;
+    if (!e) return fail(GATOR_EINVAL, "k_gat8: no such form");
     const int row0 = p.n_tiled, B = B_total - row0;      // this launch's samples start at row row0 of the batch
     const size_t o = (size_t)row0 * c->J;
     Gat8Args a;
@@ -1564,10 +805,10 @@ int launch_gat8(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, 
     a.gl0_W = w.gl0_W; a.gl0_b = w.gl0_b; a.gn_w = w.gn_w; a.gn_b = w.gn_b; a.gl3_p = f->g_gl3; a.gl3_b = w.gl3_b; a.posT = f->g_posT;
     a.biasT = f->g_biasT; a.m1T = f->g_m1T; a.m2T = f->g_m2T;
     a.norm_w = w.norm_w; a.norm_b = w.norm_b;
-    a.wstream = p.gat8.lb ? f->g8stream_b.get() : f->g8stream.get();      // the byte-lo stream, or the H3 stream (the one-plane form reads its hi and mid)
+    a.wstream = e->byte_lo ? f->g8stream_b.get() : f->g8stream.get();      // the byte-lo stream, or the H3 stream (the one-plane form reads its hi and mid)
     for (int i = 0; i < kDepth; ++i) {
         const GatBlockPk& b = f->gblk[i];
-        a.blk[i] = Gat8Blk{b.back, b.mc, b.mdT, b.aoffT, b.f1b, f->g_vecs + (size_t)i * 2048};
+        a.blk[i] = Gat8Blk{b.back, b.mc, b.mdT, b.aoffT, b.f1b, f->g_vecs + (size_t)i * V_TOTAL};
     }
     a.feat = ws.feat + o * kC;
     a.tl = Gat8Tail{};
@@ -1590,7 +831,7 @@ int launch_gat8(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, 
     }
     // L2 warm-up: each workgroup touches its share of the next block's weight stream
     a.pf_n = std::min(32, (B + 7) / 8);                  // workgroups b and b + 8 share an XCD (round-robin dispatch; speed only)
-    a.pf_loads = (kBlkTiles * (p.gat8.lb ? kTileH3B : kTileX3) * 4 / a.pf_n + 8191) / 8192;       // 8 KiB (64 lines) per instruction
+    a.pf_loads = (kBlkTiles * e->tile_floats * 4 / a.pf_n + 8191) / 8192;       // 8 KiB (64 lines) per instruction
     if (a.pf_loads > 6) a.pf_loads = 0;      // fewer than ~8 workgroups per XCD (B < 64): a share is so large that touching it costs more than it hides
     a.tl.warm_n = (tail && a.pf_n >= 8) ? a.pf_n : 0;      // (fewer than 8 workgroups per XCD: a share is too large to be worth touching)
     a.lin_inv = std::ldexp(1.0f, -(4 + f->gat8_wshift));
@@ -1598,7 +839,7 @@ int launch_gat8(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, 
     Gat8Diag diag;
     GATOR_TRY(gat8_diag_setup(f, tail, a, diag));
 #endif
-    kernel<<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
+    e->kernel<<<B, 512, kGat8Lds, (hipStream_t)stream>>>(a);
     GATOR_HIP_CHECK(hipGetLastError());
 #ifdef GATOR_DIAG
     GATOR_TRY(gat8_diag_report(diag, B));

@@ -12,6 +12,7 @@
 #include "fused_common.h"
 #include "fused_state.h"
 #include "x3_common.h"
+#include "joint_tokens.h"
 
 namespace gator {
 namespace {
@@ -54,20 +55,12 @@ struct JointTailArgs {
     int x2;                       // K/V tiles as two fp16 planes of 16 x value (mdr_ops.h: cross_attention_head, JointX2)
 };
 
-__device__ __forceinline__ float row_sum32x2(const f32x16& a, const f32x16& b) {
-    float s = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += a[r] + b[r];
-    return s + xhalf(s);
-}
-
 __global__ __launch_bounds__(256) void k_gat_joint(const JointTailArgs a) {
     __shared__ float XO[64];
     __shared__ __attribute__((aligned(16))) float JF[2 * kTile];
-    // every per-channel vector the joint-token part needs, fetched by one vector load per thread at the start (in flight during the
-    // lifter sums; published by the barrier that follows them).  Through the scalar cache, as before, each of the 18 vectors was an
-    // exposed round trip in the middle of the chain: 6.6 of the launch's 20 us.
-    enum { VJ_JFB = 0, VJ_JF5 = 64, VJ_N1W = 384, VJ_N1B = 576, VJ_TOTAL = 768 };      // n1w / n1b: [3 layers][64]
+    // every per-channel vector the joint-token part needs (joint_tokens.h: VJ_*), fetched by one vector load per thread at the start (in
+    // flight during the lifter sums; published by the barrier that follows them).  Through the scalar cache, as before, each of the 18
+    // vectors was an exposed round trip in the middle of the chain: 6.6 of the launch's 20 us.
     __shared__ __attribute__((aligned(16))) float VJ[VJ_TOTAL];
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, h = lane >> 5, J = a.J, tok = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -81,16 +74,11 @@ __global__ __launch_bounds__(256) void k_gat_joint(const JointTailArgs a) {
     f32x16 posj, ft[4];
     float p2x = 0.f, p2y = 0.f;
     auto job_tile = [&](int job, int i) {
-        const int li = job >> 2, kv = (job >> 1) & 1, nb = job & 1;
-        return load_wtile(kv ? a.j_wv_p[li] : a.j_wk_p[li], nb * 2 + i, lane);
+        const JointJob jb = joint_job(job);
+        return load_wtile(jb.kv ? a.j_wv_p[jb.li] : a.j_wk_p[jb.li], jb.nb * 2 + i, lane);
     };
     if (a.jkv) {
-        if (t < VJ_TOTAL / 4) {
-            const int off = 4 * t;
-            const float* src = off < VJ_JF5 ? a.jf_b + off : off < VJ_N1W ? a.jf5 + (off - VJ_JF5)
-                               : off < VJ_N1B ? a.j_n1w[(off - VJ_N1W) >> 6] + (off & 63) : a.j_n1b[(off - VJ_N1B) >> 6] + (off & 63);
-            reinterpret_cast<f32x4*>(VJ)[t] = *reinterpret_cast<const f32x4*>(src);
-        }
+        if (t < VJ_TOTAL / 4) joint_stage_vecs(a, VJ, t);
         if (wave < 2) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) jw[i] = load_wtile(a.jf_p, wave * 4 + i, lane);
@@ -139,19 +127,18 @@ __global__ __launch_bounds__(256) void k_gat_joint(const JointTailArgs a) {
     f32x16 jf[2];
     jf[0] = load_block(JF, lane);
     jf[1] = load_block(JF + kTile, lane);
-    const float mean = (row_sum32x2(jf[0], jf[1])) * (1.0f / 64.0f);
-    const f32x16 d0 = jf[0] - mean, d1 = jf[1] - mean;
-    const float rstd = 1.0f / sqrtf(row_sum32x2(d0 * d0, d1 * d1) * (1.0f / 64.0f) + 1e-5f);
+    f32x16 d0 = jf[0], d1 = jf[1];
+    const float rstd = ln_center64(d0, d1);
     // per LBF layer: k = wk(LN1(jf)), v = wv(LN1(jf)) as MFMA operand tiles; 12 jobs (layer, k|v, channel block) over the 4 waves
 #pragma unroll 1
     for (int job = wave * 3; job < wave * 3 + 3; ++job) {
-        const int li = job >> 2, kv = (job >> 1) & 1, nb = job & 1;
+        const JointJob jb = joint_job(job);
+        const int li = jb.li, kv = jb.kv, nb = jb.nb;
         const int jn = job + 1 < wave * 3 + 3 ? job + 1 : job;       // next job's weight tiles in flight during this one
         const WTile nw0 = job_tile(jn, 0), nw1 = job_tile(jn, 1);
         asm volatile("" ::: "memory");
         f32x16 fz[2];
-        fz[0] = d0 * rstd * chanvec_lds(VJ, VJ_N1W + 64 * li, h) + chanvec_lds(VJ, VJ_N1B + 64 * li, h);
-        fz[1] = d1 * rstd * chanvec_lds(VJ, VJ_N1W + 64 * li + 32, h) + chanvec_lds(VJ, VJ_N1B + 64 * li + 32, h);
+        joint_norm1(d0, d1, rstd, VJ, li, h, fz[0], fz[1]);
         float* out = a.jkv + (((size_t)b * 3 + li) * 4 + kv * 2 + nb) * kTile;
         f32x16 r0 = zero16(), r1 = zero16();
         if (kv == 0) {

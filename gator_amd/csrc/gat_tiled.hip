@@ -34,14 +34,10 @@ constexpr int kTabS = 20;              // row stride of the J x J tables (J <= 1
 constexpr int kGrpTiles = 4;           // tiles per weight group (ring slot = 4 x 6 KiB = 24 KiB, 6 pieces of 1 KiB per wave)
 constexpr int kRing = 3;               // ring slots: group k+2 is copied while group k is in use
 constexpr int kGroupsPerBlock = 66;
-constexpr float kLog2eT = 1.4426950408889634f;
-
-enum { TV_N1W = 0, TV_N1B = 128, TV_QKVB = 256, TV_PROJB = 640, TV_GCNB = 768, TV_LIN0B = 896, TV_BACKB = 1024, TV_N2W = 1152,
-       TV_N2B = 1280, TV_FC1B = 1408, TV_FC2B = 1920, TV_TOTAL = 2048 };     // order of FusedState::g_vecs (gat_fused.hip)
 
 struct TiledBlk {
     const float *qkv, *proj, *w0, *w1, *lin0, *lin1, *back, *fc1, *fc2;       // X3 tile grids [NB][KB]
-    const float *vecs, *M, *lin1_b;                                           // per-block vectors (TV_*), gcn.M [J][128], linears[1].bias [16]
+    const float *vecs, *M, *lin1_b;                                           // per-block vectors (fused_state.h: V_*), gcn.M [J][128], linears[1].bias [16]
 };
 struct TiledArgs {
     int B, S, Btap;                 // Btap: batch stride of the block-tap buffer (the whole batch of the call)
@@ -57,40 +53,21 @@ struct TiledArgs {
 // LDS carve-up (floats)
 constexpr int kRingSlot = kGrpTiles * kTileX3;
 constexpr int oRING = 0, oEXK = oRING + kRing * kRingSlot, oEXV = oEXK + kTT * kEXS, oVEC = oEXV + kTT * kEXS,
-              oBIAS = oVEC + TV_TOTAL, oAOFF = oBIAS + 8 * 19 * kTabS, oM1 = oAOFF + kDepth * 19 * kTabS, oM2 = oM1 + 19 * kTabS,
+              oBIAS = oVEC + V_TOTAL, oAOFF = oBIAS + 8 * 19 * kTabS, oM1 = oAOFF + kDepth * 19 * kTabS, oM2 = oM1 + 19 * kTabS,
               oADIAG = oM2 + 19 * kTabS, oL1B = oADIAG + kDepth * 32, oMT = oL1B + kDepth * 16, kTiledLdsFloats = oMT + 19 * kC;
 static_assert(kTiledLdsFloats * 4 <= 160 * 1024, "LDS budget");
 
-__device__ __forceinline__ f32x16 chanvec_L(const float* V, int off, int h) {      // v[r] = V[off + kap(r) + 4h]
-    f32x16 v;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(V + off + 8 * g + 4 * h);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[4 * g + j] = t[j];
-    }
-    return v;
-}
 // the 16 channels of block `cb` that lane half h holds, read from row-major [..][128] at row pointer `row` (global or LDS)
-__device__ __forceinline__ f32x16 row_block(const float* row, int cb, int h) { return chanvec_L(row, 32 * cb, h); }
+__device__ __forceinline__ f32x16 row_block(const float* row, int cb, int h) { return chanvec_lds(row, 32 * cb, h); }
 
-__device__ __forceinline__ float sum64(const f32x16 (&x)[4]) {
-    float s = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += (x[0][r] + x[1][r]) + (x[2][r] + x[3][r]);
-    return s + xhalf(s);
-}
 // nn.LayerNorm(128) of the wave's tokens, result split into operand planes
 template <bool GELU>
 __device__ __forceinline__ void ln128(const f32x16 (&x)[4], const float* V, int ow, int ob, int h, f32x16 (&y)[4]) {
-    const float mean = sum64(x) * (1.0f / 128.0f);
-    f32x16 d[4], sq[4];
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) { d[kb] = x[kb] - mean; sq[kb] = d[kb] * d[kb]; }
-    const float rstd = 1.0f / sqrtf(sum64(sq) * (1.0f / 128.0f) + 1e-5f);
+    f32x16 d[4] = {x[0], x[1], x[2], x[3]};
+    const float rstd = ln_center128(d);
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
-        y[kb] = d[kb] * rstd * chanvec_L(V, ow + 32 * kb, h) + chanvec_L(V, ob + 32 * kb, h);
+        y[kb] = d[kb] * rstd * chanvec_lds(V, ow + 32 * kb, h) + chanvec_lds(V, ob + 32 * kb, h);
         if (GELU) gelu_tile(y[kb]);
     }
 }
@@ -167,17 +144,6 @@ __device__ __forceinline__ f32x16 from_head(const float (&q)[16]) {
     return v;
 }
 
-// LDS-DMA of one 1 KiB piece (64 lanes x 16 B): global -> LDS without registers.  Issued through inline asm ON PURPOSE: hipcc
-// counts the builtin form in its vmcnt bookkeeping and, because the copy writes LDS, drains it (s_waitcnt vmcnt(0)) before the
-// next LDS access or the next copy -- measured: 0.48 of the kernel's 1.2 ms at B=1024 was that wait.  The asm form is invisible
-// to that bookkeeping; begin_group() waits for it explicitly before the barrier that publishes the slot.
-__device__ __forceinline__ void glds16(const float* gsrc, const float* lds_dst) {
-    unsigned keep;
-    const unsigned dst = (unsigned)(unsigned long long)lds_dst;             // low 32 bits of a generic LDS address = the LDS byte offset
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-}
-
 // N weight tiles of a ring slot, one product each: tile i+1 is read from LDS while tile i feeds its 12 MFMAs, and never earlier
 // (unfenced, hipcc hoists all of a group's LDS reads to its top: 5 x 24 registers on top of the 300 the state needs -> scratch).
 __device__ __forceinline__ void ld_wtile(X3& o, const float* p, int lane) { o = x3_load(p, lane); }
@@ -247,10 +213,10 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
     };
     // the block's vector table: biases that start an accumulator carry lin_s
     auto stage_vecs = [&](const float* vecs, float* Vd, int tid_) {
-        for (int e = tid_; e < TV_TOTAL / 4; e += 256) {
+        for (int e = tid_; e < V_TOTAL / 4; e += 256) {
             f32x4 v = reinterpret_cast<const f32x4*>(vecs)[e];
             const int off = 4 * e;
-            if (H4 && ((off >= TV_QKVB && off < TV_N2W) || off >= TV_FC1B)) v = v * a.lin_s;
+            if (H4 && ((off >= V_QKVB && off < V_N2W) || off >= V_FC1B)) v = v * a.lin_s;
             reinterpret_cast<f32x4*>(Vd)[e] = v;
         }
     };
@@ -283,7 +249,7 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
 #pragma unroll
             for (int p0 = 0; p0 < 2; ++p0) {
                 const int p = ((wave - 2 * i) & 3) + 4 * p0;
-                if (p < NP) glds16(tl[i] + p * 256 + lane * 4, slot + (i * 6 + p) * 256);
+                if (p < NP) glds<16>(tl[i] + p * 256 + lane * 4, slot + (i * 6 + p) * 256);
             }
     };
     auto begin_group = [&]() -> const float* {      // -> ring slot holding the group that begins now
@@ -369,7 +335,7 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
         const float* prow = a.pos + (size_t)j * kC;
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
-            f32x16 acc = chanvec_L(a.gl3_b, 32 * nb, h) + row_block(prow, nb, h), ac1 = zero16();
+            f32x16 acc = chanvec_lds(a.gl3_b, 32 * nb, h) + row_block(prow, nb, h), ac1 = zero16();
             mma2_T(load_wtile(a.gl3_p, nb * 2 + 0, lane), hb[0], acc, load_wtile(a.gl3_p, nb * 2 + 1, lane), hb[1], ac1);
             x[nb] = acc + ac1;
         }
@@ -384,17 +350,17 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
             __syncthreads();                                                 // V of this block (written behind the previous block's last barrier) is visible
             {
                 f32x16 yf[4];
-                ln128<false>(x, V, TV_N1W, TV_N1B, h, yf);
+                ln128<false>(x, V, V_N1W, V_N1B, h, yf);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ys[i] = sp(yf[i], 1.0f);
             }
             adiag = TADIAG[bi * 32 + j];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) pacc[i] = chanvec_L(V, TV_PROJB + 32 * i, h) + chanvec_L(V, TV_GCNB + 32 * i, h);
+            for (int i = 0; i < 4; ++i) pacc[i] = chanvec_lds(V, V_PROJB + 32 * i, h) + chanvec_lds(V, V_GCNB + 32 * i, h);
 #pragma unroll 1
             for (int nb = 0; nb < 4; ++nb) {
-                f32x16 q = chanvec_L(V, TV_QKVB + 32 * nb, h), k = chanvec_L(V, TV_QKVB + 128 + 32 * nb, h),
-                       v = chanvec_L(V, TV_QKVB + 256 + 32 * nb, h), h1 = zero16();
+                f32x16 q = chanvec_lds(V, V_QKVB + 32 * nb, h), k = chanvec_lds(V, V_QKVB + 128 + 32 * nb, h),
+                       v = chanvec_lds(V, V_QKVB + 256 + 32 * nb, h), h1 = zero16();
 #pragma unroll
                 for (int kb = 0; kb < 4; ++kb) {
                     const float* slot = begin_group();
@@ -430,7 +396,7 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
 #pragma unroll
                             for (int i = 0; i < 4; ++i) s = fmaf(qh[4 * g + i], kv[i], s);
                         }
-                        s = (s * (0.25f * inv * inv) + brow[jp]) * kLog2eT;  // q k^T * head_dim**-0.5 + hop/path bias (q, k carry lin_s)
+                        s = (s * (0.25f * inv * inv) + brow[jp]) * kLog2e;  // q k^T * head_dim**-0.5 + hop/path bias (q, k carry lin_s)
                         sc[jp] = s;
                         mx = fmaxf(mx, s);
                     }
@@ -480,12 +446,12 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
             for (int i = 0; i < 4; ++i) ss[i] = sp(pacc[i], inv);
             f32x16 xb[4];                                                    // linearback output; added to the residual once
 #pragma unroll
-            for (int i = 0; i < 4; ++i) xb[i] = chanvec_L(V, TV_BACKB + 32 * i, h);
+            for (int i = 0; i < 4; ++i) xb[i] = chanvec_lds(V, V_BACKB + 32 * i, h);
 #pragma unroll 1
             for (int nb = 0; nb < 4; ++nb) {
                 {   // linears[0], output block nb
                     const float* slot = begin_group();
-                    f32x16 u0 = chanvec_L(V, TV_LIN0B + 32 * nb, h);
+                    f32x16 u0 = chanvec_lds(V, V_LIN0B + 32 * nb, h);
                     for_tiles<4, WT>(slot, lane, [&](int kb, const WT& wt) { u0 = mm(wt, ss[kb], u0); });
                     ex_write(EXK, t, h, u0);
                 }
@@ -518,17 +484,17 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
             OT y2[4];
             {
                 f32x16 yf[4];
-                ln128<false>(x, V, TV_N2W, TV_N2B, h, yf);
+                ln128<false>(x, V, V_N2W, V_N2B, h, yf);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) y2[i] = sp(yf[i], 1.0f);
             }
             f32x16 xm[4];                                                    // fc2 output; added to the residual once
 #pragma unroll
-            for (int i = 0; i < 4; ++i) xm[i] = chanvec_L(V, TV_FC2B + 32 * i, h);
+            for (int i = 0; i < 4; ++i) xm[i] = chanvec_lds(V, V_FC2B + 32 * i, h);
 #pragma unroll 1
             for (int c = 0; c < 16; ++c) {
                 const float* s1 = begin_group();
-                f32x16 hd = chanvec_L(V, TV_FC1B + 32 * c, h);
+                f32x16 hd = chanvec_lds(V, V_FC1B + 32 * c, h);
                 for_tiles<4, WT>(s1, lane, [&](int kb, const WT& wt) { hd = mm(wt, y2[kb], hd); });
                 if constexpr (H4) gelu_tile_scaled(hd, inv); else gelu_tile(hd);
                 const OT hx = sp(hd, inv);
@@ -539,16 +505,8 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
             for (int i = 0; i < 4; ++i) { if constexpr (H4) x[i] = fma16(xm[i], inv, x[i]); else x[i] += xm[i]; }
         }
         if (a.blk_tap && valid) {
-            float* dst = a.blk_tap + ((size_t)bi * a.Btap * J + gtok) * kC + 4 * h;
 #pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v4;
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) v4[jj] = x[kb][4 * g + jj];
-                    *reinterpret_cast<f32x4*>(dst + 32 * kb + 8 * g) = v4;
-                }
+            for (int kb = 0; kb < 4; ++kb) store_row_block(a.blk_tap + ((size_t)bi * a.Btap * J + gtok) * kC + 32 * kb, h, x[kb]);
         }
         // next block's vectors: every read of V of this block is done once all waves pass this barrier
         if (bi + 1 < kDepth) {
@@ -559,24 +517,13 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
     }
     // ---- tail: feat = GELU(LN(x))  (GAT.py:148-150) ----
     {
-        f32x16 d[4], sq[4];
-        const float mean = sum64(x) * (1.0f / 128.0f);
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) { d[kb] = x[kb] - mean; sq[kb] = d[kb] * d[kb]; }
-        const float rstd = 1.0f / sqrtf(sum64(sq) * (1.0f / 128.0f) + 1e-5f);
+        f32x16 d[4] = {x[0], x[1], x[2], x[3]};
+        const float rstd = ln_center128(d);
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
-            f32x16 y = d[kb] * rstd * chanvec_L(a.norm_w, 32 * kb, h) + chanvec_L(a.norm_b, 32 * kb, h);
+            f32x16 y = d[kb] * rstd * chanvec_lds(a.norm_w, 32 * kb, h) + chanvec_lds(a.norm_b, 32 * kb, h);
             gelu_tile(y);
-            if (valid) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v4;
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) v4[jj] = y[4 * g + jj];
-                    *reinterpret_cast<f32x4*>(a.feat + gtok * kC + 32 * kb + 8 * g + 4 * h) = v4;
-                }
-            }
+            if (valid) store_row_block(a.feat + gtok * kC + 32 * kb, h, y);
         }
     }
 }
@@ -615,7 +562,7 @@ int launch_gat_tiled(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan
         auto sel = [&](const float* t) { return image + (size_t)(t - f->gblk[0].qkv) / kTile * kTileX3; };
         q.qkv = sel(b.qkv); q.proj = sel(b.proj); q.w0 = sel(b.w0); q.w1 = sel(b.w1); q.lin0 = sel(b.lin0); q.lin1 = sel(b.lin1);
         q.back = sel(b.back); q.fc1 = sel(b.fc1); q.fc2 = sel(b.fc2);
-        q.vecs = f->g_vecs + (size_t)i * 2048;
+        q.vecs = f->g_vecs + (size_t)i * V_TOTAL;
         q.M = w.blk[i].gcn_M;
         q.lin1_b = w.blk[i].xl1_b;
     }

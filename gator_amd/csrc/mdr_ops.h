@@ -17,23 +17,13 @@
 namespace gator {
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
 
 // ---- row-wise helpers over the 64 channels (2 blocks) of a token (lane pair l, l^32) -------------------------------
-__device__ __forceinline__ float row_sum64(const f32x16& a, const f32x16& b) {
-    float s = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += a[r] + b[r];
-    return s + xhalf(s);
-}
-
 // nn.LayerNorm(64), eps inside the sqrt
 __device__ __forceinline__ void layernorm64(const f32x16 (&x)[2], const float* __restrict__ w, const float* __restrict__ b,
                                             int h, f32x16 (&y)[2]) {
-    const float mean = row_sum64(x[0], x[1]) * (1.0f / 64.0f);
-    f32x16 d0 = x[0] - mean, d1 = x[1] - mean;
-    const float var = row_sum64(d0 * d0, d1 * d1) * (1.0f / 64.0f);
-    const float rstd = 1.0f / sqrtf(var + 1e-5f);
+    f32x16 d0 = x[0], d1 = x[1];
+    const float rstd = ln_center64(d0, d1);
     y[0] = d0 * rstd * load_chanvec_S(w, 0, h) + load_chanvec_S(b, 0, h);
     y[1] = d1 * rstd * load_chanvec_S(w, 32, h) + load_chanvec_S(b, 32, h);
 }
@@ -52,7 +42,7 @@ __device__ __forceinline__ float row_sumsq64(const f32x16& a, const f32x16& b) {
 // nn.LayerNorm(64) with the affine part as one FMA per value: (d * rstd) * w + b.  w and b come from the workgroup's LDS table; when
 // the result only feeds 4-product linears the table holds 16 w and 16 b (mdr_stage_vectors), so the result IS the operand scale.
 __device__ __forceinline__ void layernorm64_L(const f32x16 (&x)[2], const float* w, const float* b, int h, f32x16 (&y)[2]) {
-    const float mean = row_sum64(x[0], x[1]) * (1.0f / 64.0f);
+    const float mean = row_sum(x[0], x[1]) * (1.0f / 64.0f);
     f32x16 d0 = x[0] - mean, d1 = x[1] - mean;
     const float var = row_sumsq64(d0, d1) * (1.0f / 64.0f);
     const float rstd = 1.0f / sqrtf(var + 1e-5f);
@@ -60,7 +50,7 @@ __device__ __forceinline__ void layernorm64_L(const f32x16 (&x)[2], const float*
     y[1] = __builtin_elementwise_fma(d1 * rstd, chanvec_lds(w, 32, h), chanvec_lds(b, 32, h));
 }
 __device__ __forceinline__ void custom_ln64_L(f32x16 (&x)[2], const float* a2, const float* b2, int h) {
-    const float mean = row_sum64(x[0], x[1]) * (1.0f / 64.0f);
+    const float mean = row_sum(x[0], x[1]) * (1.0f / 64.0f);
     f32x16 d0 = x[0] - mean, d1 = x[1] - mean;
     const float std = sqrtf(row_sumsq64(d0, d1) * (1.0f / 63.0f));
     const float inv = 1.0f / (std + 1e-6f);
@@ -70,9 +60,9 @@ __device__ __forceinline__ void custom_ln64_L(f32x16 (&x)[2], const float* a2, c
 
 // Annotated-Transformer LayerNorm: a_2 * (x - mean) / (std_unbiased + 1e-6) + b_2
 __device__ __forceinline__ void custom_ln64(f32x16 (&x)[2], const float* __restrict__ a2, const float* __restrict__ b2, int h) {
-    const float mean = row_sum64(x[0], x[1]) * (1.0f / 64.0f);
+    const float mean = row_sum(x[0], x[1]) * (1.0f / 64.0f);
     f32x16 d0 = x[0] - mean, d1 = x[1] - mean;
-    const float std = sqrtf(row_sum64(d0 * d0, d1 * d1) * (1.0f / 63.0f));
+    const float std = sqrtf(row_sum(d0 * d0, d1 * d1) * (1.0f / 63.0f));
     const float inv = 1.0f / (std + 1e-6f);
     x[0] = load_chanvec_S(a2, 0, h) * d0 * inv + load_chanvec_S(b2, 0, h);
     x[1] = load_chanvec_S(a2, 32, h) * d1 * inv + load_chanvec_S(b2, 32, h);

@@ -4,7 +4,8 @@ as a test: per-sample kernel and sample-tiled kernel, persistent and four-launch
 A change that is meant to move bits re-records the file (and re-runs the error budget); any other change must leave it green.
 tests/golden/mdr_form_digests.json does the same for the MDR kernels' other forms (tools/ab_digest.py: form_digests): exact split, fp32-input
 MFMA, config 3 and the whole-head kernels, four-launch and persistent, at B = 11.
-tests/golden/caller_side_digests.json does it for the kernels around the forward (tools/ab_digest.py: caller_digests)."""
+tests/golden/caller_side_digests.json does it for the kernels around the forward (tools/ab_digest.py: caller_digests).
+tests/golden/encoder_form_digests.json does it for every form of the GAT encoder kernels (tools/ab_digest.py: encoder_digests)."""
 import json
 import os
 
@@ -26,6 +27,9 @@ def test_fp32_forward_digests_match_the_recorded_build():
     got = digests()
     bad = {k: (got.get(k), h) for k, h in want.items() if got.get(k) != h}
     assert not bad, 'outputs moved bits against tests/golden/fp32_digests.json: %s' % bad
+ENCODER_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'encoder_form_digests.json')
+ENCODER_FORMS = ['default', 'tail0', 'lobyte0', 'h4_0', 'gat8_0', 'x3_0', 'bf16', 'bf16_tail0', 'tiled', 'tiled_h4_0', 'tiled_bf16', 'gat', 'gat_x3_0',
+                 'taps', 'tiled_taps']
 
 
 @pytest.mark.parametrize('form', ['default', 'x3_1', 'x3_0', 'bf16', 'head_partials0'])
@@ -44,6 +48,23 @@ def test_mdr_form_digests_match_the_recorded_build(form):
     assert not bad, 'outputs moved bits against tests/golden/mdr_form_digests.json: %s' % bad
 
 
+@pytest.mark.parametrize('form', ENCODER_FORMS)
+def test_encoder_form_digests_match_the_recorded_build(form):
+    """Every form of the GAT encoder bit for bit against the build recorded before its kernels' shared steps were stated once: the eight
+    per-sample forms at B = 3 and 65 (all eleven k_gat8 instantiations, k_gat<true|false, false>, both L2 warm-ups and the tail warm-up),
+    the three sample-tiled forms at B = 8, the stand-alone encoder entry (k_gat<., true>) and the block taps of both encoders; both golden
+    variants (tools/ab_digest.py: encoder_digests)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tools.ab_digest import ENCODER_FORMS as forms, encoder_digests
+    assert sorted(forms) == sorted(ENCODER_FORMS)
+    want = {k: h for k, h in json.load(open(ENCODER_PATH))['digests'].items() if k.startswith(form + ' ')}
+    got = encoder_digests([form])
+    assert len(want) >= 2 and set(got) == set(want)
+    bad = {k: (got.get(k), h) for k, h in want.items() if got.get(k) != h}
+    assert not bad, 'outputs moved bits against tests/golden/encoder_form_digests.json: %s' % bad
+
+
 def test_caller_side_digests_match_the_recorded_build():
     """The kernels around the forward (preprocess, camera crop, Procrustes / joint / mesh / sequence errors, camera targets) bit for bit
     against the build that was recorded before their shared steps moved into csrc/joints2d.h and csrc/procrustes.h: small seeded shapes
@@ -60,7 +81,7 @@ def test_caller_side_digests_match_the_recorded_build():
 
 
 def test_byte_lo_weight_stream_equals_the_three_plane_stream_bit_for_bit(monkeypatch):
-    """k_gat8 streams its weights with the lo plane as one byte per weight by default (gat_roles.hip: H3B); GATOR_GAT8_LOBYTE=0 keeps
+    """k_gat8 streams its weights with the lo plane as one byte per weight by default (gat8_forms.h: H3B); GATOR_GAT8_LOBYTE=0 keeps
     the three fp16 planes.  The switch is read per context, so both forms run in this process; the digests (which cover B = 5 / 256 / 700
     on k_gat8) must be equal.  (Which kernel ran is visible in profiles/r05_kernel_stats_*: k_gat8<true, 10, false, true>.)"""
     import sys

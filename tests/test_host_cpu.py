@@ -89,11 +89,12 @@ def test_bad_configuration_is_rejected():
 def test_gat8_roles_keep_the_same_barrier_sequence():
     """csrc/gat_roles.hip: the product waves and the helper waves of k_gat8 run disjoint branches of one kernel that meet at
     numbered workgroup barriers; a barrier that only one role executes would hang the GPU.  Both branches must name exactly the
-    sequence 0, 1 .. 22, each number once and in order."""
+    sequence 0, 1 .. 22, each number once and in order.  (The epilogue both roles end in is csrc/gat8_tail.h.)"""
     import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gator_amd', 'csrc', 'gat_roles.hip')).read()
-    body = src[src.index('void k_gat8('):src.index('__global__ void k_gather_tiles')]
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gator_amd', 'csrc')
+    src = open(os.path.join(csrc, 'gat_roles.hip')).read()
+    body = src[src.index('void k_gat8('):src.index('// The eleven forms of k_gat8')]
     body = re.sub(r'#ifdef GATOR_DIAG.*?#endif', '', body, flags=re.S)       # (the diagnostic library's stamps / experiments)
     head, rest = body.split('product waves ====', 1)
     product, helper = rest.split('helper waves ====', 1)
@@ -108,6 +109,7 @@ def test_gat8_roles_keep_the_same_barrier_sequence():
     for role, text in (('product', product), ('helper', helper)):
         assert len(re.findall(r'gat8_tail<', text)) == 1, role
         assert text.rindex('gat8_tail<') > text.rindex('GAT8_BAR(22)'), role
-    tail = src[src.index('void gat8_tail('):src.index('// H4: the token-wise products on four partial products')]
+    tail_src = open(os.path.join(csrc, 'gat8_tail.h')).read()
+    tail = tail_src[tail_src.index('void gat8_tail('):]
     assert tail.count('__syncthreads()') == 1 and 'GAT8_BAR' not in tail
     assert tail.index('if (!joint) return;') < tail.index('__syncthreads()')      # the lifter-only exit is workgroup-uniform and ahead of the barrier

@@ -8,7 +8,9 @@
     and whole-head kernels at B = 11, which the fp32 digests above never reach.
   * `--caller --write tests/golden/caller_side_digests.json` does the same for caller_digests(): the kernels around the forward
     (preprocess, camera crop, Procrustes / joint / mesh / sequence errors, camera targets) on small seeded shapes.
-python tools/ab_digest.py [tag] [--forms | --caller] [--write path [--commit hash-of-the-recorded-build]]"""
+  * `--encoder --write tests/golden/encoder_form_digests.json` does the same for encoder_digests(): every form of the GAT encoder kernels
+    (k_gat8, k_gat, k_gat_tiled, the tail launches, the stand-alone encoder entry, the block taps) at batches the fp32 digests never reach.
+python tools/ab_digest.py [tag] [--forms | --caller | --encoder] [--write path [--commit hash-of-the-recorded-build]]"""
 import contextlib, hashlib, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -46,10 +48,10 @@ FORM_B_ROLLED = 513     # k_mdr_head<512, false> (the rolled whole head) is plan
 
 
 @contextlib.contextmanager
-def _switches(env):
-    old = {k: os.environ.get(k) for k in FORM_SWITCHES}
+def _switches(env, names=FORM_SWITCHES):
+    old = {k: os.environ.get(k) for k in names}
     try:
-        for k in FORM_SWITCHES:
+        for k in names:
             os.environ.pop(k, None)
         os.environ.update(env)
         yield
@@ -92,6 +94,67 @@ def form_digests(forms=None):
                     assert bool(torch.isfinite(v).all()) and bool(torch.isfinite(w).all())
                     key = '%s persist=%s %s B=%d ' % (form, persist, name, B)
                     out[key + 'forward'], out[key + 'pose2mesh'] = _sha(v, p), _sha(w)
+    return out
+
+
+# The GAT encoder's forms (gat_roles.hip + gat8_*.h / gat_fused.hip / gat_tiled.hip / gat_tail.hip).  name: (entry, environment, precision, batches, taps)
+#   entry 'sample': the whole forward with the per-sample encoder pinned.  B = 3, and B = 65 = nine workgroups per XCD group, where both L2
+#       warm-ups and the tail warm-up are on (below 64 they are off).  With the two variants (LR 10 / 12) the eight forms reach all eleven
+#       k_gat8 instantiations and k_gat<true|false, false>.
+#   entry 'tiled': the whole forward with the sample-tiled encoder pinned, B = 8: two workgroups, the second with one sample (J = 17) or two (J = 19).
+#   entry 'gat': the stand-alone encoder (models/GAT.py -> gator_gat_forward_f32, k_gat<., true>): digest of pose3d + feat.
+#   taps: a second forward with enable_block_taps(True); the six block taps join the digest.
+ENCODER_FORMS = {
+    'default': ('sample', {}, 'f32', (3, 65), False),
+    'tail0': ('sample', {'GATOR_GAT8_TAIL': '0'}, 'f32', (3, 65), False),
+    'lobyte0': ('sample', {'GATOR_GAT8_LOBYTE': '0'}, 'f32', (3, 65), False),
+    'h4_0': ('sample', {'GATOR_GAT8_H4': '0'}, 'f32', (3, 65), False),
+    'gat8_0': ('sample', {'GATOR_GAT8': '0'}, 'f32', (3, 65), False),
+    'x3_0': ('sample', {'GATOR_GAT_X3': '0'}, 'f32', (3, 65), False),
+    'bf16': ('sample', {}, 'bf16', (3, 65), False),
+    'bf16_tail0': ('sample', {'GATOR_GAT8_TAIL': '0'}, 'bf16', (3, 65), False),
+    'tiled': ('tiled', {}, 'f32', (8,), False),
+    'tiled_h4_0': ('tiled', {'GATOR_GAT_TILED_H4': '0'}, 'f32', (8,), False),
+    'tiled_bf16': ('tiled', {}, 'bf16', (8,), False),
+    'gat': ('gat', {}, 'f32', (3,), False),
+    'gat_x3_0': ('gat', {'GATOR_GAT_X3': '0'}, 'f32', (3,), False),
+    'taps': ('sample', {}, 'f32', (3,), True),
+    'tiled_taps': ('tiled', {}, 'f32', (8,), True),
+}
+ENCODER_SWITCHES = ('GATOR_GAT_X3', 'GATOR_GAT8', 'GATOR_GAT8_H4', 'GATOR_GAT8_LOBYTE', 'GATOR_GAT8_TAIL', 'GATOR_GAT8_DBG', 'GATOR_GAT_TILED',
+                    'GATOR_GAT_TILED_H4', 'GATOR_GAT_TILED_MIN_BATCH', 'GATOR_C3_ENCODER')
+
+
+def encoder_digests(forms=None):
+    """{'<form> <variant> B=<B>': digest} of (vertices, pose3d[, gat_block0..5]), or of (pose3d, feat) for the stand-alone encoder entry.
+    The switches are read when a context is created, so every case drops the models' contexts first."""
+    out = {}
+    models = {name: build_model(name, 'fused')[1] for name, _ in VARIANTS}
+    for form in (forms or ENCODER_FORMS):
+        entry, env, precision, batches, taps = ENCODER_FORMS[form]
+        for name, J in VARIANTS:
+            for B in batches:
+                m = models[name]
+                x = torch.from_numpy(synthetic.synthetic_pose2d(B, J, seed=B)).cuda()
+                with _switches(env, ENCODER_SWITCHES):
+                    m.invalidate()
+                    m.pose_lifter.invalidate()
+                    if entry == 'gat':
+                        got = list(m.pose_lifter(x.reshape(B, 2 * J)))
+                    else:
+                        m.precision = precision
+                        m.set_encoder(entry)
+                        got = list(m(x))
+                        if taps:
+                            m.enable_block_taps(True)
+                            got = list(m(x)) + [m.get_tap('gat_block%d' % i, (B, J, 128)).clone() for i in range(6)]
+                        m.set_encoder('auto')
+                        m.precision = 'f32'
+                    torch.cuda.synchronize()
+                    m.invalidate()
+                    m.pose_lifter.invalidate()
+                assert all(bool(torch.isfinite(t).all()) for t in got)
+                out['%s %s B=%d' % (form, name, B)] = _sha(*got)
     return out
 
 
@@ -267,6 +330,8 @@ def main():
         return main_forms()
     if '--caller' in sys.argv:
         return main_caller()
+    if '--encoder' in sys.argv:
+        return main_encoder()
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
     write = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
     if write in args:
@@ -291,6 +356,20 @@ def main_forms():
         what = ('sha256[:32] per MDR form (tools/ab_digest.py: form_digests), gfx950, golden weights: forward = (vertices, pose3d) bytes on '
                 'synthetic_pose2d(B, J, seed=B); pose2mesh = vertices of the MDR entry point on randn(B, J, 133) seeded with B.  Recorded with '
                 'the library of commit %s' % commit)
+        with open(write, 'w') as f:
+            json.dump({'what': what, 'digests': d}, f, indent=1)
+
+
+def main_encoder():
+    write = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
+    d = encoder_digests()
+    for k, h in d.items():
+        print('%-40s %s' % (k, h), flush=True)
+    if write:
+        commit = sys.argv[sys.argv.index('--commit') + 1] if '--commit' in sys.argv else 'unknown'
+        what = ('sha256[:32] per GAT encoder form (tools/ab_digest.py: encoder_digests), gfx950, golden weights, inputs synthetic_pose2d(B, J, '
+                'seed=B): (vertices, pose3d) bytes of the forward, with the six block taps where the form records them; (pose3d, feat) of the '
+                'stand-alone encoder entry.  Recorded with the library of commit %s' % commit)
         with open(write, 'w') as f:
             json.dump({'what': what, 'digests': d}, f, indent=1)
 
