@@ -45,7 +45,7 @@ struct FusedOptions {
                                         // Needs gat8 and both encoders' four-product forms; cleared by the guard
     bool c3_up_w1 = true;               // GATOR_C3_UPSAMPLE_W1 (default 1): the vertex regressor's weights on ONE fp16 plane, coarse vertices on two; =0: weights on two
     bool c3_up_bf16 = false;            // GATOR_C3_UPSAMPLE_BF16 (default 0): the vertex regressor on one bf16 plane instead of its two fp16 planes.  Set unless up_x3 = 2
-    bool c3_guard = true;               // GATOR_C3_GUARD (default 1): clear c3_mdr and c3_encoder if the weights bound the attention logits above 2^10 (fused_create); =0: never
+    bool c3_guard = true;               // GATOR_C3_GUARD (default 1): clear c3_mdr and c3_encoder if the weights bound the logits of any of the three attentions above 2^10 (fused_create); =0: never
     // forward
     bool graph = false;                 // GATOR_GRAPH (default 0): =1 starts the ctx with hipGraph replay of repeated forwards on (gator_set_graph_replay)
     int subbatch_streams = 0;           // GATOR_SUBBATCH_STREAMS: 2 runs batches >= 128 as two half-batches on two streams, if gator_config.subbatch_streams is 0 (fused_forward)

@@ -147,39 +147,70 @@ static double sym_eig_max(std::vector<double>& A, int n) {
     return m;
 }
 
+// sigma_max of rows [r0, r0 + n) of a row-major [.][K] matrix: the root of the largest eigenvalue of the n x n Gram matrix, in double (exact,
+// no start vector).  n <= 32
+static double sigma_max_rows(const std::vector<float>& W, int r0, int n, int K) {
+    std::vector<double> G((size_t)n * n);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double acc = 0;
+            for (int k = 0; k < K; ++k) acc += (double)W[(size_t)(r0 + i) * K + k] * (double)W[(size_t)(r0 + j) * K + k];
+            G[i * n + j] = acc;
+        }
+    return std::sqrt(std::max(sym_eig_max(G, n), 0.0));
+}
+static double norm_rows(const std::vector<float>& v, int r0, int n) {
+    double s = 0;
+    for (int i = 0; i < n; ++i) s += (double)v[r0 + i] * v[r0 + i];
+    return std::sqrt(s);
+}
+static double max_abs(const std::vector<float>& v) {
+    double m = 0;
+    for (float x : v) m = std::max(m, (double)std::fabs(x));
+    return m;
+}
+
 // Guard of config 3's 16-bit mode (round 6): its 431 x 431 attention carries q and k on ONE fp16 plane each, which moves a
 // score by up to 2^-11 |q| |k|.  |q| |k| is bounded from the weights alone: the custom LayerNorm in front of the in-projections gives
 // every token unit unbiased standard deviation, |x| <= max|a_2| sqrt(63) + |b_2| (vanilla_transformer_encoder.py:31-34), and per head
 // |q_h| <= sigma_max(Wq_h) |x| + |bq_h|, |k_h| likewise, so |q_h . k_h| / sqrt(d_k) <= (sigma_max(Wq_h) |x| + |bq_h|) (sigma_max(Wk_h) |x| +
-// |bk_h|) / sqrt(d_k).  sigma_max is exact: the largest eigenvalue of the 32 x 32 Gram matrix W_h W_h^T, in double.  Returns the largest
-// bound over layers and heads, in the exp2 domain; gator_c3_state() reports it.
-float c3_logit_bound(const Weights& w) {
+// |bk_h|) / sqrt(d_k).  sigma_max is exact: the largest eigenvalue of the 32 x 32 Gram matrix W_h W_h^T, in double.
+// The other two attentions of the mode carry one-plane operands as well and get the same construction (tests/test_gpu_softmax_edges.py:
+// sharp cross-attention cost 2.2 mm in the mode, sharp encoder attention 1.3 mm, with the self-attention's bound at 75):
+//   cross-attention (JointX1): q and k come from nn.LayerNorm(64) without biases (MDR.py:27-28), |x| <= max|norm1.weight| sqrt(64) + |norm1.bias|,
+//     bound sigma_max(Wq_h) sigma_max(Wk_h) |x|^2 / sqrt(32);
+//   encoder (its token-wise products on one activation plane): nn.LayerNorm(128) in front of qkv, |x| <= max|norm1.weight| sqrt(128) + |norm1.bias|,
+//     heads of 16 rows, bound (sigma_max(Wq_h) |x| + |bq_h|) (sigma_max(Wk_h) |x| + |bk_h|) / sqrt(16) + max|hop / path bias|.
+// Returns the largest bound over the three sites, layers / blocks and heads, in the exp2 domain; gator_c3_state() reports it.  hop_bias: the
+// ctx's folded [8][J][J] tile, or nullptr for a ctx without the encoder.
+float c3_logit_bound(const Weights& w, const float* hop_bias, int J) {
     double worst = 0;
     for (int li = 0; li < 3; ++li) {
         const MdrLayerW& r = w.lay[li];
         const std::vector<float> wq = d2h(r.sa_w[0], 64 * 64), wk = d2h(r.sa_w[1], 64 * 64), bq = d2h(r.sa_b[0], 64), bk = d2h(r.sa_b[1], 64),
                                  a2 = d2h(r.a2, 64), b2 = d2h(r.b2, 64);
-        double amax = 0, bn = 0;
-        for (int i = 0; i < 64; ++i) { amax = std::max(amax, (double)std::fabs(a2[i])); bn += (double)b2[i] * b2[i]; }
-        const double xn = amax * std::sqrt(63.0) + std::sqrt(bn);
+        const double xn = max_abs(a2) * std::sqrt(63.0) + norm_rows(b2, 0, 64);
         // |W_h x + b_h| <= sigma_max(W_h) |x| + |b_h| for head hd's 32 rows of an in-projection
-        auto head_norm = [&](const std::vector<float>& W, const std::vector<float>& bias, int hd) {
-            std::vector<double> G(32 * 32);
-            double bb = 0;
-            for (int i = 0; i < 32; ++i) {
-                bb += (double)bias[32 * hd + i] * bias[32 * hd + i];
-                for (int j = 0; j < 32; ++j) {
-                    double acc = 0;
-                    for (int k = 0; k < 64; ++k) acc += (double)W[(32 * hd + i) * 64 + k] * (double)W[(32 * hd + j) * 64 + k];
-                    G[i * 32 + j] = acc;
-                }
-            }
-            return std::sqrt(std::max(sym_eig_max(G, 32), 0.0)) * xn + std::sqrt(bb);
-        };
         for (int hd = 0; hd < 2; ++hd)
-            worst = std::max(worst, head_norm(wq, bq, hd) * head_norm(wk, bk, hd) / std::sqrt(32.0) * 1.4426950408889634);
+            worst = std::max(worst, (sigma_max_rows(wq, 32 * hd, 32, 64) * xn + norm_rows(bq, 32 * hd, 32)) *
+                                        (sigma_max_rows(wk, 32 * hd, 32, 64) * xn + norm_rows(bk, 32 * hd, 32)) / std::sqrt(32.0));
+        const std::vector<float> cq = d2h(r.wq, 64 * 64), ck = d2h(r.wk, 64 * 64), n1w = d2h(r.n1w, 64), n1b = d2h(r.n1b, 64);
+        const double cn = max_abs(n1w) * std::sqrt(64.0) + norm_rows(n1b, 0, 64);
+        for (int hd = 0; hd < 2; ++hd)
+            worst = std::max(worst, sigma_max_rows(cq, 32 * hd, 32, 64) * cn * sigma_max_rows(ck, 32 * hd, 32, 64) * cn / std::sqrt(32.0));
     }
-    return (float)worst;
+    if (hop_bias != nullptr) {
+        const double hop = max_abs(d2h(hop_bias, (size_t)kH * J * J));
+        for (int i = 0; i < kDepth; ++i) {
+            const GatBlockW& r = w.blk[i];
+            const std::vector<float> qkv = d2h(r.qkv_w, 384 * 128), qb = d2h(r.qkv_b, 384), n1w = d2h(r.n1w, 128), n1b = d2h(r.n1b, 128);
+            const double xn = max_abs(n1w) * std::sqrt(128.0) + norm_rows(n1b, 0, 128);
+            for (int hd = 0; hd < kH; ++hd)
+                worst = std::max(worst, (sigma_max_rows(qkv, 16 * hd, 16, 128) * xn + norm_rows(qb, 16 * hd, 16)) *
+                                            (sigma_max_rows(qkv, 128 + 16 * hd, 16, 128) * xn + norm_rows(qb, 128 + 16 * hd, 16)) / std::sqrt(16.0) + hop);
+        }
+    }
+    return (float)(worst * 1.4426950408889634);
 }
 
 // Packs each linear into the tiles at p, one after the other, and stores where it went.
@@ -282,6 +313,15 @@ int fused_create_gat(gator_ctx* c, FusedState* f, void* stream) {
                 const std::vector<float> h = d2h(pt.p, pt.n);
                 std::copy(h.begin(), h.end(), vv.begin() + (size_t)i * V_TOTAL + pt.at);
             }
+            // K's bias adds q_i . b_k to every logit of query row i: constant over the keys, so the softmax - the only reader of K - does not
+            // see it and no loss keeps it small; as the start value of the K projection's accumulator a large one rounds every partial product
+            // at ITS magnitude (at |b_k| ~ 170: 2.5 x the fp32 reference's error in k_gat / k_gat_tiled, tests/test_gpu_softmax_edges.py).  Each
+            // channel loses the multiple of 8 nearest to it: 0 for |b_k| < 4, so an ordinary checkpoint is packed as it is; exact in fp32.
+            for (int ch = 0; ch < 128; ++ch) {
+                float& bk = vv[(size_t)i * V_TOTAL + V_QKVB + 128 + ch];
+                const float shift = 8.0f * std::nearbyint(bk / 8.0f);
+                if (std::isfinite(shift)) bk -= shift;
+            }
         }
         f->g_vecs = upload(vv);
     }
@@ -331,7 +371,7 @@ int fused_create(gator_ctx* c, void* stream) {
         // keep the fp32 configuration's two planes for this ctx (measured: bound 470 -> 0.63 mm max, 3 340 -> 7.6 mm; tests/test_gpu_bf16.py).
         // (the encoder leaves the mode with them: under such weights the MDR layers amplify the 11-bit rounding of its activations too -
         // measured at bound 3 449: 5.1 mm max in the mode, 1.9 with the MDR layers on two planes, and the figure of the test with both out)
-        f->c3_logit_bound = c3_logit_bound(w);
+        f->c3_logit_bound = c3_logit_bound(w, (c->parts & GATOR_PART_GAT) ? c->hop_bias : nullptr, c->J);
         if (f->opt.c3_guard && !(f->c3_logit_bound <= 1024.0f)) f->opt.c3_mdr = f->opt.c3_encoder = false;
     }
     const size_t n_up = f->opt.up_x3 == 0 ? (size_t)3 * kOB * kCB * kTile : 0, n_layer = (size_t)64 * kTile;
@@ -375,6 +415,17 @@ int fused_create(gator_ctx* c, void* stream) {
         for (int r = 0; r < 3; ++r) {
             std::copy(bw.begin() + r * 64, bw.begin() + (r + 1) * 64, hw.begin() + (24 + r) * 64); hb[24 + r] = bb[r];
             std::copy(mw.begin() + (20 + r) * 64, mw.begin() + (21 + r) * 64, hw.begin() + (28 + r) * 64); hb[28 + r] = mb[20 + r];
+        }
+        {   // mat_A feeds nothing but the softmax over its 20 columns (MDR.py:161-166), which a shift common to all 20 biases does not change - so
+            // no loss keeps that shift small, and as the start value of the head linear's accumulator it would round every partial product at
+            // ITS magnitude (at +-100: 2.7 x the fp32 reference's error, tests/test_gpu_softmax_edges.py).  The multiple of 8 nearest to the
+            // biases' mean is taken out here: 0 for |mean| < 4, so an ordinary checkpoint is packed as it is; the subtraction is exact in fp32
+            // (both sides are multiples of the larger one's ulp and the result is small) unless the 20 biases themselves span more than 2^20 ulps.
+            double mean = 0;
+            for (int r = 0; r < 20; ++r) mean += mb[r];
+            const float shift = 8.0f * std::nearbyint((float)(mean / 20.0) / 8.0f);
+            if (std::isfinite(shift))
+                for (int r = 0; r < 20; ++r) hb[r] = mb[r] - shift;
         }
         if (c->alpha) {
             const std::vector<float> sw = d2h(w.scale_w, 64), sb = d2h(w.scale_b, 1);

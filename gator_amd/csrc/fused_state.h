@@ -73,7 +73,7 @@ struct FusedState {
     // tile ratio of each set that was looked at (0: not looked at), and which default forms this ctx gave up for the exact ones
     float h3_tile_ratio[4] = {0.f, 0.f, 0.f, 0.f};      // [GATOR_H3SET_*]
     int h3_demoted = 0;                 // bit GATOR_H3SET_*: that set's four-product form was demoted (gat8_h4 / gat_tiled_h4 off, mdr_x3 2 -> 1, fused tail off)
-    float c3_logit_bound = 0.f;         // bound on |q . k| / sqrt(d_k) of the MDR self-attention in the exp2 domain, from the weights (fused_create)
+    float c3_logit_bound = 0.f;         // bound on the logits of the mode's one-plane attentions (MDR self- and cross-attention, encoder) in the exp2 domain, from the weights (fused_create)
     DevBuf<void> up_w2;                 // fp16 [ob/2][28][2][tap 3][plane 2][64][8]  scaled hi/lo split of upsample_conv.weight
     float up_w2_unscale = 1.f;          // 2^-(weight shift + activation shift), applied to the finished sums
     DevBuf<void> up_w16;                // bf16 [tap][ob][28][64][8] (packed on the first bf16 call, which waits for the pack)

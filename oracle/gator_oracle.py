@@ -122,6 +122,8 @@ def gat_forward(sd, c, pose2d, dtype=torch.float32, taps=None, p='pose_lifter.',
         q, k, v = qkv[0], qkv[1], qkv[2]
         att = (q @ k.transpose(-2, -1)) * ((C // H) ** -0.5)
         att = att + bias.expand(B, -1, -1, -1)
+        if taps is not None:
+            taps['enc_logits%d' % i] = att                                                  # [B,H,J,J] in front of the softmax
         att = att.softmax(dim=-1)
         if drop is not None:
             att = drop(p + b + 'attn.attn_drop', att, rates.gat_attn)                       # modules.py:133
@@ -204,7 +206,10 @@ def mdr_forward(sd, c, pc, dtype=torch.float32, taps=None, p='pose2mesh.', train
         q = F.linear(fz[:, :V], g(e + 'attn.wq.weight')).reshape(B, V, Hh, d).permute(0, 2, 1, 3)
         k = F.linear(fz[:, V:], g(e + 'attn.wk.weight')).reshape(B, J, Hh, d).permute(0, 2, 1, 3)
         v = F.linear(fz[:, V:], g(e + 'attn.wv.weight')).reshape(B, J, Hh, d).permute(0, 2, 1, 3)
-        att = ((q @ k.transpose(-2, -1)) * (d ** -0.5)).softmax(dim=-1)
+        att = (q @ k.transpose(-2, -1)) * (d ** -0.5)
+        if taps is not None:
+            taps['cross_logits%d' % li] = att                                               # [B,2,431,J] in front of the softmax
+        att = att.softmax(dim=-1)
         if drop is not None:
             att = drop(p + e + 'attn.attn_drop', att, rates.mdr_attn)                       # MDR.py:42
         o = (att @ v).transpose(1, 2).reshape(B, V, E)
@@ -228,6 +233,8 @@ def mdr_forward(sd, c, pc, dtype=torch.float32, taps=None, p='pose2mesh.', train
         qq, kk, vv = [F.linear(vf, g(sa + '%d.weight' % n), g(sa + '%d.bias' % n)).view(B, -1, Hh, d).transpose(1, 2)
                       for n in range(3)]
         sc = torch.matmul(qq, kk.transpose(-2, -1)) / math.sqrt(d)
+        if taps is not None:
+            taps['self_logits%d' % li] = sc                                                 # [B,2,431,431] in front of the softmax
         pa = F.softmax(sc, dim=-1)
         if KEEP_ATTENTION_MAPS:
             _ATTN_KEPT[li] = pa
@@ -242,6 +249,8 @@ def mdr_forward(sd, c, pc, dtype=torch.float32, taps=None, p='pose2mesh.', train
             taps['mdr_lbf%d' % li] = vf
     ac = F.linear(vf, g('motion_linear.weight'), g('motion_linear.bias'))
     mat_a, mat_c = ac[:, :, :20], ac[:, :, -3:]
+    if taps is not None:
+        taps['head_logits'] = mat_a                                                     # [B,431,20] in front of mat_a.softmax
     mat_b = F.linear(vf, g('bias_linear.weight'), g('bias_linear.bias'))
     if c.alpha:
         mat_b = F.layer_norm(mat_b, (3,), g('bias_norm.weight'), g('bias_norm.bias'), 1e-5)

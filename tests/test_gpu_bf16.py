@@ -153,7 +153,8 @@ def test_config3_attention_long_way_under_large_logits(gain, monkeypatch):
 def test_config3_guard_keeps_two_planes_under_sharp_attention(gain, one_plane):
     """Round 6: gator_create bounds the self-attention logits from the weights ((sigma_max(Wq_h) |x| + |bq_h|)(sigma_max(Wk_h) |x| + |bk_h|)
     with the custom LayerNorm's bound on |x|); above 2^10 in the exp2 domain the MDR layers of gator_forward_bf16 keep two planes for that ctx.  The shipped
-    synthetic weights (bound ~75) and the logits-x-9 weights (~670, measured 0.63 mm) stay in the mode; logits x 64 (~4 800, measured 7.6 mm in the mode)
+    synthetic weights (self-attention bound ~75; the reported bound is the largest of the three attentions', here the encoder's ~160) and the logits-x-9
+    weights (~670, measured 0.63 mm) stay in the mode; logits x 64 (~4 800, measured 7.6 mm in the mode)
     fall out of it and meet the mode's bar again -- a checkpoint with sharp attention degrades in speed, not silently in millimetres."""
     from oracle import gator_oracle as go
     z, m = build_model('h36m17_bn', 'fused', device=None)
@@ -205,10 +206,13 @@ def _sylvester(n):
     return h
 
 
-def _c3_bounds(sd):
-    """(the fixed guard's bound, the round-6 power iteration's) of the self-attention logits, restated in numpy float64 from the weights:
-    per layer and head, (sigma_max(Wq_h) |x| + |bq_h|) (sigma_max(Wk_h) |x| + |bk_h|) / sqrt(32) in the exp2 domain, |x| <= max|a_2| sqrt(63)
-    + |b_2|; and sigma_max(Wq_h^T Wk_h) |x|^2 / sqrt(32) by 64 power steps from the all-ones vector."""
+def _c3_bounds(sd, c):
+    """(the fixed guard's bound, the round-6 power iteration's) of the attention logits, restated in numpy float64 from the weights.
+    Self-attention, per layer and head: (sigma_max(Wq_h) |x| + |bq_h|) (sigma_max(Wk_h) |x| + |bk_h|) / sqrt(32) in the exp2 domain, |x| <= max|a_2| sqrt(63)
+    + |b_2|; and sigma_max(Wq_h^T Wk_h) |x|^2 / sqrt(32) by 64 power steps from the all-ones vector.  The fixed guard also bounds the other two
+    one-plane attentions the same way and reports the largest: cross-attention sigma_max(Wq_h) sigma_max(Wk_h) |x|^2 / sqrt(32) with |x| <=
+    max|norm1.weight| sqrt(64) + |norm1.bias|; encoder (sigma_max(Wq_h) |x| + |bq_h|) (sigma_max(Wk_h) |x| + |bk_h|) / sqrt(16) + max|hop / path bias|
+    over its 8 heads of 16 rows, |x| <= max|norm1.weight| sqrt(128) + |norm1.bias|."""
     new = old = 0.0
     for sfx in ('', '_1', '_2'):
         g = lambda k: np.asarray(sd['pose2mesh.' + k % sfx], np.float32).astype(np.float64)
@@ -227,6 +231,23 @@ def _c3_bounds(sd):
                     break
                 sig, v = np.sqrt(n), u / n
             old = max(old, sig * xn * xn / np.sqrt(32.0) * np.log2(np.e))
+        cn = np.abs(g('encoder%s.norm1.weight')).max() * np.sqrt(64.0) + np.sqrt((g('encoder%s.norm1.bias') ** 2).sum())
+        cq, ck = g('encoder%s.attn.wq.weight'), g('encoder%s.attn.wk.weight')
+        for h in range(2):
+            r = slice(32 * h, 32 * h + 32)
+            new = max(new, np.linalg.svd(cq[r], compute_uv=False)[0] * np.linalg.svd(ck[r], compute_uv=False)[0] * cn * cn / np.sqrt(32.0) * np.log2(np.e))
+    from oracle import gator_oracle as go
+    f32 = {k: (v if torch.is_tensor(v) else torch.from_numpy(np.asarray(v))) for k, v in sd.items()}
+    hop = float(go.hop_path_bias(f32, c, torch.float32).abs().max())          # the ctx folds the tile in fp32
+    for i in range(6):
+        g = lambda k: np.asarray(sd['pose_lifter.blocks.%d.' % i + k], np.float32).astype(np.float64)
+        w, b = g('attn.qkv.weight'), g('attn.qkv.bias')
+        xn = np.abs(g('norm1.weight')).max() * np.sqrt(128.0) + np.sqrt((g('norm1.bias') ** 2).sum())
+        for h in range(8):
+            q, k = slice(16 * h, 16 * h + 16), slice(128 + 16 * h, 128 + 16 * h + 16)
+            nq = np.linalg.svd(w[q], compute_uv=False)[0] * xn + np.linalg.norm(b[q])
+            nk = np.linalg.svd(w[k], compute_uv=False)[0] * xn + np.linalg.norm(b[k])
+            new = max(new, (nq * nk / 4.0 + hop) * np.log2(np.e))
     return new, old
 
 
@@ -239,7 +260,7 @@ def test_config3_guard_bound_formula(name):
     m(torch.from_numpy(synthetic.synthetic_pose2d(4, c.J, seed=2)).cuda())
     torch.cuda.synchronize()
     state, bound = m.c3_state()
-    new, old = _c3_bounds(sd)
+    new, old = _c3_bounds(sd, c)
     print('\n[config 3 guard, %s] bound %.2f (numpy %.2f; the power iteration gave %.2f)' % (name, bound, new, old))
     assert state and abs(bound - new) <= 1e-4 * new
 
@@ -283,7 +304,7 @@ def test_config3_guard_against_adversarial_weights(case):
     torch.cuda.synchronize()
     m.device_status()
     state, bound = m.c3_state()
-    new, old = _c3_bounds(sd_o)
+    new, old = _c3_bounds(sd_o, c)
     r64, _ = go.gator_forward(sd_o, c, x, torch.float64)
     e = np.abs(v.cpu().numpy().astype(np.float64) - r64.numpy()) * 1e3
     print('\n[config 3 guard, %s] bound %.1f (fixed formula %.1f, power iteration %.1f) -> MDR layers on %s; vs fp64: max %.3f mm rms %.4f mm'
