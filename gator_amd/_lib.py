@@ -70,6 +70,15 @@ class PreprocessNoiseArgs(ctypes.Structure):   # include/gator_hip.h: gator_prep
         [(n, ctypes.c_void_p) for n in ('stats', 'pose2d', 'valid', 'noisy_crop', 'area', 'decisions')]
 
 
+DRAW_KEYPOINTS, DRAW_COCO = 0, 1                # include/gator_hip.h: GATOR_DRAW_*
+
+
+class Draw2dArgs(ctypes.Structure):            # include/gator_hip.h: gator_draw2d_args (device pointers; image_index: host)
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'n_people', 'n_images', 'H', 'W', 'joint_dim', 'style')] + \
+        [('kp_thre', ctypes.c_float), ('alpha', ctypes.c_float), ('reserved', ctypes.c_int32)] + \
+        [(n, ctypes.c_void_p) for n in ('joints', 'colors', 'bbox', 'images', 'out', 'image_index')]
+
+
 LIFT_HUMAN36, LIFT_COCO = 0, 1                  # include/gator_hip.h: GATOR_LIFT_*
 ABI_VERSION = 2                                # include/gator_hip.h: GATOR_ABI_VERSION this binding was written against
 EDEVICE, EDEVICE_DEFERRED = -7, -8
@@ -131,6 +140,11 @@ SIGNATURES = {
     'gator_render_resolve': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _I, ctypes.c_float, _P, _P, _P, _P]),
     'gator_renderer_workspace': (_I, [_P, ctypes.POINTER(_L), ctypes.POINTER(_L)]),
     'gator_renderer_set_small_box': (_I, [_P, _I]),
+    'gator_draw2d_create': (_I, [_P, _I, _I, ctypes.POINTER(_P)]),
+    'gator_draw2d_destroy': (_I, [_P]),
+    'gator_draw2d_u8': (_I, [_P, ctypes.POINTER(Draw2dArgs), _P]),
+    'gator_draw2d_workspace': (_I, [_P, ctypes.POINTER(_L), ctypes.POINTER(_L)]),
+    'gator_draw2d_set_tile_rows': (_I, [_P, _I]),
     'gator_comm_unique_id': (_I, [_P]),
     'gator_comm_create': (_I, [_P, _I, _I, ctypes.POINTER(_P)]),
     'gator_comm_destroy': (_I, [_P]),

@@ -5,7 +5,8 @@ camera that lays the mesh over the image.
   forward_joints' joints [B,n,3] + target --fit_camera-->  cam [B,3] (s, tx, ty), loss [B][, orig_cam [B,4]]   demo/run.py:138-157,21-39
 
 fit_camera runs the reference's 1500 Adam steps of models.project_net.OptimzeCamLayer for every sample of the batch in one launch;
-fit_mesh_to_image is the demo's whole flow, batched; render_fit draws its result over the frames (gator_amd.render, demo/renderer.py)."""
+fit_mesh_to_image is the demo's whole flow, batched; render_fit draws its result over the frames (gator_amd.render, demo/renderer.py) and
+draw_fit the detections it started from (gator_amd.vis, lib/vis.py)."""
 import ctypes
 
 import numpy as np
@@ -104,3 +105,31 @@ def render_fit(fit, faces_or_renderer, images=None, image_size=None, colors=None
         size = (int(image_size[0]), int(image_size[1]))
     r = faces_or_renderer if isinstance(faces_or_renderer, render.MeshRenderer) else render.MeshRenderer(faces_or_renderer, mesh.device, n_verts=mesh.shape[1])
     return r.render(mesh, cam, background=images, color=render.DEMO_COLOR if colors is None else colors, size=size)
+
+
+def draw_fit(fit, raw_joints, skeleton, images, add_pelvis_neck=False, box=False, kp_thre=0.4, alpha=1.0, colors=None, out=None):
+    """The detections over the frames, next to render_fit (demo/run.py:214-219, batched): raw_joints [B,17,2|3] is what fit_mesh_to_image
+    was given, images [B,H,W,3] uint8 on its device.  skeleton: the joint set's limb pairs, or a vis.SkeletonDrawer to reuse.
+    add_pelvis_neck appends the two extra COCO joints by crop_joints' rule (the mean of the hips and of the shoulders; demo/run.py:103-121
+    gives them the product of the two confidences).  A third column is the detector's confidence, tested against kp_thre; the demo draws
+    every joint (two columns).  box=True also draws fit['bbox'], the box the camera was fitted in.  -> [B,H,W,3] uint8 on the device."""
+    from . import vis
+    _lib.need_device('draw_fit', raw_joints, images)
+    x = raw_joints.contiguous().float()
+    if x.dim() != 3 or x.shape[2] not in (2, 3):
+        raise ValueError('draw_fit: expected raw_joints [B,J,2|3], got %s' % (tuple(x.shape),))
+    if add_pelvis_neck:
+        if x.shape[1] < 17:
+            raise ValueError('draw_fit: add_pelvis_neck needs the 17 COCO joints, got %d' % x.shape[1])
+        extra = torch.stack([(x[:, 11] + x[:, 12]) * 0.5, (x[:, 5] + x[:, 6]) * 0.5], 1)
+        if x.shape[2] == 3:
+            extra[:, 0, 2] = x[:, 11, 2] * x[:, 12, 2]
+            extra[:, 1, 2] = x[:, 5, 2] * x[:, 6, 2]
+        x = torch.cat([x, extra], 1)
+    corners = None
+    if box:
+        b = fit['bbox'].to(x.device).float()
+        x0, y0, x1, y1 = b[:, 0], b[:, 1], b[:, 0] + b[:, 2], b[:, 1] + b[:, 3]
+        corners = torch.stack([torch.stack([x0, y0], 1), torch.stack([x1, y0], 1), torch.stack([x1, y1], 1), torch.stack([x0, y1], 1)], 1)
+    d = skeleton if isinstance(skeleton, vis.SkeletonDrawer) else vis.SkeletonDrawer(skeleton, x.shape[1], x.device)
+    return d.draw(images, x, colors=colors, bbox=corners, kp_thre=kp_thre, alpha=alpha, out=out)

@@ -594,6 +594,53 @@ int gator_renderer_workspace(const gator_renderer* r, int64_t* bytes, int64_t* a
 /* Measurement hook (tools/render_bench.py): bounding-box area in pixels up to which one lane walks a triangle alone; 0 = built-in. */
 int gator_renderer_set_small_box(gator_renderer* r, int32_t pixels);
 
+/* The demo's 2D pose overlay (lib/vis.py: vis_2d_keypoints, vis_coco_skeleton) on the device: an ordered, anti-aliased composite of
+ * capsules (cv2.line), discs and rings (cv2.circle) into uint8 frames (gator_amd/csrc/draw2d.hip states the primitive model, the blend
+ * and the final mix; tests/draw_refs.py is the same rule in numpy and the device agrees with it byte for byte).
+ * Byte parity with OpenCV's LINE_AA is not claimed: the documented rule is the contract.
+ *
+ * gator_draw2d_create: skeleton [n_limbs,2] joint index pairs on the HOST.  GATOR_EINVAL with a reason for a NULL argument, n_limbs
+ * outside 1..4096, n_joints < 1, a joint index outside 0..n_joints-1.
+ *
+ * gator_draw2d_u8 draws n_people skeletons into n_images frames of H x W.  Device pointers: joints [n_people,n_joints,joint_dim]
+ * float32 pixels, joint_dim = 2 (x, y) or 3 (x, y, confidence); colors [n_limbs,3] float32 in the image's channel order on the 0..255
+ * scale; bbox [n_people,4,2] float32 corners or NULL; images and out [n_images,H,W,3] uint8, out == images draws in place (no other
+ * overlap).  image_index [n_people] on the HOST names the frame of each person, people of one frame are drawn in person order; NULL:
+ * person p alone in frame p (needs n_people <= n_images; later frames are copied).  kp_thre: with joint_dim == 3 a limb's line needs
+ * both joints' confidence > kp_thre and a joint's mark its own; ignored when joint_dim == 2.  A primitive with a non-finite coordinate
+ * is skipped; coordinates are truncated towards zero and clamped to +-2^20.  alpha in [0, 1]: out = img (1 - alpha) + canvas alpha,
+ * rounded half to even in float32; 1 returns the canvas.  style GATOR_DRAW_KEYPOINTS: lines of thickness 2, filled discs of radius 3,
+ * colors[l] per limb (vis_2d_keypoints); GATOR_DRAW_COCO: lines of thickness 2, rings of radius 2 and thickness 3 (vis_coco_skeleton,
+ * which passes one colour for every limb and joints without confidence).
+ * Two launches on `stream`, no atomics, no host synchronisation; the same bytes from run to run and whatever else is in the batch.  The
+ * primitive records live in the handle and grow when a larger call arrives (the device is synchronised when they do); a call no larger
+ * than an earlier one allocates nothing and, with image_index NULL, is capturable into a graph.  image_index is read before the call
+ * returns.  The calls on one handle are ordered by the caller.
+ * GATOR_EINVAL naming the field, before any launch: a NULL handle, args, joints, colors, images or out; struct_size smaller than this
+ * struct; H or W outside 1..8192; n_people < 1; n_images outside 1..65535; joint_dim not 2 or 3; an unknown style; alpha outside [0, 1]
+ * or NaN; an image_index[p] outside 0..n_images-1; image_index NULL with n_people > n_images. */
+#define GATOR_DRAW_KEYPOINTS 0
+#define GATOR_DRAW_COCO 1
+typedef struct gator_draw2d gator_draw2d;
+typedef struct {
+    int32_t struct_size; /* = sizeof of this struct in the caller's header */
+    int32_t n_people, n_images, H, W, joint_dim, style;
+    float kp_thre, alpha;
+    int32_t reserved;
+    const float *joints, *colors, *bbox;
+    const uint8_t* images;
+    uint8_t* out;
+    const int32_t* image_index; /* HOST */
+} gator_draw2d_args;
+int gator_draw2d_create(const int32_t* skeleton, int32_t n_limbs, int32_t n_joints, gator_draw2d** out);
+int gator_draw2d_destroy(gator_draw2d* d);
+int gator_draw2d_u8(gator_draw2d* d, const gator_draw2d_args* args, void* stream);
+/* Test hook: bytes of workspace the handle holds and how many allocations it has made since create. */
+int gator_draw2d_workspace(const gator_draw2d* d, int64_t* bytes, int64_t* allocations);
+/* Measurement and test hook (tools/draw_bench.py): the tile kernel has two forms that write the same bytes, 64 x 4 pixel tiles with one
+ * pixel a thread (rows = 1) and 64 x 16 tiles with four (rows = 4); 0 = the built-in choice by the size of the grid. */
+int gator_draw2d_set_tile_rows(gator_draw2d* d, int32_t rows);
+
 /* Host-side graph constants (no GPU needed).  Replace the absent Cython algos.pyx
  * (lib/models/backbones/setup.py:1-6) and lib/models/backbones/modules.py:6-29, lib/graph_utils.py:71-89. */
 int gator_floyd_warshall(const float* adj, int32_t n, int64_t* dist, int64_t* path);
