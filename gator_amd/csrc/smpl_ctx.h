@@ -1,0 +1,59 @@
+// The SMPL handle (gator_smpl_*): the packed model and the workspaces of its two users, the layer (smpl_lbs.hip) and the fit
+// (smpl_fit.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "internal.h"
+
+namespace gator {
+constexpr int kSmplMaxJ = 32, kSmplMaxB = 16;
+constexpr int kTV = 128;     // vertices per tile of the layer: four waves of 32 columns; the vertex planes are padded to whole tiles
+}  // namespace gator
+
+struct gator_smpl {
+    int device = 0, NV = 0, NJ = 0, NB = 0, K = 0, Kp = 0, NVp = 0, MI = 0;
+    gator::DevBuf<float> basis;      // [3][Kp][NVp]  coordinate planes of [shapedirs | posedirs], zero padded
+    gator::DevBuf<float> vtempl;     // [3][NVp]
+    gator::DevBuf<int32_t> widx;     // [MI][NVp]     skinning influences of a vertex: joint index ...
+    gator::DevBuf<float> wval;       // [MI][NVp]     ... and weight (0 in unused slots)
+    gator::DevBuf<double> jfold;     // [NJ*3][1+NB]  J_regressor . v_template, J_regressor . shapedirs (folded in fp64)
+    gator::DevBuf<int32_t> parents;  // [NJ]
+    // workspace of the forward, grown when a larger batch arrives
+    gator::DevBuf<float> coef;       // [cap][Kp]
+    gator::DevBuf<float> xform;      // [cap][NJ][12]
+    gator::DevBuf<float> offs;       // [cap][4]
+    int cap = 0;
+    // the fit: model side (folded at create), then its workspace, grown like the forward's
+    gator::DevBuf<uint32_t> amask;   // [MI][NVp]     bit k: joint k is the influence's joint or one of its ancestors (MI <= 4 only)
+    double tcen[3] = {0, 0, 0};      // centroid of v_template
+    gator::DevBuf<float> fjoints;    // [fcap][NJ][3] posed joints of the candidate
+    gator::DevBuf<float> fstate;     // [2][fcap][P]  candidate, current: pose | betas | trans, three arrays each
+    gator::DevBuf<double> fscal;     // [fcap][4]     lambda, squared error of the current state, bad-sample flag
+    gator::DevBuf<float> fpart;      // [fcap][S][pairs][32][32] per-chunk partial sums of M's upper tiles
+    gator::DevBuf<float> fM;         // [2][fcap][N][N] M of the candidate, of the current state
+    int fcap = 0;
+};
+
+namespace gator {
+// The layer's Rodrigues (rodrigues_layer.py:13-52) in fp64: angle = |axisang + 1e-8|, quaternion (cos, sin . axisang / angle), normalised
+// (axisang / angle is no unit vector), then quat2mat.  r: 3x3 row-major.
+__device__ inline void smpl_rodrigues(double ax, double ay, double az, double* r) {
+    const double ex = ax + 1e-8, ey = ay + 1e-8, ez = az + 1e-8;             // batch_rodrigues: norm(axisang + 1e-8)
+    const double angle = sqrt(ex * ex + ey * ey + ez * ez);
+    const double half = angle * 0.5, sn = sin(half);
+    double w = cos(half), x = sn * (ax / angle), y = sn * (ay / angle), z = sn * (az / angle);
+    const double qn = sqrt(w * w + x * x + y * y + z * z);                   // quat2mat normalises: axisang / angle is no unit vector
+    w /= qn; x /= qn; y /= qn; z /= qn;
+    const double w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z, wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
+    r[0] = w2 + x2 - y2 - z2; r[1] = 2 * xy - 2 * wz;    r[2] = 2 * wy + 2 * xz;
+    r[3] = 2 * wz + 2 * xy;   r[4] = w2 - x2 + y2 - z2;  r[5] = 2 * yz - 2 * wx;
+    r[6] = 2 * xz - 2 * wy;   r[7] = 2 * wx + 2 * yz;    r[8] = w2 - x2 - y2 + z2;
+}
+
+int smpl_reserve(gator_smpl* c, int B);                                  // the forward's workspace for a batch of B
+// k_smpl_pose on the ctx's workspace (coefficient rows, skinning transforms, offsets), no centring, scale 1
+int smpl_pose_stage(gator_smpl* c, const float* pose, const float* betas, const float* trans, int batch, float* joints, hipStream_t st);
+int smpl_fit_build(gator_smpl* c, const gator_smpl_model* m);            // smpl_fit.hip: the fit's share of gator_smpl_create
+}  // namespace gator

@@ -17,28 +17,12 @@
 #include <vector>
 
 #include "internal.h"
-
-struct gator_smpl {
-    int device = 0, NV = 0, NJ = 0, NB = 0, K = 0, Kp = 0, NVp = 0, MI = 0;
-    gator::DevBuf<float> basis;      // [3][Kp][NVp]  coordinate planes of [shapedirs | posedirs], zero padded
-    gator::DevBuf<float> vtempl;     // [3][NVp]
-    gator::DevBuf<int32_t> widx;     // [MI][NVp]     skinning influences of a vertex: joint index ...
-    gator::DevBuf<float> wval;       // [MI][NVp]     ... and weight (0 in unused slots)
-    gator::DevBuf<double> jfold;     // [NJ*3][1+NB]  J_regressor . v_template, J_regressor . shapedirs (folded in fp64)
-    gator::DevBuf<int32_t> parents;  // [NJ]
-    // workspace of the forward, grown when a larger batch arrives
-    gator::DevBuf<float> coef;       // [cap][Kp]
-    gator::DevBuf<float> xform;      // [cap][NJ][12]
-    gator::DevBuf<float> offs;       // [cap][4]
-    int cap = 0;
-};
+#include "smpl_ctx.h"
 
 namespace gator {
 namespace {
 
-constexpr int kSmplMaxJ = 32, kSmplMaxB = 16;
 constexpr int kTS = 32;      // samples per tile: the M of one 32x32x2 MFMA
-constexpr int kTV = 128;     // vertices per tile: four waves of 32 columns
 constexpr int kKU = 4;      // k-pairs per pipeline stage of the blend GEMM: K is padded to two stages, 4 kKU
 constexpr int kCoefLd = 33;  // LDS leading dimension of the transposed coefficient tile (conflict-free both ways)
 
@@ -61,17 +45,8 @@ __global__ __launch_bounds__(64) void k_smpl_pose(const float* __restrict__ pose
         const float* a = pose + ((size_t)b * NJ + t) * 3;
         const double ax = a[0], ay = a[1], az = a[2];
         poison += (ax + ay + az) * 0.0;
-        const double ex = ax + 1e-8, ey = ay + 1e-8, ez = az + 1e-8;             // batch_rodrigues: norm(axisang + 1e-8)
-        const double angle = sqrt(ex * ex + ey * ey + ez * ez);
-        const double half = angle * 0.5, sn = sin(half);
-        double w = cos(half), x = sn * (ax / angle), y = sn * (ay / angle), z = sn * (az / angle);
-        const double qn = sqrt(w * w + x * x + y * y + z * z);                   // quat2mat normalises: axisang / angle is no unit vector
-        w /= qn; x /= qn; y /= qn; z /= qn;
-        const double w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z, wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
         double* r = R + t * 9;
-        r[0] = w2 + x2 - y2 - z2; r[1] = 2 * xy - 2 * wz;    r[2] = 2 * wy + 2 * xz;
-        r[3] = 2 * wz + 2 * xy;   r[4] = w2 - x2 + y2 - z2;  r[5] = 2 * yz - 2 * wx;
-        r[6] = 2 * xz - 2 * wy;   r[7] = 2 * wx + 2 * yz;    r[8] = w2 - x2 - y2 + z2;
+        smpl_rodrigues(ax, ay, az, r);
         if (t >= 1)
             for (int e = 0; e < 9; ++e) cf[NB + (t - 1) * 9 + e] = (float)(r[e] - ((e & 3) == 0 ? 1.0 : 0.0));      // subtract_flat_id
         for (int c = 0; c < 3; ++c) {
@@ -283,6 +258,8 @@ int smpl_build(gator_smpl* c, const gator_smpl_model* m) {
     return GATOR_OK;
 }
 
+}  // namespace
+
 int smpl_reserve(gator_smpl* c, int B) {
     if (B <= c->cap) return GATOR_OK;
     if (c->cap) GATOR_HIP_CHECK(hipDeviceSynchronize());       // queued forwards may still read the buffers that are replaced
@@ -293,7 +270,13 @@ int smpl_reserve(gator_smpl* c, int B) {
     c->cap = B;
     return GATOR_OK;
 }
-}  // namespace
+
+int smpl_pose_stage(gator_smpl* c, const float* pose, const float* betas, const float* trans, int batch, float* joints, hipStream_t st) {
+    k_smpl_pose<<<batch, 64, 0, st>>>(pose, c->NB ? betas : nullptr, trans, c->jfold, c->parents, c->NJ, c->NB, c->K, c->Kp, -1, 1.0,
+                                      c->coef, c->xform, c->offs, joints);
+    GATOR_HIP_CHECK(hipGetLastError());
+    return GATOR_OK;
+}
 }  // namespace gator
 
 extern "C" int gator_smpl_create(const gator_smpl_model* m, gator_smpl** out) {
@@ -319,6 +302,7 @@ extern "C" int gator_smpl_create(const gator_smpl_model* m, gator_smpl** out) {
     const hipError_t e = hipGetDevice(&c->device);
     if (e != hipSuccess) rc = fail(GATOR_EHIP, "gator_smpl_create: no HIP device available: %s", hipGetErrorString(e));
     if (rc == GATOR_OK) rc = smpl_build(c, m);
+    if (rc == GATOR_OK) rc = smpl_fit_build(c, m);
     if (rc != GATOR_OK) { delete c; return rc; }
     *out = c;
     return GATOR_OK;

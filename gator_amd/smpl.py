@@ -5,6 +5,7 @@ data/COCO/dataset.py:147-166), batched.
   SMPLLayer(pose [B,72], betas [B,10] | None, trans [B,3] | None)  ->  (verts [B,6890,3], joints [B,24,3])      the layer's own call
   get_smpl_coord(layer, pose, shape, trans)                        ->  (mesh, joints + five face key points), mm   the datasets' wrapper
   targets_from_smpl(layer, pose, shape, trans, regressors ...)     ->  {'mesh', 'reg_pose3d', 'lift_pose3d'}        Trainer.step's targets
+  SMPLLayer.fit(verts [B,6890,3], iters, init) / fit_to_mesh(layer, verts) -> (pose, betas, trans, rms)             the inverse: mesh -> parameters
 
 The model's arrays come from the caller: the official files are licence-gated and are no part of this package.  No backward: the
 reference never differentiates through the layer."""
@@ -143,6 +144,67 @@ class SMPLLayer:
         return verts, joints
 
     __call__ = forward
+
+    def fit_width(self):
+        """(P, N): the fit's unknowns, 3 NJ + NB + 3, and the padded width of its normal matrix."""
+        P, N = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(_lib.load().gator_smpl_fit_width(self._ctx, ctypes.byref(P), ctypes.byref(N)), 'gator_smpl_fit_width')
+        return P.value, N.value
+
+    def _verts_arg(self, verts):
+        if verts.dim() != 3 or verts.shape[1:] != (self.num_verts, 3):
+            raise ValueError('SMPLLayer: verts must be [B,%d,3], got %s' % (self.num_verts, tuple(verts.shape)))
+        if not verts.is_cuda or verts.device != self.device:
+            raise RuntimeError('SMPLLayer: verts must live on %s' % (self.device,))
+        return verts.contiguous().float()
+
+    def fit(self, verts, iters=20, init=None):
+        """The inverse of forward: (pose [B,NJ*3], betas [B,NB], trans [B,3], rms [B]) whose forward (out_scale 1, no centring) is the
+        least-squares fit to verts [B,NV,3] (the layer's unit), by `iters` Levenberg-Marquardt steps on the device
+        (gator_smpl_fit_f32, csrc/smpl_fit.hip).  init: a (pose, betas, trans) tuple, e.g. the previous frame's result; None starts
+        from zero pose, zero betas and the centroid offset.  rms: the root mean square vertex distance of the returned state.
+        No host synchronisation; capturable into a graph; a sample with a non-finite input comes back as NaN, alone.
+
+        Deliberately out of scope: pose and shape priors, joint-limit constraints, per-vertex weights, fitting to 2D evidence, and
+        models with more than 4 influences per vertex (refused).  The result is the unconstrained least-squares fit in vertex
+        space: on a mesh that no parameters reproduce, nothing keeps the pose plausible."""
+        verts = self._verts_arg(verts)
+        B = verts.shape[0]
+        if init is not None:
+            if len(init) != 3:
+                raise ValueError('SMPLLayer.fit: init is a (pose, betas, trans) tuple')
+            ip, ib, it = (self._arg(init[0], self.num_joints * 3, 'init pose', B), self._arg(init[1], self.num_betas, 'init betas', B),
+                          self._arg(init[2], 3, 'init trans', B))
+        else:
+            ip = ib = it = None
+        pose, betas, trans, rms = (torch.empty(shape, device=self.device, dtype=torch.float32)
+                                   for shape in ((B, self.num_joints * 3), (B, self.num_betas), (B, 3), (B,)))
+        ptr = _lib.ptr
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().gator_smpl_fit_f32(self._ctx, ptr(verts), ptr(ip), ptr(ib), ptr(it), B, int(iters), ptr(pose), ptr(betas),
+                                                      ptr(trans), ptr(rms), _lib.stream_ptr(self.device)), 'gator_smpl_fit_f32')
+        return pose, betas, trans, rms
+
+    def fit_normal(self, pose, betas, trans, verts):
+        """The fit's stage entry (gator_smpl_fit_normal_f32): M = [J | r]^T [J | r] at the given state, [B,N,N] float32 with
+        H = M[:, :P, :P], g = M[:, :P, P] and the squared error M[:, P, P].  Only the upper triangle is specified."""
+        verts = self._verts_arg(verts)
+        B = verts.shape[0]
+        pose = self._arg(pose, self.num_joints * 3, 'pose', B)
+        betas = self._arg(betas, self.num_betas, 'betas', B)
+        trans = self._arg(trans, 3, 'trans', B)
+        N = self.fit_width()[1]
+        M = torch.zeros((B, N, N), device=self.device, dtype=torch.float32)
+        ptr = _lib.ptr
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().gator_smpl_fit_normal_f32(self._ctx, ptr(pose), ptr(betas), ptr(trans), ptr(verts), B, ptr(M),
+                                                             _lib.stream_ptr(self.device)), 'gator_smpl_fit_normal_f32')
+        return M
+
+
+def fit_to_mesh(layer, verts, **kw):
+    """SMPLLayer.fit as a function: verts [B,NV,3] -> (pose, betas, trans, rms); iters= and init= as there."""
+    return layer.fit(verts, **kw)
 
 
 def get_smpl_coord(layer, pose, shape, trans=None):

@@ -317,6 +317,31 @@ int gator_smpl_forward_f32(gator_smpl* ctx, const float* pose, const float* beta
 /* Test hook: the base of the ctx's workspace and the batch it holds (0 / NULL before the first forward). */
 int gator_smpl_workspace(const gator_smpl* ctx, const void** base, int64_t* capacity);
 
+/* The inverse of the layer: a batched Levenberg-Marquardt fit of (pose [batch, NJ*3], betas [batch, NB], trans [batch, 3]) to target
+ * vertices [batch, NV, 3] in the layer's unit, out_scale 1, no centring; device pointers.  The result is the UNCONSTRAINED least-squares
+ * fit in vertex space: no pose or shape prior, no joint limits, no per-vertex weights, no 2D evidence.  Models with more than 4
+ * influences per vertex are refused (GATOR_EUNSUPPORTED with a reason); the layer itself takes them.
+ *   unknowns  P = 3 NJ + NB + 3: a world-frame rotation increment per joint, the betas, the translation;
+ *   M         [J | r]^T [J | r] of width N = 32 ceil((P + 1) / 32) (96 for SMPL): H = M[:P,:P], g = M[:P,P], squared error M[P][P];
+ *             the Jacobian, the damping schedule and the update are stated once in csrc/smpl_fit.hip.
+ * gator_smpl_fit_f32: `iters` (1..256) steps from the given start (init_pose, init_betas, init_trans: NULL together or set together;
+ *   the warm start of a video is the previous frame's result) or from zero pose, zero betas and trans = centroid(target) -
+ *   centroid(v_template).  out_pose / out_betas / out_trans: the float32 state to feed back to gator_smpl_forward_f32; out_rms [batch]:
+ *   the root mean square vertex distance of that state.  A fixed number of launches decided by the arguments: no host read, no early
+ *   exit, capturable into a graph; a repeated call at a batch no larger than an earlier one allocates nothing.  A sample's result does
+ *   not depend on the batch around it (bit for bit) and is the same from run to run; a non-finite target or start makes that sample's
+ *   four outputs NaN and changes no other sample.
+ * gator_smpl_fit_normal_f32: the stage entry, M at a given state: out_M [batch, N, N], of which the upper 32x32 tiles (every element
+ *   [a][b] with a / 32 <= b / 32, so the whole upper triangle) are written and the rest is left alone.
+ * gator_smpl_fit_width: P and N of the ctx's model (either pointer may be NULL).
+ * GATOR_EINVAL with a reason, before any launch: a NULL ctx, target or output, iters outside 1..256, a partial init, batch < 0 or above
+ * 65535.  batch = 0 is a no-op. */
+int gator_smpl_fit_f32(gator_smpl* ctx, const float* target_verts, const float* init_pose, const float* init_betas, const float* init_trans,
+                       int32_t batch, int32_t iters, float* out_pose, float* out_betas, float* out_trans, float* out_rms, void* stream);
+int gator_smpl_fit_normal_f32(gator_smpl* ctx, const float* pose, const float* betas, const float* trans, const float* target_verts,
+                              int32_t batch, float* out_M, void* stream);
+int gator_smpl_fit_width(const gator_smpl* ctx, int32_t* P, int32_t* N);
+
 /* Multi-GPU: samples are independent, the batch is sharded contiguously over one process per GPU, and the path's one
  * collective is the all-gather of the predicted vertices [B/N,6890,3] (+ pose3d [B/N,J,3]) over xGMI.  gator_amd/parallel.py issues
  * it through torch.distributed ("nccl" = RCCL); these entry points do the same on RCCL directly for hosts without torch:
