@@ -3,6 +3,8 @@ does not load, importing the HIP path raises -- the product never routes through
 import ctypes
 import os
 
+import numpy as np
+
 try:
     import torch        # the callers' tensors and streams; the binding itself loads without it
 except ImportError:
@@ -226,6 +228,46 @@ def stream_ptr(device):
 def ptr(t):
     """A tensor's address, or None (a NULL pointer) for an absent optional tensor."""
     return None if t is None else t.data_ptr()
+
+
+def host_ptr(a):
+    """A host numpy array as a `void*` argument, or None (a NULL pointer) for an absent optional array."""
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def host_index(a):
+    """Integer indices (numpy, a sequence or a tensor) as a contiguous host int32 array of the same shape."""
+    a = np.asarray(a.cpu() if torch is not None and torch.is_tensor(a) else a).astype(np.int64)
+    return np.ascontiguousarray(np.clip(a, -1, 2 ** 31 - 1).astype(np.int32))       # out-of-range stays out of range for the C ABI's check
+
+
+class DeviceHandle:
+    """A handle of an auxiliary library (include/gator_hip.h: <PREFIX>_create / _destroy / _workspace) on one HIP device."""
+    PREFIX = None
+    NO_CPU = 'the device must be a HIP device (there is no CPU path)'
+
+    def _create(self, device, *args):
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('%s: %s' % (type(self).__name__, self.NO_CPU))
+        if self.device.index is None:       # tensors report their device with its index
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self._lib, self._h = load(), ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(getattr(self._lib, self.PREFIX + '_create')(*args, ctypes.byref(self._h)), self.PREFIX + '_create')
+
+    def close(self):
+        h, self._h = getattr(self, '_h', None), None      # (no module global here: __del__ also runs while the interpreter shuts down)
+        if h:
+            getattr(self._lib, self.PREFIX + '_destroy')(h)
+
+    __del__ = close
+
+    def workspace(self):
+        """(bytes held, allocations made since create) -- the test hook of the C ABI."""
+        b, n = ctypes.c_int64(), ctypes.c_int64()
+        check(getattr(self._lib, self.PREFIX + '_workspace')(self._h, ctypes.byref(b), ctypes.byref(n)), self.PREFIX + '_workspace')
+        return b.value, n.value
 
 
 def need_device(who, *tensors, what='inputs'):

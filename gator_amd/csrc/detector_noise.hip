@@ -8,7 +8,7 @@
 // fp64 where the reference has it; the build disables contracted multiply-adds for every source (gator_amd/build.py: FLAGS).
 #include <hip/hip_runtime.h>
 
-#include "internal.h"
+#include "handle.h"
 #include "joints2d.h"
 #include "philox.h"
 
@@ -273,9 +273,7 @@ extern "C" int gator_preprocess_noise_f32(const gator_preprocess_noise_args* arg
     using namespace gator;
     const char* who = "gator_preprocess_noise_f32";
     if (!args) return fail(GATOR_EINVAL, "%s: null args", who);
-    if (args->struct_size != (int32_t)sizeof(gator_preprocess_noise_args))
-        return fail(GATOR_EINVAL, "%s: struct_size %d, this library's gator_preprocess_noise_args has %d bytes", who, args->struct_size,
-                    (int)sizeof(gator_preprocess_noise_args));
+    GATOR_TRY(check_struct_size(who, "gator_preprocess_noise_args", args->struct_size, sizeof(gator_preprocess_noise_args)));
     const gator_preprocess_noise_args& a = *args;
     if (a.batch < 0) return fail(GATOR_EINVAL, "%s: batch %d", who, a.batch);
     if (!a.joints || !a.pose2d || !a.valid || !a.noisy_crop) return fail(GATOR_EINVAL, "%s: joints, pose2d, valid and noisy_crop are required", who);

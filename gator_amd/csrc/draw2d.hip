@@ -42,10 +42,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
-#include <vector>
 
-#include "internal.h"
+#include "handle.h"
 
 namespace gator {
 namespace {
@@ -71,18 +69,13 @@ struct Tables { const int32_t *img_off, *person_of; };      // both NULL: person
 }  // namespace
 }  // namespace gator
 
-struct gator_draw2d {
-    ~gator_draw2d() { if (tab_copied) (void)hipEventDestroy(tab_copied); }
-    int device = 0, L = 0, J = 0;
+struct gator_draw2d : gator::Handle {
+    int L = 0, J = 0;
     int rows = 0;                                 // gator_draw2d_set_tile_rows: 0 = the built-in choice
     gator::DevBuf<int32_t> skeleton;              // [L][2]
-    // workspace, grown when a larger call arrives (a capacity is 0 whenever its buffer is not there)
-    gator::DevBuf<gator::Prim> recs;              // [cap_recs]
-    gator::DevBuf<int32_t> tab;                   // [cap_tab]  img_off [N+1] | person_of [P]
-    gator::DevBuf<int32_t, true> tab_host;        // pinned staging of tab
-    hipEvent_t tab_copied = nullptr;              // recorded behind the staging's copy; the next call waits for it before it rewrites the staging
-    size_t cap_recs = 0, cap_tab = 0, cap_tab_host = 0;
-    int64_t allocations = 0, bytes = 0;
+    // workspace, grown when a larger call arrives (gator::Handle::grow)
+    gator::WorkBuf<gator::Prim> recs;             // [P][records per person]
+    gator::StagedTable<int32_t> tab;              // img_off [N+1] | person_of [P]
 };
 
 namespace gator {
@@ -268,41 +261,23 @@ __global__ __launch_bounds__(256) void k_draw_tiles(const Prim* __restrict__ rec
     }
 }
 
-template <class T, bool Pn> int grow(gator_draw2d* h, DevBuf<T, Pn>& buf, size_t& cap, size_t need) {
-    if (need <= cap) return GATOR_OK;
-    GATOR_HIP_CHECK(hipDeviceSynchronize());          // queued work may still read the block that is replaced
-    h->bytes -= (int64_t)(cap * sizeof(T));
-    cap = 0;
-    GATOR_TRY(buf.alloc(need * sizeof(T)));
-    h->bytes += (int64_t)(need * sizeof(T));
-    h->allocations += 1;
-    cap = need;
-    return GATOR_OK;
-}
-
-// render.hip's make_tables convention: image_index (host) or NULL for "person p alone in image p"; people of an image keep person order
+// image_index (host) or NULL for "person p alone in image p"; people of an image keep person order (image_groups.h)
 int make_tables(gator_draw2d* h, const char* who, const int32_t* image_index, int P, int N, hipStream_t st, Tables* tb) {
     *tb = Tables{nullptr, nullptr};
-    if (!image_index) {
-        if (P > N) return fail(GATOR_EINVAL, "%s: image_index is NULL, so person p goes into image p, but n_people %d > n_images %d", who, P, N);
-        return GATOR_OK;
-    }
-    for (int p = 0; p < P; ++p)
-        if (image_index[p] < 0 || image_index[p] >= N)
-            return fail(GATOR_EINVAL, "%s: image_index[%d] = %d outside 0..%d", who, p, image_index[p], N - 1);
     const size_t count = (size_t)N + 1 + P;
-    GATOR_HIP_CHECK(hipEventSynchronize(h->tab_copied));      // the last call's copy has read the staging
-    GATOR_TRY(grow(h, h->tab_host, h->cap_tab_host, count));
-    GATOR_TRY(grow(h, h->tab, h->cap_tab, count));
-    int32_t *img_off = h->tab_host.get(), *person_of = img_off + N + 1;
-    std::memset(img_off, 0, count * sizeof(int32_t));
-    for (int p = 0; p < P; ++p) img_off[image_index[p] + 1]++;
-    for (int n = 0; n < N; ++n) img_off[n + 1] += img_off[n];
-    std::vector<int32_t> fill(img_off, img_off + N);
-    for (int p = 0; p < P; ++p) person_of[fill[image_index[p]]++] = p;
-    GATOR_HIP_CHECK(hipMemcpyAsync(h->tab.get(), img_off, count * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    GATOR_HIP_CHECK(hipEventRecord(h->tab_copied, st));
-    *tb = Tables{h->tab.get(), h->tab.get() + N + 1};
+    int32_t* t = nullptr;
+    ImageGroups g = image_groups(nullptr, P, N, nullptr, nullptr, nullptr);
+    if (image_index) {
+        GATOR_TRY(h->tab.stage(h, count, &t));
+        g = image_groups(image_index, P, N, t, t + N + 1, nullptr);
+    }
+    if (g.error == ImageGroups::kNullTooMany)
+        return fail(GATOR_EINVAL, "%s: image_index is NULL, so person p goes into image p, but n_people %d > n_images %d", who, P, N);
+    if (g.error) return fail(GATOR_EINVAL, "%s: image_index[%d] = %d outside 0..%d", who, g.at, g.value, N - 1);
+    if (!image_index) return GATOR_OK;
+    const int32_t* d = nullptr;
+    GATOR_TRY(h->tab.upload(h, count, st, &d));
+    *tb = Tables{d, d + N + 1};
     return GATOR_OK;
 }
 
@@ -319,34 +294,18 @@ extern "C" int gator_draw2d_create(const int32_t* skeleton, int32_t n_limbs, int
     for (int k = 0; k < n_limbs * 2; ++k)
         if (skeleton[k] < 0 || skeleton[k] >= n_joints)
             return fail(GATOR_EINVAL, "%s: skeleton limb %d has joint index %d outside 0..%d", who, k / 2, skeleton[k], n_joints - 1);
-    gator_draw2d* h = new gator_draw2d;
-    h->L = n_limbs; h->J = n_joints;
-    auto build = [&]() -> int {
-        GATOR_HIP_CHECK(hipGetDevice(&h->device));
-        GATOR_HIP_CHECK(hipEventCreateWithFlags(&h->tab_copied, hipEventDisableTiming));
+    return create_handle(out, [&](gator_draw2d* h) -> int {
+        h->L = n_limbs; h->J = n_joints;
         GATOR_TRY(h->skeleton.alloc((size_t)n_limbs * 2 * sizeof(int32_t)));
         GATOR_HIP_CHECK(hipMemcpy(h->skeleton.get(), skeleton, (size_t)n_limbs * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
         return GATOR_OK;
-    };
-    const int rc = build();
-    if (rc != GATOR_OK) { delete h; return rc; }
-    *out = h;
-    return GATOR_OK;
+    });
 }
 
-extern "C" int gator_draw2d_destroy(gator_draw2d* h) {
-    if (!h) return GATOR_OK;
-    (void)hipDeviceSynchronize();
-    delete h;
-    return GATOR_OK;
-}
+extern "C" int gator_draw2d_destroy(gator_draw2d* h) { return gator::destroy_handle(h); }
 
 extern "C" int gator_draw2d_workspace(const gator_draw2d* h, int64_t* bytes, int64_t* allocations) {
-    using namespace gator;
-    if (!h) return fail(GATOR_EINVAL, "gator_draw2d_workspace: null handle");
-    if (bytes) *bytes = h->bytes;
-    if (allocations) *allocations = h->allocations;
-    return GATOR_OK;
+    return gator::handle_workspace(h, "gator_draw2d_workspace", bytes, allocations);
 }
 
 extern "C" int gator_draw2d_set_tile_rows(gator_draw2d* h, int32_t rows) {
@@ -360,13 +319,9 @@ extern "C" int gator_draw2d_set_tile_rows(gator_draw2d* h, int32_t rows) {
 extern "C" int gator_draw2d_u8(gator_draw2d* h, const gator_draw2d_args* a, void* stream) {
     using namespace gator;
     const char* who = "gator_draw2d_u8";
-    if (!h) return fail(GATOR_EINVAL, "%s: null handle", who);
+    GATOR_TRY(check_handle(h, who));
     if (!a) return fail(GATOR_EINVAL, "%s: null args", who);
-    if (a->struct_size < (int32_t)sizeof(gator_draw2d_args))
-        return fail(GATOR_EINVAL, "%s: struct_size %d is smaller than this library's gator_draw2d_args (%d bytes)", who, a->struct_size, (int)sizeof(gator_draw2d_args));
-    int dev = 0;
-    GATOR_HIP_CHECK(hipGetDevice(&dev));
-    if (dev != h->device) return fail(GATOR_EINVAL, "%s: the handle lives on device %d, the current device is %d", who, h->device, dev);
+    GATOR_TRY(check_struct_size(who, "gator_draw2d_args", a->struct_size, sizeof(gator_draw2d_args), true));
     if (!a->joints) return fail(GATOR_EINVAL, "%s: joints is NULL", who);
     if (!a->colors) return fail(GATOR_EINVAL, "%s: colors is NULL", who);
     if (!a->images) return fail(GATOR_EINVAL, "%s: images is NULL", who);
@@ -383,7 +338,7 @@ extern "C" int gator_draw2d_u8(gator_draw2d* h, const gator_draw2d_args* a, void
     hipStream_t st = (hipStream_t)stream;
     Tables tb;
     GATOR_TRY(make_tables(h, who, a->image_index, a->n_people, a->n_images, st, &tb));
-    GATOR_TRY(grow(h, h->recs, h->cap_recs, (size_t)a->n_people * R));
+    GATOR_TRY(h->grow(h->recs, (size_t)a->n_people * R));
     const int threads = a->n_people * (h->L + 1);
     k_draw_build<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(a->joints, h->J, a->joint_dim, h->skeleton, h->L, a->colors, a->bbox,
                                                                     a->n_people, a->kp_thre, a->style, h->recs);

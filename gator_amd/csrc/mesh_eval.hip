@@ -181,9 +181,7 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_errors(const float* __res
     }
 }
 
-bool coo_ok(const gator_coo& g) {
-    return g.nnz >= 0 && g.n_joint >= 1 && g.n_joint <= kMaxRegJoints && (g.nnz == 0 || (g.row && g.col && g.val));
-}
+bool reg_ok(const gator_coo& g, int root) { return coo_ok(g) && g.n_joint <= kMaxRegJoints && root >= 0 && root < g.n_joint; }
 
 }  // namespace
 }  // namespace gator
@@ -194,14 +192,14 @@ extern "C" int gator_mesh_errors_f32(const float* pred, const float* target, int
     using namespace gator;
     if (!pred || !target || !errors || !root_regressor) return fail(GATOR_EINVAL, "gator_mesh_errors_f32: null mesh, output or root regressor");
     if (batch <= 0 || n_verts < 3) return fail(GATOR_EINVAL, "gator_mesh_errors_f32: batch %d, n_verts %d (batch >= 1, n_verts >= 3)", batch, n_verts);
-    if (!coo_ok(*root_regressor) || root < 0 || root >= root_regressor->n_joint)
+    if (!reg_ok(*root_regressor, root))
         return fail(GATOR_EINVAL, "gator_mesh_errors_f32: root regressor (nnz >= 0 with its arrays, 1..64 joints, root inside them)");
     gator_coo ev = {nullptr, nullptr, nullptr, -1, 0};          // nnz < 0: the kernel's mark for "absent"
     const bool has_eval = eval_regressor && !(eval_regressor->nnz == 0 && !eval_regressor->row && !eval_regressor->col && !eval_regressor->val);
     int ne = 0;
     if (has_eval) {
         ev = *eval_regressor;
-        if (!coo_ok(ev) || eval_root < 0 || eval_root >= ev.n_joint)
+        if (!reg_ok(ev, eval_root))
             return fail(GATOR_EINVAL, "gator_mesh_errors_f32: evaluation regressor (nnz >= 0 with its arrays, 1..64 joints, root inside them)");
         ne = eval_joints ? n_eval : ev.n_joint;
         if (ne < 3 || ne > kMaxPts) return fail(GATOR_EINVAL, "gator_mesh_errors_f32: 3..32 evaluation joints");

@@ -26,6 +26,9 @@ inline int raise_pts_lds(const void* fn, bool (&done)[64]) {
     return GATOR_OK;
 }
 
+// A gator_coo as every entry point takes it: a count, and its three arrays unless it is empty.  The joint range is the caller's.
+inline bool coo_ok(const gator_coo& g) { return g.nnz >= 0 && (g.nnz == 0 || (g.row && g.col && g.val)); }
+
 // The sum of x over the 64 lanes of a wave, the same bits in every lane: a + b == b + a bit for bit, so after each xor step both
 // partners hold one value.
 __device__ __forceinline__ double wave_sum(double x) {

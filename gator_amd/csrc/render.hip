@@ -38,26 +38,20 @@
 #include <cstring>
 #include <vector>
 
-#include "internal.h"
+#include "handle.h"
 
-struct gator_renderer {
-    ~gator_renderer() { if (tab_copied) (void)hipEventDestroy(tab_copied); }
-    int device = 0, F = 0, V = 0;
+struct gator_renderer : gator::Handle {
+    int F = 0, V = 0;
     int small_box = 0;                 // box area (pixels) up to which a lane walks its own triangle
     gator::DevBuf<int32_t> faces;      // [F][3]
     gator::DevBuf<int32_t> vf_off;     // [V+1]  vertex-to-face CSR ...
     gator::DevBuf<int32_t> vf;         // [3F][3] ... the faces of a vertex, ascending, each as its three vertex indices (one load less in the chain)
-    // workspace of gator_render_f32 and the image tables of every entry point, grown when a larger call arrives
-    // (a capacity is the element count its buffer holds and is 0 whenever the buffer is not there: gator::grow)
-    gator::DevBuf<int32_t> xy;         // [cap_xy][2]
-    gator::DevBuf<float> z;            // [cap_z]
-    gator::DevBuf<float> nrm;          // [cap_nrm][3]
-    gator::DevBuf<uint64_t> keys;      // [cap_px]
-    gator::DevBuf<int32_t> tab;        // [cap_tab]  mesh_img [M] | mesh_slot [M] | img_off [N+1] | mesh_of [M]
-    gator::DevBuf<int32_t, true> tab_host;   // [cap_tab_host]  pinned staging of tab: built here, copied on the call's stream
-    hipEvent_t tab_copied = nullptr;   // recorded behind that copy; the next call waits for it before it rewrites the staging
-    size_t cap_xy = 0, cap_z = 0, cap_nrm = 0, cap_px = 0, cap_tab = 0, cap_tab_host = 0;
-    int64_t allocations = 0, bytes = 0;
+    // workspace of gator_render_f32, grown when a larger call arrives (gator::Handle::grow)
+    gator::WorkBuf<int32_t> xy;        // [M][V][2]
+    gator::WorkBuf<float> z;           // [M][V]
+    gator::WorkBuf<float> nrm;         // [M][V][3]
+    gator::WorkBuf<uint64_t> keys;     // [N][H][W]
+    gator::StagedTable<int32_t> tab;   // the image tables of every entry point: mesh_img [M] | mesh_slot [M] | img_off [N+1] | mesh_of [M]
 };
 
 namespace gator {
@@ -260,28 +254,6 @@ __global__ __launch_bounds__(256) void k_render_resolve(const uint64_t* __restri
     }
 }
 
-// alloc() frees the old block before it asks for the new one, so the capacity is 0 from that moment until the new block is there: a
-// failed growth leaves an empty buffer that the next call grows again, never a capacity without a block behind it.
-template <class T, bool P> int grow(gator_renderer* h, DevBuf<T, P>& buf, size_t& cap, size_t need, size_t per) {
-    if (need <= cap) return GATOR_OK;
-    GATOR_HIP_CHECK(hipDeviceSynchronize());          // queued work may still read the block that is replaced
-    h->bytes -= (int64_t)(cap * per * sizeof(T));
-    cap = 0;
-    GATOR_TRY(buf.alloc(need * per * sizeof(T)));
-    h->bytes += (int64_t)(need * per * sizeof(T));
-    h->allocations += 1;
-    cap = need;
-    return GATOR_OK;
-}
-
-int check_handle(const gator_renderer* h, const char* who) {
-    if (!h) return fail(GATOR_EINVAL, "%s: null handle", who);
-    int dev = 0;
-    GATOR_HIP_CHECK(hipGetDevice(&dev));
-    if (dev != h->device) return fail(GATOR_EINVAL, "%s: the renderer lives on device %d, the current device is %d", who, h->device, dev);
-    return GATOR_OK;
-}
-
 int check_shape(const gator_renderer* h, const char* who, int n_meshes, int n_images, int H, int W) {
     if (n_meshes < 1 || n_images < 1) return fail(GATOR_EINVAL, "%s: n_meshes and n_images must be >= 1", who);
     if (H < 1 || H > kMaxSide || W < 1 || W > kMaxSide) return fail(GATOR_EINVAL, "%s: H and W must be 1..%d", who, kMaxSide);
@@ -291,37 +263,26 @@ int check_shape(const gator_renderer* h, const char* who, int n_meshes, int n_im
     return GATOR_OK;
 }
 
-// Validates image_index (host, or NULL: mesh m is drawn alone into image m), numbers the meshes of every image (slot = rank of the mesh
-// among those of its image, in mesh order) and uploads the tables.  max_id_bits: 32 for the visibility key, 31 when face ids go out as int32.
+// image_index (host, or NULL: mesh m is drawn alone into image m) through image_groups.h (slot = rank of the mesh among those of its
+// image, in mesh order), the id limit, the upload.  ids_out: face ids go out as int32, so an id has 31 bits and not the visibility key's 32.
 int make_tables(gator_renderer* h, const char* who, const int32_t* image_index, int M, int N, bool ids_out, hipStream_t st, Tables* tb) {
     *tb = Tables{nullptr, nullptr, nullptr, nullptr};
-    const uint64_t id_limit = ids_out ? (1ull << 31) : (1ull << 32);
-    if (!image_index) {
-        if (M > N) return fail(GATOR_EINVAL, "%s: image_index is NULL, so mesh m goes into image m, but n_meshes %d > n_images %d", who, M, N);
-        if ((uint64_t)h->F >= id_limit) return fail(GATOR_EINVAL, "%s: max_meshes_per_image * n_faces must be below 2^%d", who, ids_out ? 31 : 32);
-        return GATOR_OK;
-    }
-    for (int m = 0; m < M; ++m)
-        if (image_index[m] < 0 || image_index[m] >= N)
-            return fail(GATOR_EINVAL, "%s: image_index[%d] = %d outside 0..%d", who, m, image_index[m], N - 1);
     const size_t count = (size_t)3 * M + N + 1;
-    GATOR_HIP_CHECK(hipEventSynchronize(h->tab_copied));      // the last call's copy has read the staging
-    GATOR_TRY(grow(h, h->tab_host, h->cap_tab_host, count, 1));
-    int32_t *mesh_img = h->tab_host.get(), *mesh_slot = mesh_img + M, *img_off = mesh_slot + M, *mesh_of = img_off + N + 1;
-    std::memset(mesh_img, 0, count * sizeof(int32_t));
-    for (int m = 0; m < M; ++m) {
-        mesh_img[m] = image_index[m];
-        mesh_slot[m] = img_off[image_index[m] + 1]++;
+    int32_t* t = nullptr;
+    ImageGroups g = image_groups(nullptr, M, N, nullptr, nullptr, nullptr);
+    if (image_index) {
+        GATOR_TRY(h->tab.stage(h, count, &t));
+        g = image_groups(image_index, M, N, t + 2 * (size_t)M, t + 2 * (size_t)M + N + 1, t + M);
     }
-    int32_t most = 0;
-    for (int n = 0; n < N; ++n) { most = std::max(most, img_off[n + 1]); img_off[n + 1] += img_off[n]; }
-    if ((uint64_t)most * (uint64_t)h->F >= id_limit)
-        return fail(GATOR_EINVAL, "%s: max_meshes_per_image * n_faces = %d * %d must be below 2^%d", who, most, h->F, ids_out ? 31 : 32);
-    for (int m = 0; m < M; ++m) mesh_of[img_off[mesh_img[m]] + mesh_slot[m]] = m;
-    GATOR_TRY(grow(h, h->tab, h->cap_tab, count, 1));
-    GATOR_HIP_CHECK(hipMemcpyAsync(h->tab.get(), mesh_img, count * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    GATOR_HIP_CHECK(hipEventRecord(h->tab_copied, st));
-    const int32_t* d = h->tab.get();
+    if (g.error == ImageGroups::kNullTooMany)
+        return fail(GATOR_EINVAL, "%s: image_index is NULL, so mesh m goes into image m, but n_meshes %d > n_images %d", who, M, N);
+    if (g.error) return fail(GATOR_EINVAL, "%s: image_index[%d] = %d outside 0..%d", who, g.at, g.value, N - 1);
+    if ((uint64_t)g.most * (uint64_t)h->F >= (ids_out ? 1ull << 31 : 1ull << 32))
+        return fail(GATOR_EINVAL, "%s: max_meshes_per_image * n_faces = %d * %d must be below 2^%d", who, g.most, h->F, ids_out ? 31 : 32);
+    if (!image_index) return GATOR_OK;
+    std::memcpy(t, image_index, (size_t)M * sizeof(int32_t));      // mesh_img
+    const int32_t* d = nullptr;
+    GATOR_TRY(h->tab.upload(h, count, st, &d));
     *tb = Tables{d, d + M, d + 2 * (size_t)M, d + 2 * (size_t)M + N + 1};
     return GATOR_OK;
 }
@@ -403,11 +364,8 @@ extern "C" int gator_renderer_create(const int32_t* faces, int32_t n_faces, int3
                 for (int q = 0; q < 3; ++q) slot[q] = faces[(size_t)f * 3 + q];
             }
     }
-    gator_renderer* h = new gator_renderer;
-    h->F = n_faces; h->V = n_verts; h->small_box = kSmallBoxPixels;
-    auto build = [&]() -> int {
-        GATOR_HIP_CHECK(hipGetDevice(&h->device));
-        GATOR_HIP_CHECK(hipEventCreateWithFlags(&h->tab_copied, hipEventDisableTiming));
+    return create_handle(out, [&](gator_renderer* h) -> int {
+        h->F = n_faces; h->V = n_verts; h->small_box = kSmallBoxPixels;
         GATOR_TRY(h->faces.alloc((size_t)n_faces * 3 * sizeof(int32_t)));
         GATOR_TRY(h->vf_off.alloc(off.size() * sizeof(int32_t)));
         GATOR_TRY(h->vf.alloc(vf.size() * sizeof(int32_t)));
@@ -415,26 +373,13 @@ extern "C" int gator_renderer_create(const int32_t* faces, int32_t n_faces, int3
         GATOR_HIP_CHECK(hipMemcpy(h->vf_off.get(), off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         GATOR_HIP_CHECK(hipMemcpy(h->vf.get(), vf.data(), vf.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         return GATOR_OK;
-    };
-    const int rc = build();
-    if (rc != GATOR_OK) { delete h; return rc; }
-    *out = h;
-    return GATOR_OK;
+    });
 }
 
-extern "C" int gator_renderer_destroy(gator_renderer* h) {
-    if (!h) return GATOR_OK;
-    (void)hipDeviceSynchronize();
-    delete h;
-    return GATOR_OK;
-}
+extern "C" int gator_renderer_destroy(gator_renderer* h) { return gator::destroy_handle(h); }
 
 extern "C" int gator_renderer_workspace(const gator_renderer* h, int64_t* bytes, int64_t* allocations) {
-    using namespace gator;
-    if (!h) return fail(GATOR_EINVAL, "gator_renderer_workspace: null handle");
-    if (bytes) *bytes = h->bytes;
-    if (allocations) *allocations = h->allocations;
-    return GATOR_OK;
+    return gator::handle_workspace(h, "gator_renderer_workspace", bytes, allocations);
 }
 
 extern "C" int gator_renderer_set_small_box(gator_renderer* h, int32_t pixels) {
@@ -504,10 +449,10 @@ extern "C" int gator_render_f32(gator_renderer* h, const float* verts, const flo
     Tables tb;
     GATOR_TRY(make_tables(h, who, image_index, n_meshes, n_images, out_face_id != nullptr, st, &tb));
     const size_t mv = (size_t)n_meshes * h->V, px = (size_t)n_images * H * W;
-    GATOR_TRY(grow(h, h->xy, h->cap_xy, mv, 2));
-    GATOR_TRY(grow(h, h->z, h->cap_z, mv, 1));
-    GATOR_TRY(grow(h, h->nrm, h->cap_nrm, mv, 3));
-    GATOR_TRY(grow(h, h->keys, h->cap_px, px, 1));
+    GATOR_TRY(h->grow(h->xy, mv * 2));
+    GATOR_TRY(h->grow(h->z, mv));
+    GATOR_TRY(h->grow(h->nrm, mv * 3));
+    GATOR_TRY(h->grow(h->keys, px));
     GATOR_TRY(launch_vertices(h, verts, cams, n_meshes, H, W, A, h->xy, h->z, h->nrm, st));
     GATOR_TRY(launch_raster(h, h->xy, h->z, tb, n_meshes, n_images, H, W, flags, h->keys, st));
     return launch_resolve(h, h->keys, h->xy, h->nrm, colors, tb, background, n_images, H, W, L, out_rgb, out_face_id, out_depth, st);

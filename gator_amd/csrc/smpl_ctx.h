@@ -5,34 +5,34 @@
 
 #include <cstdint>
 
-#include "internal.h"
+#include "handle.h"
 
 namespace gator {
 constexpr int kSmplMaxJ = 32, kSmplMaxB = 16;
 constexpr int kTV = 128;     // vertices per tile of the layer: four waves of 32 columns; the vertex planes are padded to whole tiles
 }  // namespace gator
 
-struct gator_smpl {
-    int device = 0, NV = 0, NJ = 0, NB = 0, K = 0, Kp = 0, NVp = 0, MI = 0;
+struct gator_smpl : gator::Handle {
+    int NV = 0, NJ = 0, NB = 0, K = 0, Kp = 0, NVp = 0, MI = 0;
     gator::DevBuf<float> basis;      // [3][Kp][NVp]  coordinate planes of [shapedirs | posedirs], zero padded
     gator::DevBuf<float> vtempl;     // [3][NVp]
     gator::DevBuf<int32_t> widx;     // [MI][NVp]     skinning influences of a vertex: joint index ...
     gator::DevBuf<float> wval;       // [MI][NVp]     ... and weight (0 in unused slots)
     gator::DevBuf<double> jfold;     // [NJ*3][1+NB]  J_regressor . v_template, J_regressor . shapedirs (folded in fp64)
     gator::DevBuf<int32_t> parents;  // [NJ]
-    // workspace of the forward, grown when a larger batch arrives
-    gator::DevBuf<float> coef;       // [cap][Kp]
-    gator::DevBuf<float> xform;      // [cap][NJ][12]
-    gator::DevBuf<float> offs;       // [cap][4]
+    // workspace of the forward, grown when a larger batch arrives (gator::Handle::grow per buffer; cap is the batch all three hold)
+    gator::WorkBuf<float> coef;      // [cap][Kp]
+    gator::WorkBuf<float> xform;     // [cap][NJ][12]
+    gator::WorkBuf<float> offs;      // [cap][4]
     int cap = 0;
     // the fit: model side (folded at create), then its workspace, grown like the forward's
     gator::DevBuf<uint32_t> amask;   // [MI][NVp]     bit k: joint k is the influence's joint or one of its ancestors (MI <= 4 only)
     double tcen[3] = {0, 0, 0};      // centroid of v_template
-    gator::DevBuf<float> fjoints;    // [fcap][NJ][3] posed joints of the candidate
-    gator::DevBuf<float> fstate;     // [2][fcap][P]  candidate, current: pose | betas | trans, three arrays each
-    gator::DevBuf<double> fscal;     // [fcap][4]     lambda, squared error of the current state, bad-sample flag
-    gator::DevBuf<float> fpart;      // [fcap][S][pairs][32][32] per-chunk partial sums of M's upper tiles
-    gator::DevBuf<float> fM;         // [2][fcap][N][N] M of the candidate, of the current state
+    gator::WorkBuf<float> fjoints;   // [fcap][NJ][3] posed joints of the candidate
+    gator::WorkBuf<float> fstate;    // [2][fcap][P]  candidate, current: pose | betas | trans, three arrays each
+    gator::WorkBuf<double> fscal;    // [fcap][4]     lambda, squared error of the current state, bad-sample flag
+    gator::WorkBuf<float> fpart;     // [fcap][S][pairs][32][32] per-chunk partial sums of M's upper tiles
+    gator::WorkBuf<float> fM;        // [2][fcap][N][N] M of the candidate, of the current state
     int fcap = 0;
 };
 
@@ -53,7 +53,8 @@ __device__ inline void smpl_rodrigues(double ax, double ay, double az, double* r
 }
 
 int smpl_reserve(gator_smpl* c, int B);                                  // the forward's workspace for a batch of B
-// k_smpl_pose on the ctx's workspace (coefficient rows, skinning transforms, offsets), no centring, scale 1
-int smpl_pose_stage(gator_smpl* c, const float* pose, const float* betas, const float* trans, int batch, float* joints, hipStream_t st);
+// k_smpl_pose on the ctx's workspace (coefficient rows, skinning transforms, offsets); center < 0: no centring
+int smpl_pose_stage(gator_smpl* c, const float* pose, const float* betas, const float* trans, int batch, int center, double out_scale,
+                    float* joints, hipStream_t st);
 int smpl_fit_build(gator_smpl* c, const gator_smpl_model* m);            // smpl_fit.hip: the fit's share of gator_smpl_create
 }  // namespace gator

@@ -431,16 +431,15 @@ FitState fit_state(const gator_smpl* c, int which) {
 int fit_reserve(gator_smpl* c, int B) {
     GATOR_TRY(smpl_reserve(c, B));
     if (B <= c->fcap) return GATOR_OK;
-    if (c->fcap) GATOR_HIP_CHECK(hipDeviceSynchronize());       // queued fits may still read the buffers that are replaced
     c->fcap = 0;
     int P, NT, S;
     fit_sizes(c, &P, &NT, &S);
     const size_t N = 32 * (size_t)NT;
-    GATOR_TRY(c->fjoints.alloc(sizeof(float) * (size_t)B * c->NJ * 3));
-    GATOR_TRY(c->fstate.alloc(sizeof(float) * 2 * (size_t)B * P));
-    GATOR_TRY(c->fscal.alloc(sizeof(double) * (size_t)B * 4));
-    GATOR_TRY(c->fpart.alloc(sizeof(float) * (size_t)B * S * fit_pairs(NT) * 1024));
-    GATOR_TRY(c->fM.alloc(sizeof(float) * 2 * (size_t)B * N * N));
+    GATOR_TRY(c->grow(c->fjoints, (size_t)B * c->NJ * 3));
+    GATOR_TRY(c->grow(c->fstate, 2 * (size_t)B * P));
+    GATOR_TRY(c->grow(c->fscal, (size_t)B * 4));
+    GATOR_TRY(c->grow(c->fpart, (size_t)B * S * fit_pairs(NT) * 1024));
+    GATOR_TRY(c->grow(c->fM, 2 * (size_t)B * N * N));
     c->fcap = B;
     return GATOR_OK;
 }
@@ -458,7 +457,7 @@ int launch_normal(gator_smpl* c, const float* trans, const float* target, int ba
 int fit_normal(gator_smpl* c, const float* pose, const float* betas, const float* trans, const float* target, int batch, float* M, hipStream_t st) {
     int P, NT, S;
     fit_sizes(c, &P, &NT, &S);
-    GATOR_TRY(smpl_pose_stage(c, pose, betas, nullptr, batch, c->fjoints, st));
+    GATOR_TRY(smpl_pose_stage(c, pose, betas, nullptr, batch, -1, 1.0, c->fjoints, st));
     switch (NT) {
         case 1: GATOR_TRY(launch_normal<1>(c, trans, target, batch, S, P, st)); break;
         case 2: GATOR_TRY(launch_normal<2>(c, trans, target, batch, S, P, st)); break;
@@ -471,13 +470,10 @@ int fit_normal(gator_smpl* c, const float* pose, const float* betas, const float
 }
 
 int fit_common_checks(const char* who, gator_smpl* ctx, int batch) {
-    if (!ctx) return fail(GATOR_EINVAL, "%s: null ctx", who);
+    GATOR_TRY(check_handle(ctx, who, "ctx"));
     if (batch < 0 || batch > kFitMaxBatch) return fail(GATOR_EINVAL, "%s: batch %d outside 0..%d", who, batch, kFitMaxBatch);
     if (ctx->MI > 4)
         return fail(GATOR_EUNSUPPORTED, "%s: the model has up to %d influences per vertex, the fit supports at most 4", who, ctx->MI);
-    int dev = 0;
-    GATOR_HIP_CHECK(hipGetDevice(&dev));
-    if (dev != ctx->device) return fail(GATOR_EINVAL, "%s: the ctx lives on device %d, the current device is %d", who, ctx->device, dev);
     return GATOR_OK;
 }
 }  // namespace

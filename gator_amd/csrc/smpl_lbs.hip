@@ -262,18 +262,18 @@ int smpl_build(gator_smpl* c, const gator_smpl_model* m) {
 
 int smpl_reserve(gator_smpl* c, int B) {
     if (B <= c->cap) return GATOR_OK;
-    if (c->cap) GATOR_HIP_CHECK(hipDeviceSynchronize());       // queued forwards may still read the buffers that are replaced
     c->cap = 0;
-    GATOR_TRY(c->coef.alloc(sizeof(float) * (size_t)B * c->Kp));
-    GATOR_TRY(c->xform.alloc(sizeof(float) * (size_t)B * c->NJ * 12));
-    GATOR_TRY(c->offs.alloc(sizeof(float) * (size_t)B * 4));
+    GATOR_TRY(c->grow(c->coef, (size_t)B * c->Kp));
+    GATOR_TRY(c->grow(c->xform, (size_t)B * c->NJ * 12));
+    GATOR_TRY(c->grow(c->offs, (size_t)B * 4));
     c->cap = B;
     return GATOR_OK;
 }
 
-int smpl_pose_stage(gator_smpl* c, const float* pose, const float* betas, const float* trans, int batch, float* joints, hipStream_t st) {
-    k_smpl_pose<<<batch, 64, 0, st>>>(pose, c->NB ? betas : nullptr, trans, c->jfold, c->parents, c->NJ, c->NB, c->K, c->Kp, -1, 1.0,
-                                      c->coef, c->xform, c->offs, joints);
+int smpl_pose_stage(gator_smpl* c, const float* pose, const float* betas, const float* trans, int batch, int center, double out_scale,
+                    float* joints, hipStream_t st) {
+    k_smpl_pose<<<batch, 64, 0, st>>>(pose, c->NB ? betas : nullptr, trans, c->jfold, c->parents, c->NJ, c->NB, c->K, c->Kp, center < 0 ? -1 : center,
+                                      out_scale, c->coef, c->xform, c->offs, joints);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;
 }
@@ -283,8 +283,7 @@ extern "C" int gator_smpl_create(const gator_smpl_model* m, gator_smpl** out) {
     using namespace gator;
     if (!m || !out) return fail(GATOR_EINVAL, "gator_smpl_create: null argument");
     *out = nullptr;
-    if (m->struct_size != (int32_t)sizeof(gator_smpl_model))
-        return fail(GATOR_EINVAL, "gator_smpl_create: struct_size %d, this library's gator_smpl_model has %d bytes", m->struct_size, (int)sizeof(gator_smpl_model));
+    GATOR_TRY(check_struct_size("gator_smpl_create", "gator_smpl_model", m->struct_size, sizeof(gator_smpl_model)));
     if (m->n_verts < 1 || m->n_verts > (1 << 24)) return fail(GATOR_EINVAL, "gator_smpl_create: n_verts %d outside 1..%d", m->n_verts, 1 << 24);
     if (m->n_joints < 2 || m->n_joints > kSmplMaxJ) return fail(GATOR_EINVAL, "gator_smpl_create: n_joints %d outside 2..%d", m->n_joints, kSmplMaxJ);
     if (m->n_betas < 0 || m->n_betas > kSmplMaxB) return fail(GATOR_EINVAL, "gator_smpl_create: n_betas %d outside 0..%d", m->n_betas, kSmplMaxB);
@@ -293,27 +292,17 @@ extern "C" int gator_smpl_create(const gator_smpl_model* m, gator_smpl** out) {
     for (int j = 1; j < m->n_joints; ++j)
         if (m->parents[j] < 0 || m->parents[j] >= j)
             return fail(GATOR_EINVAL, "gator_smpl_create: parents[%d] = %d, a parent must precede its joint", j, m->parents[j]);
-    gator_smpl* c = new gator_smpl;
-    c->NV = m->n_verts; c->NJ = m->n_joints; c->NB = m->n_betas;
-    c->K = c->NB + (c->NJ - 1) * 9;
-    c->Kp = (c->K + 4 * kKU - 1) / (4 * kKU) * (4 * kKU);
-    c->NVp = (c->NV + kTV - 1) / kTV * kTV;
-    int rc = GATOR_OK;
-    const hipError_t e = hipGetDevice(&c->device);
-    if (e != hipSuccess) rc = fail(GATOR_EHIP, "gator_smpl_create: no HIP device available: %s", hipGetErrorString(e));
-    if (rc == GATOR_OK) rc = smpl_build(c, m);
-    if (rc == GATOR_OK) rc = smpl_fit_build(c, m);
-    if (rc != GATOR_OK) { delete c; return rc; }
-    *out = c;
-    return GATOR_OK;
+    return create_handle(out, [&](gator_smpl* c) -> int {
+        c->NV = m->n_verts; c->NJ = m->n_joints; c->NB = m->n_betas;
+        c->K = c->NB + (c->NJ - 1) * 9;
+        c->Kp = (c->K + 4 * kKU - 1) / (4 * kKU) * (4 * kKU);
+        c->NVp = (c->NV + kTV - 1) / kTV * kTV;
+        GATOR_TRY(smpl_build(c, m));
+        return smpl_fit_build(c, m);
+    });
 }
 
-extern "C" int gator_smpl_destroy(gator_smpl* ctx) {
-    if (!ctx) return GATOR_OK;
-    (void)hipDeviceSynchronize();
-    delete ctx;
-    return GATOR_OK;
-}
+extern "C" int gator_smpl_destroy(gator_smpl* ctx) { return gator::destroy_handle(ctx); }
 
 extern "C" int gator_smpl_workspace(const gator_smpl* ctx, const void** base, int64_t* capacity) {
     using namespace gator;
@@ -327,21 +316,16 @@ extern "C" int gator_smpl_forward_f32(gator_smpl* ctx, const float* pose, const 
                                       int32_t center_idx, float out_scale, float* verts, float* joints, void* stream) {
     using namespace gator;
     if (center_idx >= 0 && trans) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: center_idx goes with trans = NULL (the layer centres only an untranslated batch)");
-    if (!ctx) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: null ctx");
+    GATOR_TRY(check_handle(ctx, "gator_smpl_forward_f32", "ctx"));
     if (batch < 0 || (batch > 0 && !pose)) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: bad pose / batch");
     if (center_idx >= ctx->NJ) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: center_idx %d, the model has %d joints", center_idx, ctx->NJ);
     if (!std::isfinite(out_scale)) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: out_scale must be finite");
     const int tiles = (batch + kTS - 1) / kTS;
     if (tiles > 65535) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: batch %d above %d", batch, 65535 * kTS);
     if (batch == 0) return GATOR_OK;
-    int dev = 0;
-    GATOR_HIP_CHECK(hipGetDevice(&dev));
-    if (dev != ctx->device) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: the ctx lives on device %d, the current device is %d", ctx->device, dev);
     GATOR_TRY(smpl_reserve(ctx, batch));
     hipStream_t st = (hipStream_t)stream;
-    k_smpl_pose<<<batch, 64, 0, st>>>(pose, ctx->NB ? betas : nullptr, trans, ctx->jfold, ctx->parents, ctx->NJ, ctx->NB, ctx->K, ctx->Kp,
-                                      center_idx < 0 ? -1 : center_idx, (double)out_scale, ctx->coef, ctx->xform, ctx->offs, joints);
-    GATOR_HIP_CHECK(hipGetLastError());
+    GATOR_TRY(smpl_pose_stage(ctx, pose, betas, trans, batch, center_idx, (double)out_scale, joints, st));
     if (verts) {
         const dim3 grid(ctx->NVp / kTV, tiles);
         const size_t lds = skin_lds_bytes(ctx);

@@ -22,7 +22,8 @@
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
-#include "procrustes.h"      // wave_sum
+#include "handle.h"          // check_struct_size
+#include "procrustes.h"      // wave_sum, coo_ok
 #include "so3.h"             // rotvec_exp, rotmat_log
 
 namespace gator {
@@ -249,8 +250,6 @@ __global__ __launch_bounds__(kCamThreads) void k_camera_targets(const gator_came
     }
 }
 
-bool cam_coo_ok(const gator_coo& g) { return g.nnz >= 0 && (g.nnz == 0 || (g.row && g.col && g.val)); }
-
 }  // namespace
 }  // namespace gator
 
@@ -275,22 +274,21 @@ extern "C" int gator_camera_targets_f32(const gator_camera_targets_args* args, v
     using namespace gator;
     const char* who = "gator_camera_targets_f32";
     if (!args) return fail(GATOR_EINVAL, "%s: null args", who);
-    if (args->struct_size != (int32_t)sizeof(gator_camera_targets_args))
-        return fail(GATOR_EINVAL, "%s: struct_size %d, this library's is %zu", who, args->struct_size, sizeof(gator_camera_targets_args));
+    GATOR_TRY(check_struct_size(who, "gator_camera_targets_args", args->struct_size, sizeof(gator_camera_targets_args)));
     const gator_camera_targets_args& a = *args;
     if (a.batch < 0) return fail(GATOR_EINVAL, "%s: batch %d", who, a.batch);
     if (a.n_verts < 1) return fail(GATOR_EINVAL, "%s: n_verts %d (at least 1)", who, a.n_verts);
     if (a.n_smpl_joints < 1 || a.root_idx < 0 || a.root_idx >= a.n_smpl_joints)
         return fail(GATOR_EINVAL, "%s: root_idx %d outside [0, %d)", who, a.root_idx, a.n_smpl_joints);
     if (a.lift_set != GATOR_LIFT_HUMAN36 && a.lift_set != GATOR_LIFT_COCO) return fail(GATOR_EINVAL, "%s: lift_set %d (0 human36, 1 coco)", who, a.lift_set);
-    if (!cam_coo_ok(a.reg_h36m) || a.reg_h36m.n_joint < 1 || a.reg_h36m.n_joint > kCamMaxJoints)
+    if (!coo_ok(a.reg_h36m) || a.reg_h36m.n_joint < 1 || a.reg_h36m.n_joint > kCamMaxJoints)
         return fail(GATOR_EINVAL, "%s: reg_h36m (nnz >= 0 with its arrays, 1..%d joints)", who, kCamMaxJoints);
     if (a.reg_h36m_n_verts != a.n_verts)
         return fail(GATOR_EINVAL, "%s: reg_h36m over %d vertices, meshes of %d", who, a.reg_h36m_n_verts, a.n_verts);
     const bool has_coco = a.reg_coco.n_joint != 0;
     if (a.lift_set == GATOR_LIFT_COCO && !has_coco) return fail(GATOR_EINVAL, "%s: lift_set coco without reg_coco", who);
     if (has_coco) {
-        if (!cam_coo_ok(a.reg_coco) || a.reg_coco.n_joint < 13 || a.reg_coco.n_joint > kCamMaxJoints - 2)
+        if (!coo_ok(a.reg_coco) || a.reg_coco.n_joint < 13 || a.reg_coco.n_joint > kCamMaxJoints - 2)
             return fail(GATOR_EINVAL, "%s: reg_coco (nnz >= 0 with its arrays, 13..%d joints: pelvis and neck come from joints 5, 6, 11, 12)", who,
                         kCamMaxJoints - 2);
         if (a.reg_coco_n_verts != a.n_verts)

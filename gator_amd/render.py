@@ -10,7 +10,6 @@
 Geometry, visibility and the compositing rule are the reference's (pyrender through a weak-perspective camera).  The LIGHTING is a documented
 diffuse model with the reference's scene parameters, lin = base * (ambient + (1/pi) * sum_k I_k * max(0, n . l_k)), out = lin ** (1/2.2):
 colour parity with pyrender's shader is not claimed and not measured."""
-import ctypes
 import math
 
 import numpy as np
@@ -45,7 +44,9 @@ def demo_rotation(angle=None, axis=None, rotate=False):
     return R
 
 
-class MeshRenderer:
+class MeshRenderer(_lib.DeviceHandle):
+    PREFIX = 'gator_renderer'
+
     def __init__(self, faces, device='cuda:0', n_verts=None):
         """faces [F,3] integer vertex indices (numpy or tensor); n_verts defaults to the largest index + 1."""
         f = np.ascontiguousarray(np.asarray(faces.cpu() if torch.is_tensor(faces) else faces).astype(np.int64))
@@ -53,32 +54,10 @@ class MeshRenderer:
             raise ValueError('MeshRenderer: faces must be [F,3], got %s' % (f.shape,))
         if f.size and (f.min() < -2 ** 31 or f.max() >= 2 ** 31):
             raise ValueError('MeshRenderer: a face index does not fit int32')
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('MeshRenderer: the device must be a HIP device (there is no CPU path)')
-        if self.device.index is None:       # tensors report their device with its index
-            self.device = torch.device('cuda', torch.cuda.current_device())
         self.n_faces = int(f.shape[0])
         self.n_verts = int(n_verts) if n_verts is not None else (int(f.max()) + 1 if f.size else 0)
         self._faces = f.astype(np.int32)
-        self._h = ctypes.c_void_p()
-        self._lib = _lib.load()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.gator_renderer_create(self._faces.ctypes.data_as(ctypes.c_void_p), self.n_faces, self.n_verts, ctypes.byref(self._h)),
-                       'gator_renderer_create')
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            self._lib.gator_renderer_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    __del__ = close
-
-    def workspace(self):
-        """(bytes held, allocations made since create) -- the test hook of the C ABI."""
-        b, n = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(self._lib.gator_renderer_workspace(self._h, ctypes.byref(b), ctypes.byref(n)), 'gator_renderer_workspace')
-        return b.value, n.value
+        self._create(device, _lib.host_ptr(self._faces), self.n_faces, self.n_verts)
 
     def set_small_box(self, pixels):
         _lib.check(self._lib.gator_renderer_set_small_box(self._h, int(pixels)), 'gator_renderer_set_small_box')
@@ -111,10 +90,10 @@ class MeshRenderer:
     def _index(image_index, M):
         if image_index is None:
             return None
-        idx = np.ascontiguousarray(np.asarray(image_index.cpu() if torch.is_tensor(image_index) else image_index).astype(np.int64))
+        idx = _lib.host_index(image_index)
         if idx.shape != (M,):
             raise ValueError('image_index must have one entry per mesh (%d), got %s' % (M, idx.shape))
-        return np.clip(idx, -1, 2 ** 31 - 1).astype(np.int32)       # out-of-range stays out of range for the C ABI's check
+        return idx
 
     @staticmethod
     def _lights(lights):
@@ -148,7 +127,7 @@ class MeshRenderer:
         n = torch.empty((M, self.n_verts, 3), device=self.device, dtype=torch.float32)
         r = self._rot(rot)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.gator_render_vertices_f32(self._h, _lib.ptr(v), _lib.ptr(c), M, int(H), int(W), r.ctypes.data_as(ctypes.c_void_p) if r is not None else None,
+            _lib.check(self._lib.gator_render_vertices_f32(self._h, _lib.ptr(v), _lib.ptr(c), M, int(H), int(W), _lib.host_ptr(r),
                                                            _lib.ptr(xy), _lib.ptr(z), _lib.ptr(n), _lib.stream_ptr(self.device)), 'gator_render_vertices_f32')
         return xy, z, n
 
@@ -163,7 +142,7 @@ class MeshRenderer:
         N = int(n_images) if n_images is not None else M
         keys = torch.empty((max(N, 0), max(int(H), 0), max(int(W), 0)), device=self.device, dtype=torch.int64)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.gator_render_raster(self._h, _lib.ptr(xy), _lib.ptr(zz), idx.ctypes.data_as(ctypes.c_void_p) if idx is not None else None,
+            _lib.check(self._lib.gator_render_raster(self._h, _lib.ptr(xy), _lib.ptr(zz), _lib.host_ptr(idx),
                                                      M, N, int(H), int(W), CULL_BACKFACES if cull_backfaces else 0, _lib.ptr(keys), _lib.stream_ptr(self.device)),
                        'gator_render_raster')
         return keys
@@ -185,8 +164,8 @@ class MeshRenderer:
         dep = torch.empty((N, H, W), device=self.device, dtype=torch.float32) if return_depth else None
         with torch.cuda.device(self.device):
             _lib.check(self._lib.gator_render_resolve(self._h, _lib.ptr(kk), _lib.ptr(xy), _lib.ptr(nn), _lib.ptr(col),
-                                                      idx.ctypes.data_as(ctypes.c_void_p) if idx is not None else None, M, _lib.ptr(bg), N, H, W,
-                                                      L.ctypes.data_as(ctypes.c_void_p), L.shape[0], float(ambient), _lib.ptr(rgb), _lib.ptr(fid), _lib.ptr(dep),
+                                                      _lib.host_ptr(idx), M, _lib.ptr(bg), N, H, W,
+                                                      _lib.host_ptr(L), L.shape[0], float(ambient), _lib.ptr(rgb), _lib.ptr(fid), _lib.ptr(dep),
                                                       _lib.stream_ptr(self.device)), 'gator_render_resolve')
         out = (rgb,) + ((fid,) if return_face_id else ()) + ((dep,) if return_depth else ())
         return out[0] if len(out) == 1 else out
@@ -205,9 +184,9 @@ class MeshRenderer:
         fid = torch.empty(rgb.shape[:3], device=self.device, dtype=torch.int32) if return_face_id else None
         dep = torch.empty(rgb.shape[:3], device=self.device, dtype=torch.float32) if return_depth else None
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.gator_render_f32(self._h, _lib.ptr(v), _lib.ptr(c), _lib.ptr(col), idx.ctypes.data_as(ctypes.c_void_p) if idx is not None else None, M,
-                                                  _lib.ptr(bg), N, H, W, r.ctypes.data_as(ctypes.c_void_p) if r is not None else None,
-                                                  L.ctypes.data_as(ctypes.c_void_p), L.shape[0], float(ambient), CULL_BACKFACES if cull_backfaces else 0,
+            _lib.check(self._lib.gator_render_f32(self._h, _lib.ptr(v), _lib.ptr(c), _lib.ptr(col), _lib.host_ptr(idx), M,
+                                                  _lib.ptr(bg), N, H, W, _lib.host_ptr(r),
+                                                  _lib.host_ptr(L), L.shape[0], float(ambient), CULL_BACKFACES if cull_backfaces else 0,
                                                   _lib.ptr(rgb), _lib.ptr(fid), _lib.ptr(dep), _lib.stream_ptr(self.device)), 'gator_render_f32')
         out = (rgb,) + ((fid,) if return_face_id else ()) + ((dep,) if return_depth else ())
         return out[0] if len(out) == 1 else out

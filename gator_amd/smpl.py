@@ -55,10 +55,13 @@ def read_pkl(path):
         return model_arrays(pickle.load(fh, encoding='latin1'))
 
 
-class SMPLLayer:
+class SMPLLayer(_lib.DeviceHandle):
     """smplpytorch's SMPL_Layer, forward only, on one HIP device.  Same call order (pose, betas, trans), the same center_idx
     attribute, th_faces / th_J_regressor / th_weights / kintree_parents as the reference layer exposes them.  out_scale multiplies
     the (translated or centred) outputs: 1000 for the datasets' millimetres."""
+    PREFIX = 'gator_smpl'
+    NO_CPU = 'the layer runs on a HIP device (there is no CPU path)'
+    _ctx = property(lambda self: self._h)      # the C ABI's name for this handle
 
     def __init__(self, v_template, shapedirs, posedirs, weights, J_regressor, parents, faces=None, center_idx=None, device='cuda',
                  out_scale=1.0, gender='neutral'):
@@ -73,11 +76,6 @@ class SMPLLayer:
             raise ValueError('SMPLLayer: inconsistent model shapes: v_template %s shapedirs %s posedirs %s weights %s J_regressor %s parents %s'
                              % (vt.shape, sd.shape, pd.shape, w.shape, jr.shape, par.shape))
         par32 = np.ascontiguousarray(np.where((par < 0) | (par >= 2 ** 31), -1, par).astype(np.int32))
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('SMPLLayer: the layer runs on a HIP device (there is no CPU path)')
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
         self.num_verts, self.num_joints, self.num_betas = nv, nj, sd.shape[2]
         self.center_idx, self.out_scale, self.gender = center_idx, float(out_scale), gender
         self.kintree_parents = [int(p) for p in par]
@@ -87,9 +85,7 @@ class SMPLLayer:
         self.th_v_template = torch.from_numpy(vt).unsqueeze(0)
         model = _lib.SmplModel(ctypes.sizeof(_lib.SmplModel), nv, nj, sd.shape[2], vt.ctypes.data, sd.ctypes.data if sd.size else None,
                                pd.ctypes.data, w.ctypes.data, jr.ctypes.data, par32.ctypes.data)
-        self._ctx = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().gator_smpl_create(ctypes.byref(model), ctypes.byref(self._ctx)), 'gator_smpl_create')
+        self._create(device, ctypes.byref(model))
 
     @classmethod
     def from_arrays(cls, v_template, shapedirs, posedirs, weights, J_regressor, parents, faces=None, **kw):
@@ -102,14 +98,6 @@ class SMPLLayer:
     @classmethod
     def from_pkl(cls, path, **kw):
         return cls(**read_pkl(path), **kw)
-
-    def __del__(self):
-        ctx, self._ctx = getattr(self, '_ctx', None), None
-        if ctx:
-            try:
-                _lib.load().gator_smpl_destroy(ctx)
-            except Exception:
-                pass
 
     def workspace(self):
         """(device address, batch capacity) of the ctx's workspace: a test hook."""

@@ -29,43 +29,18 @@ def rainbow_colors(L):
     return lut[at][:, ::-1] * 255
 
 
-def _host_int(a):
-    a = np.asarray(a.cpu() if torch.is_tensor(a) else a).astype(np.int64)
-    return np.ascontiguousarray(np.clip(a, -1, 2 ** 31 - 1).astype(np.int32))       # out-of-range stays out of range for the C ABI's check
+class SkeletonDrawer(_lib.DeviceHandle):
+    PREFIX = 'gator_draw2d'
 
-
-class SkeletonDrawer:
     def __init__(self, skeleton, n_joints, device='cuda:0'):
         """skeleton: L pairs of joint indices (the reference's kps_line); n_joints: the joints every person has."""
-        sk = _host_int(skeleton)
+        sk = _lib.host_index(skeleton)
         if sk.ndim != 2 or sk.shape[1] != 2:
             raise ValueError('SkeletonDrawer: skeleton must be [L,2], got %s' % (sk.shape,))
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('SkeletonDrawer: the device must be a HIP device (there is no CPU path)')
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
         self.n_limbs, self.n_joints = int(sk.shape[0]), int(n_joints)
         self._skeleton = sk
-        self._h = ctypes.c_void_p()
-        self._lib = _lib.load()
         self._rainbow = None
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.gator_draw2d_create(sk.ctypes.data_as(ctypes.c_void_p), self.n_limbs, self.n_joints, ctypes.byref(self._h)),
-                       'gator_draw2d_create')
-
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h.value:
-            self._lib.gator_draw2d_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    __del__ = close
-
-    def workspace(self):
-        """(bytes held, allocations made since create) -- the test hook of the C ABI."""
-        b, n = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(self._lib.gator_draw2d_workspace(self._h, ctypes.byref(b), ctypes.byref(n)), 'gator_draw2d_workspace')
-        return b.value, n.value
+        self._create(device, _lib.host_ptr(sk), self.n_limbs, self.n_joints)
 
     def set_tile_rows(self, rows):
         """Measurement and test hook: 1 or 4 pixel rows a thread in the tile kernel (the same bytes), 0 = the built-in choice."""
@@ -111,7 +86,7 @@ class SkeletonDrawer:
             bbox = bbox.to(self.device).float().contiguous()
         idx = None
         if image_index is not None:
-            idx = _host_int(image_index)
+            idx = _lib.host_index(image_index)
             if idx.shape != (P,):
                 raise ValueError('draw: image_index must have one entry per person (%d), got %s' % (P, idx.shape))
         if out is None:
@@ -121,7 +96,7 @@ class SkeletonDrawer:
         col = self._colors(colors, style)
         a = _lib.Draw2dArgs(struct_size=ctypes.sizeof(_lib.Draw2dArgs), n_people=P, n_images=N, H=H, W=W, joint_dim=j.shape[2], style=STYLES[style],
                             kp_thre=float(kp_thre), alpha=float(alpha), joints=_lib.ptr(j), colors=_lib.ptr(col), bbox=_lib.ptr(bbox),
-                            images=_lib.ptr(images), out=_lib.ptr(out), image_index=idx.ctypes.data if idx is not None else None)
+                            images=_lib.ptr(images), out=_lib.ptr(out), image_index=_lib.host_ptr(idx))
         with torch.cuda.device(self.device):
             _lib.check(self._lib.gator_draw2d_u8(self._h, ctypes.byref(a), _lib.stream_ptr(self.device)), 'gator_draw2d_u8')
         return out

@@ -585,7 +585,7 @@ int gator_preprocess_noise_f32(const gator_preprocess_noise_args* args, void* st
  * with slot the rank of the winning mesh among the meshes of its image, -1 where empty; out_depth [n_images,H,W] f32, +Inf where empty.
  * An image is the same bits from run to run and whatever else is in the batch (integer atomic min on (depth, id) keys).
  * A vertex that is not finite or projects beyond +-2^20 px drops every face that touches it.  Workspace grows inside the handle (the
- * device is synchronised when it does); a call no larger than an earlier one allocates nothing; a growth that fails leaves the handle
+ * device is synchronised when a block is replaced); a call no larger than an earlier one allocates nothing; a growth that fails leaves the handle
  * usable for smaller calls.  image_index is read before the call returns (into a pinned block of the handle, copied on `stream`).  The
  * calls on one handle are ordered by the caller: one stream, or events between streams.
  * GATOR_EINVAL, before any launch: a NULL handle / verts / cams, no output, H or W outside 1..8192, n_meshes or n_images < 1,
@@ -638,7 +638,7 @@ int gator_renderer_set_small_box(gator_renderer* r, int32_t pixels);
  * colors[l] per limb (vis_2d_keypoints); GATOR_DRAW_COCO: lines of thickness 2, rings of radius 2 and thickness 3 (vis_coco_skeleton,
  * which passes one colour for every limb and joints without confidence).
  * Two launches on `stream`, no atomics, no host synchronisation; the same bytes from run to run and whatever else is in the batch.  The
- * primitive records live in the handle and grow when a larger call arrives (the device is synchronised when they do); a call no larger
+ * primitive records live in the handle and grow when a larger call arrives (the device is synchronised when a block is replaced); a call no larger
  * than an earlier one allocates nothing and, with image_index NULL, is capturable into a graph.  image_index is read before the call
  * returns.  The calls on one handle are ordered by the caller.
  * GATOR_EINVAL naming the field, before any launch: a NULL handle, args, joints, colors, images or out; struct_size smaller than this

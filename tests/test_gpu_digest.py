@@ -80,6 +80,26 @@ def test_caller_side_digests_match_the_recorded_build():
     assert not bad, 'outputs moved bits against tests/golden/caller_side_digests.json: %s' % bad
 
 
+HANDLES_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'handle_digests.json')
+
+
+@pytest.mark.parametrize('lib', ['renderer', 'draw2d', 'smpl', 'fit'])
+def test_handle_digests_match_the_recorded_build(lib):
+    """The auxiliary libraries behind a handle bit for bit against the build recorded before their host scaffolding (growth rule, staged
+    table, handle checks) was stated once in csrc/handle.h: small seeded calls of every entry point, and per handle a small call, the
+    largest and the small one again, whose digests must not depend on the handle's history and whose workspace() tuples (bytes and
+    allocation counts, the SMPL capacity) are the recorded ones (tools/ab_digest.py: handle_digests)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tools.ab_digest import HANDLE_LIBS, handle_digests
+    assert lib in HANDLE_LIBS
+    want = {k: h for k, h in json.load(open(HANDLES_PATH))['digests'].items() if k.startswith(lib + ' ')}
+    got = handle_digests([lib])
+    assert len(want) >= 5 and set(got) == set(want)
+    bad = {k: (got.get(k), h) for k, h in want.items() if got.get(k) != h}
+    assert not bad, 'outputs or workspaces moved against tests/golden/handle_digests.json: %s' % bad
+
+
 def test_byte_lo_weight_stream_equals_the_three_plane_stream_bit_for_bit(monkeypatch):
     """k_gat8 streams its weights with the lo plane as one byte per weight by default (gat8_forms.h: H3B); GATOR_GAT8_LOBYTE=0 keeps
     the three fp16 planes.  The switch is read per context, so both forms run in this process; the digests (which cover B = 5 / 256 / 700

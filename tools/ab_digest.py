@@ -10,7 +10,10 @@
     (preprocess, camera crop, Procrustes / joint / mesh / sequence errors, camera targets) on small seeded shapes.
   * `--encoder --write tests/golden/encoder_form_digests.json` does the same for encoder_digests(): every form of the GAT encoder kernels
     (k_gat8, k_gat, k_gat_tiled, the tail launches, the stand-alone encoder entry, the block taps) at batches the fp32 digests never reach.
-python tools/ab_digest.py [tag] [--forms | --caller | --encoder] [--write path [--commit hash-of-the-recorded-build]]"""
+  * `--handles --write tests/golden/handle_digests.json` does the same for handle_digests(): the auxiliary libraries behind a handle (mesh
+    renderer, 2D overlay, SMPL layer and fit) on small seeded shapes, with each handle's workspace() after a small, the largest and the small
+    call again.
+python tools/ab_digest.py [tag] [--forms | --caller | --encoder | --handles] [--write path [--commit hash-of-the-recorded-build]]"""
 import contextlib, hashlib, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -312,6 +315,157 @@ def caller_digests():
     return out
 
 
+# The auxiliary libraries' handles (render.hip, draw2d.hip, smpl_lbs.hip, smpl_fit.hip): small seeded calls, and per handle the sequence
+# small call / largest call / small call again with the workspace() tuple after each, so that the host side of a handle (growth rule,
+# staged tables, accounting) is pinned against the build that recorded the file.
+HANDLE_LIBS = ('renderer', 'draw2d', 'smpl', 'fit')
+HANDLE_SMPL_CASE = 'nv257'
+
+
+def _renderer_digests(out):
+    import numpy as np
+    from gator_amd import render
+    from tests import render_refs
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    base, faces = render_refs.icosphere(1)                  # 42 vertices, 80 faces
+    rs = np.random.RandomState(11000)
+    spheres = np.stack([base * 0.55, base * np.array([0.35, 0.5, 0.4])])      # two spheres; three meshes are placed from them
+    verts = (spheres[[0, 1, 0]] + rs.uniform(-0.15, 0.15, (3, 1, 3))).astype(np.float32)
+    cam = np.concatenate([rs.uniform(0.7, 1.1, (3, 2)), rs.uniform(-0.2, 0.2, (3, 2))], 1).astype(np.float32)
+    W, H = 65, 33
+    bg = dev(rs.randint(0, 256, (2, H, W, 3)).astype(np.uint8))
+    color = rs.uniform(0.2, 1.0, (3, 3)).astype(np.float32)
+    large = dict(verts=dev(verts), cam=dev(cam), background=bg, color=color, image_index=[1, 0, 1], size=(W, H), return_face_id=True, return_depth=True)
+    small = dict(verts=dev(verts[:1]), cam=dev(cam[:1]), size=(16, 9), return_face_id=True, return_depth=True)
+    r = render.MeshRenderer(faces, 'cuda:0', n_verts=base.shape[0])
+    seq, ws = [], []
+    for kw in (small, large, small):
+        seq.append(_sha_canon(*r.render(**kw)))
+        ws.append(list(r.workspace()))
+    out['renderer render M=3 N=2 index=[1,0,1]'] = seq[1]
+    out['renderer render M=2 index=None'] = _sha_canon(*r.render(dev(verts[:2]), dev(cam[:2]), size=(W, H), return_face_id=True, return_depth=True))
+    xy, z, n = r.project(large['verts'], large['cam'], size=(W, H))
+    keys = r.rasterise(xy, z, image_index=[1, 0, 1], n_images=2, size=(W, H))
+    staged = r.resolve(keys, xy, n, background=bg, color=color, image_index=[1, 0, 1], return_face_id=True, return_depth=True)
+    out['renderer project rasterise resolve M=3 N=2'] = _sha_canon(xy, z, n, keys, *staged)
+    fresh = _sha_canon(*render.MeshRenderer(faces, 'cuda:0', n_verts=base.shape[0]).render(**small))
+    assert seq[0] == seq[2] == fresh, 'the renderer depends on its workspace history'
+    out['renderer sequence small'], out['renderer sequence workspace'] = seq[0], ws
+
+
+def _draw2d_digests(out):
+    import numpy as np
+    from gator_amd import vis
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    skeleton = [(0, 1), (1, 2), (2, 3), (1, 4)]
+    rs = np.random.RandomState(12000)
+    W, H = 70, 37
+    joints = np.concatenate([rs.uniform(-5, W + 5, (3, 5, 1)), rs.uniform(-5, H + 5, (3, 5, 1)), rs.uniform(0.2, 1.0, (3, 5, 1))], 2).astype(np.float32)
+    lo, hi = joints[:, :, :2].min(1), joints[:, :, :2].max(1)
+    bbox = np.stack([lo, np.stack([hi[:, 0], lo[:, 1]], 1), hi, np.stack([lo[:, 0], hi[:, 1]], 1)], 1).astype(np.float32)
+    frames = dev(rs.randint(0, 256, (2, H, W, 3)).astype(np.uint8))
+    tiny = dev(rs.randint(0, 256, (1, 9, 16, 3)).astype(np.uint8))
+    d = vis.SkeletonDrawer(skeleton, 5, 'cuda:0')
+    large = dict(images=frames, joints=dev(joints), bbox=dev(bbox), image_index=[1, 0, 1], alpha=0.6)
+    small = dict(images=tiny, joints=dev(joints[:1] * np.array([0.2, 0.2, 1.0], np.float32)))
+    seq, ws = [], []
+    for kw in (small, large, small):
+        seq.append(_sha_canon(d.draw(**kw)))
+        ws.append(list(d.workspace()))
+    for style, colors in (('keypoints', None), ('coco', (40.0, 200.0, 120.0))):
+        for bb in (None, large['bbox']):
+            got = {}
+            for rows in (1, 4):
+                d.set_tile_rows(rows)
+                got[rows] = _sha_canon(d.draw(frames, large['joints'], colors=colors, bbox=bb, image_index=[1, 0, 1], alpha=0.6, style=style))
+            d.set_tile_rows(0)
+            inplace = frames.clone()
+            d.draw(inplace, large['joints'], colors=colors, bbox=bb, image_index=[1, 0, 1], alpha=0.6, style=style, out=inplace)
+            assert got[1] == got[4] == _sha_canon(inplace), 'draw2d: tile rows or in-place drawing change the bytes'
+            out['draw2d %s bbox=%d P=3 N=2' % (style, bb is not None)] = got[1]
+    fresh = _sha_canon(vis.SkeletonDrawer(skeleton, 5, 'cuda:0').draw(**small))
+    assert seq[0] == seq[2] == fresh and seq[1] == out['draw2d keypoints bbox=1 P=3 N=2'], 'the drawer depends on its workspace history'
+    out['draw2d sequence small'], out['draw2d sequence workspace'] = seq[0], ws
+
+
+def _smpl_case():
+    from gator_amd import smpl
+    from tests import smpl_refs
+    from tests.helpers import load_golden
+    m = smpl_refs.synthetic_model(*smpl_refs.CASES[HANDLE_SMPL_CASE][0])
+    z = load_golden('smpl_layer')
+    pose, betas, trans = (torch.from_numpy(z['%s.%s' % (HANDLE_SMPL_CASE, k)]).cuda() for k in ('pose', 'betas', 'trans'))
+    make = lambda **kw: smpl.SMPLLayer.from_arrays(m['v_template'], m['shapedirs'], m['posedirs'], m['weights'], m['J_regressor'],  # noqa: E731
+                                                   m['parents'], faces=m['faces'], **kw)
+    return make, pose, betas, trans
+
+
+def _smpl_workspace(layer, before):
+    """[batch capacity, 1 if the workspace's block is another one than after the previous call] -- the address itself is no constant"""
+    base, cap = layer.workspace()
+    return base, [cap, int(base != before)]
+
+
+def _smpl_digests(out):
+    make, pose, betas, trans = _smpl_case()
+    layer, centred = make(), make(center_idx=3)
+    seq, ws, base = [], [], 0
+    for B in (1, 33, 1):
+        seq.append(_sha_canon(*layer(pose[:B], betas[:B], trans[:B])))
+        base, w = _smpl_workspace(layer, base)
+        ws.append(w)
+    for B in (1, 33):
+        out['smpl forward B=%d' % B] = seq[0] if B == 1 else seq[1]
+        out['smpl forward B=%d center_idx=3' % B] = _sha_canon(*centred(pose[:B], betas[:B]))
+    fresh = _sha_canon(*make()(pose[:1], betas[:1], trans[:1]))
+    assert seq[0] == seq[2] == fresh, 'the SMPL layer depends on its workspace history'
+    out['smpl sequence workspace'] = ws
+
+
+def _fit_digests(out):
+    make, pose, betas, trans = _smpl_case()
+    layer = make()
+    target = layer(pose[:2], betas[:2], trans[:2])[0].clone()
+    seq, ws, base = [], [], 0
+    for B in (1, 2, 1):
+        seq.append(_sha_canon(*layer.fit(target[:B], iters=3)))
+        base, w = _smpl_workspace(layer, base)
+        ws.append(w)
+    out['fit cold B=2 iters=3'] = seq[1]
+    warm = (pose[:2] + 0.05, betas[:2] * 0.5, trans[:2] + 0.01)
+    out['fit warm B=2 iters=3'] = _sha_canon(*layer.fit(target, iters=3, init=warm))
+    M = layer.fit_normal(*warm, target)
+    P, N = layer.fit_width()
+    iu = torch.triu_indices(N, N, device=M.device)
+    out['fit normal B=2'] = _sha_canon(M[:, iu[0], iu[1]])              # only the upper triangle is specified
+    fresh = _sha_canon(*make().fit(target[:1], iters=3))
+    assert seq[0] == seq[2] == fresh, 'the SMPL fit depends on its workspace history'
+    out['fit sequence small'], out['fit sequence workspace'] = seq[0], ws
+
+
+def handle_digests(libs=None):
+    """{'<library> <case>': digest, '<library> sequence workspace': the workspace() tuple after each of the three calls}."""
+    out = {}
+    for lib in (libs or HANDLE_LIBS):
+        {'renderer': _renderer_digests, 'draw2d': _draw2d_digests, 'smpl': _smpl_digests, 'fit': _fit_digests}[lib](out)
+    torch.cuda.synchronize()
+    return out
+
+
+def main_handles():
+    write = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
+    d = handle_digests()
+    for k, h in d.items():
+        print('%-56s %s' % (k, h), flush=True)
+    if write:
+        commit = sys.argv[sys.argv.index('--commit') + 1] if '--commit' in sys.argv else 'unknown'
+        what = ('sha256[:32] of the raw output bytes of the auxiliary libraries (tools/ab_digest.py: handle_digests: renderer, draw2d, SMPL layer '
+                'and fit), gfx950, NaNs canonicalised, seeded inputs; "sequence workspace": workspace() after a small, the largest and the small '
+                'call again on one handle (SMPL: [capacity, block replaced]).  Recorded with the library of commit %s' % commit)
+        with open(write, 'w') as f:
+            json.dump({'what': what, 'digests': d}, f, indent=1)
+
+
 def main_caller():
     write = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
     d = caller_digests()
@@ -332,6 +486,8 @@ def main():
         return main_caller()
     if '--encoder' in sys.argv:
         return main_encoder()
+    if '--handles' in sys.argv:
+        return main_handles()
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
     write = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
     if write in args:
