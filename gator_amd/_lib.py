@@ -133,6 +133,8 @@ SIGNATURES = {
     'gator_smpl_create': (_I, [_P, ctypes.POINTER(_P)]),
     'gator_smpl_destroy': (_I, [_P]),
     'gator_smpl_forward_f32': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P, _P]),
+    'gator_smpl_backward_f32': (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
+    'gator_smpl_workspace_bytes': (_I, [_P, ctypes.POINTER(_L), ctypes.POINTER(_L)]),
     'gator_smpl_workspace': (_I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_L)]),
     'gator_smpl_fit_f32': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     'gator_smpl_fit_normal_f32': (_I, [_P, _P, _P, _P, _P, _I, _P, _P]),

@@ -1,5 +1,5 @@
-// The SMPL handle (gator_smpl_*): the packed model and the workspaces of its two users, the layer (smpl_lbs.hip) and the fit
-// (smpl_fit.hip).
+// The SMPL handle (gator_smpl_*): the packed model and the workspaces of its three users, the layer (smpl_lbs.hip), the fit
+// (smpl_fit.hip) and the layer's backward (smpl_backward.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +34,12 @@ struct gator_smpl : gator::Handle {
     gator::WorkBuf<float> fpart;     // [fcap][S][pairs][32][32] per-chunk partial sums of M's upper tiles
     gator::WorkBuf<float> fM;        // [2][fcap][N][N] M of the candidate, of the current state
     int fcap = 0;
+    // the backward (smpl_backward.hip): the basis once more, coefficient-minor, then its workspace, each block grown on its own
+    int Kq = 0;                      // Kp rounded up to whole 32-coefficient MFMA tiles
+    gator::WorkBuf<float> basisT;    // [3][NVp][Kq]  [shapedirs | posedirs] transposed, zero padded; made by the first backward with grad_verts
+    gator::WorkBuf<float> bpart;     // [sample tiles][NVp / kTV][Kq + 12 NJ][32] per-vertex-tile partial sums of g_coef and gA
+    gator::WorkBuf<double> btrans;   // [sample tiles][NVp / kTV][3][32]          ... of sum_v gx
+    gator::WorkBuf<double> bsum;     // [batch][Kq + 12 NJ + 4]                    their sums over the vertex tiles
 };
 
 namespace gator {
@@ -57,4 +63,5 @@ int smpl_reserve(gator_smpl* c, int B);                                  // the 
 int smpl_pose_stage(gator_smpl* c, const float* pose, const float* betas, const float* trans, int batch, int center, double out_scale,
                     float* joints, hipStream_t st);
 int smpl_fit_build(gator_smpl* c, const gator_smpl_model* m);            // smpl_fit.hip: the fit's share of gator_smpl_create
+int smpl_backward_build(gator_smpl* c, const gator_smpl_model* m);       // smpl_backward.hip: the backward's share
 }  // namespace gator

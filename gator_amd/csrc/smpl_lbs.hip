@@ -298,7 +298,8 @@ extern "C" int gator_smpl_create(const gator_smpl_model* m, gator_smpl** out) {
         c->Kp = (c->K + 4 * kKU - 1) / (4 * kKU) * (4 * kKU);
         c->NVp = (c->NV + kTV - 1) / kTV * kTV;
         GATOR_TRY(smpl_build(c, m));
-        return smpl_fit_build(c, m);
+        GATOR_TRY(smpl_fit_build(c, m));
+        return smpl_backward_build(c, m);
     });
 }
 

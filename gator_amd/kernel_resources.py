@@ -13,6 +13,7 @@ HOT = ('k_gat<true', 'k_gat8', 'k_gat_lifter', 'k_gat_joint', 'k_gat_tiled<', 'k
        'k_mdr_layer<0, 3>', 'k_mdr_layer<1, 3>', 'k_mdr_layer<2, 3>', 'k_mdr_persist<3>',
        'k_mdr_head<', 'k_mdr_head_finish', 'k_upsample_x3', 'k_upsample_x2', 'k_upsample_bf16', 'k_regress', 'k_jreg_reduce', 'k_joint_errors', 'k_rigid_align', 'k_mesh_errors', 'k_preprocess',
        'k_crop_joints', 'k_fit_camera<', 'k_smpl_pose', 'k_smpl_skin<', 'k_smpl_fit_normal<', 'k_smpl_fit_reduce', 'k_smpl_fit_solve',
+       'k_smpl_bwd_skin<', 'k_smpl_bwd_reduce', 'k_smpl_bwd_chain', 'k_smpl_bwd_transpose',
        'k_render_vertices', 'k_render_raster', 'k_render_resolve', 'k_draw_build', 'k_draw_tiles', 'k_one_euro<', 'k_seq_errors<', 'k_seq_reduce',
        'k_batch_prepare', 'k_camera_targets', 'k_noise_crop', 'k_noise_candidates', 'k_noise_finish')
 SCRATCH_BUDGET = {}      # (round 6: k_gat_tiled's entries are gone -- its scratch was a hoisted sum, gat_tiled.hip: aggregate)

@@ -7,8 +7,8 @@ data/COCO/dataset.py:147-166), batched.
   targets_from_smpl(layer, pose, shape, trans, regressors ...)     ->  {'mesh', 'reg_pose3d', 'lift_pose3d'}        Trainer.step's targets
   SMPLLayer.fit(verts [B,6890,3], iters, init) / fit_to_mesh(layer, verts) -> (pose, betas, trans, rms)             the inverse: mesh -> parameters
 
-The model's arrays come from the caller: the official files are licence-gated and are no part of this package.  No backward: the
-reference never differentiates through the layer."""
+The model's arrays come from the caller: the official files are licence-gated and are no part of this package.  The layer is
+differentiable in pose, betas and trans (gator_smpl_backward_f32, csrc/smpl_backward.hip), once; not in the model's arrays."""
 import ctypes
 import pickle
 
@@ -55,10 +55,57 @@ def read_pkl(path):
         return model_arrays(pickle.load(fh, encoding='latin1'))
 
 
+class _LayerFunction(torch.autograd.Function):
+    """The layer under autograd: the same forward entry, and gator_smpl_backward_f32 on the saved float32 inputs with the center_idx /
+    out_scale of that call (the attributes may have changed by the time backward runs).  First derivatives only."""
+
+    @staticmethod
+    def forward(ctx, layer, center, out_scale, want_verts, want_joints, pose, betas, trans):
+        verts, joints = layer._run(pose, betas, trans, center, out_scale, want_verts, want_joints)
+        ctx.layer, ctx.center, ctx.out_scale = layer, center, out_scale
+        ctx.save_for_backward(pose, betas, trans)
+        ctx.set_materialize_grads(False)                  # an output the loss does not reach arrives as None, not as zeros
+        outs = tuple(o for o in (verts, joints) if o is not None)
+        ctx.which = (want_verts, want_joints)
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        layer = ctx.layer
+        pose, betas, trans = ctx.saved_tensors
+        grads = list(grads)
+        gv = grads.pop(0) if ctx.which[0] else None
+        gj = grads.pop(0) if ctx.which[1] else None
+        need = ctx.needs_input_grad[5:8]
+        B = pose.shape[0]
+        new = lambda ok, ref: torch.empty_like(ref) if (ok and ref is not None) else None      # noqa: E731
+        g_pose, g_betas, g_trans = new(need[0], pose), new(need[1], betas), new(need[2], trans)
+        if gv is None and gj is None:                     # neither output reached the loss
+            for g in (g_pose, g_betas, g_trans):
+                if g is not None:
+                    g.zero_()
+        elif B and (g_pose is not None or g_betas is not None or g_trans is not None):
+            gv = None if gv is None else gv.contiguous().float()
+            gj = None if gj is None else gj.contiguous().float()
+            ptr = _lib.ptr
+            with torch.cuda.device(layer.device):
+                _lib.check(_lib.load().gator_smpl_backward_f32(layer._ctx, ptr(pose), ptr(betas), ptr(trans), B, ctx.center, ctx.out_scale,
+                                                               ptr(gv), ptr(gj), ptr(g_pose), ptr(g_betas), ptr(g_trans),
+                                                               _lib.stream_ptr(layer.device)), 'gator_smpl_backward_f32')
+        return None, None, None, None, None, g_pose, g_betas, g_trans
+
+
 class SMPLLayer(_lib.DeviceHandle):
-    """smplpytorch's SMPL_Layer, forward only, on one HIP device.  Same call order (pose, betas, trans), the same center_idx
-    attribute, th_faces / th_J_regressor / th_weights / kintree_parents as the reference layer exposes them.  out_scale multiplies
-    the (translated or centred) outputs: 1000 for the datasets' millimetres."""
+    """smplpytorch's SMPL_Layer on one HIP device.  Same call order (pose, betas, trans), the same center_idx attribute, th_faces /
+    th_J_regressor / th_weights / kintree_parents as the reference layer exposes them.  out_scale multiplies the (translated or
+    centred) outputs: 1000 for the datasets' millimetres.
+
+    Differentiable, like the reference layer: when grad mode is on and pose, betas or trans requires grad, the outputs carry a
+    grad_fn and loss.backward() fills the inputs' .grad with the exact vector-Jacobian product, computed on the device from the
+    inputs (nothing per vertex is kept from the forward; an output that was not asked for or not used costs nothing, and a loss on
+    the joints alone does no per-vertex work).  First derivatives only, and none with respect to the model's arrays.  Otherwise the
+    call is the plain forward: the same launches, the same bits, no grad_fn."""
     PREFIX = 'gator_smpl'
     NO_CPU = 'the layer runs on a HIP device (there is no CPU path)'
     _ctx = property(lambda self: self._h)      # the C ABI's name for this handle
@@ -105,6 +152,12 @@ class SMPLLayer(_lib.DeviceHandle):
         _lib.check(_lib.load().gator_smpl_workspace(self._ctx, ctypes.byref(base), ctypes.byref(cap)), 'gator_smpl_workspace')
         return base.value or 0, cap.value
 
+    def workspace_bytes(self):
+        """(bytes held by the ctx's grown blocks, growths since create): a test hook; a repeated call at a known batch moves neither."""
+        b, n = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(_lib.load().gator_smpl_workspace_bytes(self._ctx, ctypes.byref(b), ctypes.byref(n)), 'gator_smpl_workspace_bytes')
+        return b.value, n.value
+
     def _arg(self, x, width, name, B):
         if x is None:
             return None
@@ -123,11 +176,18 @@ class SMPLLayer(_lib.DeviceHandle):
         betas = self._arg(th_betas, self.num_betas, 'betas', B) if self.num_betas else None
         trans = self._arg(th_trans, 3, 'trans', B)
         center = -1 if (self.center_idx is None or trans is not None) else int(self.center_idx)
+        if torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (pose, betas, trans)):
+            outs = list(_LayerFunction.apply(self, center, self.out_scale, want_verts, want_joints, pose, betas, trans))
+            return (outs.pop(0) if want_verts else None), (outs.pop(0) if want_joints else None)
+        return self._run(pose, betas, trans, center, self.out_scale, want_verts, want_joints)
+
+    def _run(self, pose, betas, trans, center, out_scale, want_verts, want_joints):
+        B = pose.shape[0]
         verts = torch.empty((B, self.num_verts, 3), device=self.device, dtype=torch.float32) if want_verts else None
         joints = torch.empty((B, self.num_joints, 3), device=self.device, dtype=torch.float32) if want_joints else None
         ptr = _lib.ptr
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().gator_smpl_forward_f32(self._ctx, ptr(pose), ptr(betas), ptr(trans), B, center, self.out_scale, ptr(verts),
+            _lib.check(_lib.load().gator_smpl_forward_f32(self._ctx, ptr(pose), ptr(betas), ptr(trans), B, center, out_scale, ptr(verts),
                                                           ptr(joints), _lib.stream_ptr(self.device)), 'gator_smpl_forward_f32')
         return verts, joints
 
@@ -155,7 +215,8 @@ class SMPLLayer(_lib.DeviceHandle):
 
         Deliberately out of scope: pose and shape priors, joint-limit constraints, per-vertex weights, fitting to 2D evidence, and
         models with more than 4 influences per vertex (refused).  The result is the unconstrained least-squares fit in vertex
-        space: on a mesh that no parameters reproduce, nothing keeps the pose plausible."""
+        space: on a mesh that no parameters reproduce, nothing keeps the pose plausible.  For any of these, take the fit as the start
+        and refine through the layer itself with a torch optimiser: forward is differentiable in pose, betas and trans."""
         verts = self._verts_arg(verts)
         B = verts.shape[0]
         if init is not None:

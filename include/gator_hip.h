@@ -314,8 +314,26 @@ int gator_smpl_destroy(gator_smpl* ctx);
 int gator_smpl_forward_f32(gator_smpl* ctx, const float* pose, const float* betas, const float* trans, int32_t batch,
                            int32_t center_idx, float out_scale, float* verts, float* joints, void* stream);
 
+/* The backward of gator_smpl_forward_f32: the exact vector-Jacobian product at (pose, betas, trans), which are the forward's inputs with
+ * the forward's center_idx / out_scale (and its argument checks).  grad_verts [batch, NV, 3] and grad_joints [batch, NJ, 3] are the
+ * upstream gradients of the two outputs, either may be NULL (that output was not used: with grad_verts = NULL no per-vertex work is
+ * done); grad_pose [batch, NJ*3], grad_betas [batch, NB] and grad_trans [batch, 3] are written, a NULL one is simply not computed.
+ * Everything is recomputed from the inputs: the forward keeps nothing per vertex.  The mathematics and the kernels are stated once in
+ * csrc/smpl_backward.hip.
+ * GATOR_EINVAL with a reason, before any launch: what the forward refuses, and grad_verts = grad_joints = NULL.  batch = 0 is a no-op.
+ * No host synchronisation and no float atomics; a repeated call at a batch no larger than an earlier one allocates nothing and can be
+ * captured into a graph (the first call with grad_verts also builds the ctx's transposed basis and waits for the stream once).  Row b
+ * of every output is the same bits whatever the batch around it and from run to run.  A non-finite
+ * pose, beta, trans or upstream gradient of sample b makes sample b's three gradient rows NaN and changes no other row. */
+int gator_smpl_backward_f32(gator_smpl* ctx, const float* pose, const float* betas, const float* trans, int32_t batch,
+                            int32_t center_idx, float out_scale, const float* grad_verts, const float* grad_joints,
+                            float* grad_pose, float* grad_betas, float* grad_trans, void* stream);
+
 /* Test hook: the base of the ctx's workspace and the batch it holds (0 / NULL before the first forward). */
 int gator_smpl_workspace(const gator_smpl* ctx, const void** base, int64_t* capacity);
+/* Test hook, as the other handles' *_workspace: the bytes the ctx's grown blocks hold now (the forward's, the fit's and the backward's
+ * workspaces, the backward's transposed basis) and the number of growths since create.  Either pointer may be NULL. */
+int gator_smpl_workspace_bytes(const gator_smpl* ctx, int64_t* bytes, int64_t* allocations);
 
 /* The inverse of the layer: a batched Levenberg-Marquardt fit of (pose [batch, NJ*3], betas [batch, NB], trans [batch, 3]) to target
  * vertices [batch, NV, 3] in the layer's unit, out_scale 1, no centring; device pointers.  The result is the UNCONSTRAINED least-squares
