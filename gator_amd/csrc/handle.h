@@ -2,6 +2,8 @@
 // accounting of its workspace with the one growth rule, the staged host-to-device table, create / destroy, and the checks every entry
 // point starts with.  Host code only (DESIGN.md "Handles of the auxiliary libraries").
 #pragma once
+#include <vector>
+
 #include "image_groups.h"
 #include "internal.h"
 
@@ -9,6 +11,13 @@ namespace gator {
 
 // A workspace buffer with the element count it holds; cap is 0 whenever the block is not there.
 template <class T, bool Pinned = false> struct WorkBuf : DevBuf<T, Pinned> { size_t cap = 0; };
+
+// A table made on the host at create: the device block (one element when the table is empty) and its blocking copy.
+template <class T> int upload(DevBuf<T>& d, const std::vector<T>& h) {
+    GATOR_TRY(d.alloc(sizeof(T) * (h.empty() ? 1 : h.size())));
+    if (!h.empty()) GATOR_HIP_CHECK(hipMemcpy(d.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+    return GATOR_OK;
+}
 
 struct Handle {
     int device = 0;

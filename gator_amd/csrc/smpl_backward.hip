@@ -22,8 +22,8 @@
 // Kernels.
 //   k_smpl_pose      (smpl_lbs.hip) at the inputs: the coefficient rows and the skinning transforms, as in the forward.
 //   k_smpl_bwd_skin  the hot path, the transpose of k_smpl_skin.  A workgroup owns one (32-sample, 128-vertex) tile:
-//                    1. p - v_template = [32 x K] . [K x 3 x 128] on v_mfma_f32_32x32x2_f32, the forward's loop, a lane holding x, y, z of
-//                       one vertex for 16 samples;
+//                    1. p - v_template = [32 x K] . [K x 3 x 128]: smpl_coef_tile and smpl_blend (smpl_steps.h), the code k_smpl_skin
+//                       runs, a lane holding x, y, z of one vertex for 16 samples;
 //                    2. in registers gx = s gV, p, T^R = sum w A^R and gp = T^R^T gx; gx and p go to LDS as [coordinate][vertex][sample];
 //                    3. gA as a matrix product over the tile's vertices in vertex order, D[joint][sample] += W^T[joint][v] . (gx_r p_c)[v][sample]
 //                       with the dense [128 x 32] weight tile of the vertices in LDS (so any number of influences costs the same):
@@ -35,8 +35,8 @@
 //                    Every result is a per-tile partial, written sample-minor to the workspace.  The chunk of the vertex sum is the tile:
 //                    it depends on NV alone.
 //   k_smpl_bwd_reduce adds the tiles' partials in tile order in fp64.
-//   k_smpl_bwd_chain one wave per sample, fp64: the forward chain again, then the transforms, the reverse chain, the rest joints and the
-//                    Rodrigues derivative above; each output is rounded to float32 once.
+//   k_smpl_bwd_chain one wave per sample, fp64: smpl_kinematics (smpl_steps.h: rotations, rest joints, forward chain), then the transforms,
+//                    the reverse chain, the rest joints and the Rodrigues derivative above; each output is rounded to float32 once.
 // With grad_verts = NULL only k_smpl_bwd_chain runs (it recomputes its own rotations and joints): nothing per vertex is touched.
 // Determinism: a sample is one MFMA column (steps 3, 4) or row (step 1) and one LDS column from end to end, every sum has a fixed order
 // and nothing is atomic: row b is the same bits whatever the batch and from run to run.  A non-finite pose, beta, trans or upstream
@@ -49,16 +49,12 @@
 
 #include "internal.h"
 #include "smpl_ctx.h"
+#include "smpl_steps.h"
 
 namespace gator {
 namespace {
 
-constexpr int kTS = 32;      // samples per tile, as in the forward
-constexpr int kKU = 4;       // the forward's pipeline stage of the blend product: Kp is a multiple of 4 kKU
 constexpr int kSG = 16;      // k-steps per pipeline stage of the g_coef product
-constexpr int kLd = 33;      // leading dimension of every [..][32 samples] LDS image: conflict-free along samples and along vertices
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __host__ __device__ constexpr int bwd_pw(int Kq, int NJ) { return Kq + NJ * 12; }      // floats of one sample's partial: g_coef, gA
 __host__ __device__ constexpr int bwd_sw(int Kq, int NJ) { return Kq + NJ * 12 + 4; }  // doubles of one sample's sums: g_coef, gA, g_off
@@ -79,10 +75,7 @@ __global__ __launch_bounds__(256) void k_smpl_bwd_skin(const float* __restrict__
     const int s0 = blockIdx.y * kTS, v0 = blockIdx.x * kTV;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 31, hi = lane >> 5;
     const int ns = min(kTS, B - s0);
-    for (int e = threadIdx.x; e < kTS * Kp; e += 256) {
-        const int s = e / Kp, k = e - s * Kp;
-        gxL[k * kLd + s] = s < ns ? coef[(size_t)(s0 + s) * Kp + k] : 0.f;
-    }
+    smpl_coef_tile(coef, s0, ns, Kp, gxL);
     for (int e = threadIdx.x; e < kTV * kLd; e += 256) WL[e] = 0.f;
     for (int e = threadIdx.x; e < kTS * NJ * 9; e += 256) {
         const int s = e / (NJ * 9), q = e - s * (NJ * 9), j = q / 9, k = q - j * 9;
@@ -95,39 +88,8 @@ __global__ __launch_bounds__(256) void k_smpl_bwd_skin(const float* __restrict__
         if (w != 0.f) WL[vl * kLd + widx[(size_t)m * NVp + v0 + vl]] = w;
     }
     const int vl = wave * 32 + col, v = v0 + vl;                        // < NVp: the planes are padded to whole tiles
-    const size_t plane = (size_t)Kp * NVp;
-    const float* bp = basis + v;
     f32x16 ax = {0}, ay = {0}, az = {0};
-    // step 1: the forward's blend product, the same loop (smpl_lbs.hip: k_smpl_skin)
-    float pa[kKU], px_[kKU], py_[kKU], pz_[kKU], qa[kKU], qx[kKU], qy[kKU], qz[kKU];
-    auto fetch = [&](int k, float (&a)[kKU], float (&x)[kKU], float (&y)[kKU], float (&z)[kKU]) {
-#pragma unroll
-        for (int u = 0; u < kKU; ++u) {
-            const int kk = k + 2 * u + hi;
-            const size_t o = (size_t)kk * NVp;
-            a[u] = gxL[kk * kLd + col];
-            x[u] = bp[o]; y[u] = bp[o + plane]; z[u] = bp[o + 2 * plane];
-        }
-    };
-    auto mma = [&](const float (&a)[kKU], const float (&x)[kKU], const float (&y)[kKU], const float (&z)[kKU]) {
-#pragma unroll
-        for (int u = 0; u < kKU; ++u) {
-            ax = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], x[u], ax, 0, 0, 0);
-            ay = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], y[u], ay, 0, 0, 0);
-            az = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], z[u], az, 0, 0, 0);
-        }
-    };
-    fetch(0, pa, px_, py_, pz_);
-    for (int k = 0; k < Kp; k += 4 * kKU) {
-        fetch(k + 2 * kKU, qa, qx, qy, qz);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(pa, px_, py_, pz_);
-        __builtin_amdgcn_sched_barrier(0);
-        fetch(min(k + 4 * kKU, Kp - 2 * kKU), pa, px_, py_, pz_);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(qa, qx, qy, qz);
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    smpl_blend(gxL, basis + v, NVp, Kp, col, hi, ax, ay, az);           // step 1: p - v_template, by the forward's own code
     __syncthreads();                                                    // the coefficient tile is done with; the weight tile is complete
     // step 2
     const float tx = vtempl[v], ty = vtempl[NVp + v], tz = vtempl[2 * NVp + v];
@@ -143,7 +105,7 @@ __global__ __launch_bounds__(256) void k_smpl_bwd_skin(const float* __restrict__
     const float* gbase = gverts + ((size_t)s0 * NV + min(v, NV - 1)) * 3;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int i = (r & 3) + 8 * (r >> 2) + 4 * hi;                  // C/D map of the 32x32 MFMA: register r of lane (col, hi) is row i
+        const int i = mfma32_row(r, hi);
         const float* xi = xr + i * NJ * 9;
         float T[9];
 #pragma unroll
@@ -171,7 +133,7 @@ __global__ __launch_bounds__(256) void k_smpl_bwd_skin(const float* __restrict__
         gxL[vl * kLd + i] = g0;
         gxL[(kTV + vl) * kLd + i] = g1;
         gxL[(2 * kTV + vl) * kLd + i] = g2;
-        pL[vl * kLd + i] = tx + ax[r];                                  // v_posed = v_template + blend offsets, the forward's bits
+        pL[vl * kLd + i] = tx + ax[r];                                  // v_posed = v_template + blend offsets
         pL[(kTV + vl) * kLd + i] = ty + ay[r];
         pL[(2 * kTV + vl) * kLd + i] = tz + az[r];
         float h0 = fmaf(T[0], g0, fmaf(T[3], g1, T[6] * g2));           // gp = T^R^T gx
@@ -200,7 +162,7 @@ __global__ __launch_bounds__(256) void k_smpl_bwd_skin(const float* __restrict__
         }
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int j = (q & 3) + 8 * (q >> 2) + 4 * hi;
+            const int j = mfma32_row(q, hi);
             if (j < NJ) {
                 const int o = (Kq + j * 12 + c) * kTS + col;
                 pt[o] = a0[q]; pt[o + 4 * kTS] = a1[q]; pt[o + 8 * kTS] = a2[q];
@@ -217,7 +179,7 @@ __global__ __launch_bounds__(256) void k_smpl_bwd_skin(const float* __restrict__
     __syncthreads();                                                    // p is done with: gp takes its place
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int i = (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int i = mfma32_row(r, hi);
         pL[vl * kLd + i] = ax[r];
         pL[(kTV + vl) * kLd + i] = ay[r];
         pL[(2 * kTV + vl) * kLd + i] = az[r];
@@ -254,7 +216,7 @@ __global__ __launch_bounds__(256) void k_smpl_bwd_skin(const float* __restrict__
         }
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int k = (q & 3) + 8 * (q >> 2) + 4 * hi;
+            const int k = mfma32_row(q, hi);
             pt[(cb * 32 + k) * kTS + col] = acc[q];
         }
     }
@@ -315,35 +277,7 @@ __global__ __launch_bounds__(64) void k_smpl_bwd_chain(const float* __restrict__
         for (int k = t; k < NB; k += 64) poison += (double)betas[(size_t)b * NB + k] * 0.0;
     if (trans && t < 3) poison += (double)trans[(size_t)b * 3 + t] * 0.0;
     if (sm && t < 3) poison += sm[PW + t] * 0.0;                        // a non-finite grad_verts entry shows in its sum
-    if (t < NJ) {
-        const float* a = pose + ((size_t)b * NJ + t) * 3;
-        poison += ((double)a[0] + (double)a[1] + (double)a[2]) * 0.0;
-        smpl_rodrigues((double)a[0], (double)a[1], (double)a[2], R + t * 9);
-        for (int c = 0; c < 3; ++c) {
-            const double* f = jfold + (size_t)(t * 3 + c) * (1 + NB);
-            double acc = f[0];
-            if (betas)
-                for (int k = 0; k < NB; ++k) acc += f[1 + k] * (double)betas[(size_t)b * NB + k];
-            J[t * 3 + c] = acc;
-        }
-    }
-    __syncthreads();
-    // the forward chain, as k_smpl_pose runs it: lane e < 12 owns entry (row, col) of the 3x4 global transform
-    const int row = (t & 15) >> 2, col = t & 3;
-    for (int j = 0; j < NJ; ++j) {
-        if (t < 12) {
-            if (j == 0) {
-                G[t] = col < 3 ? R[row * 3 + col] : J[row];
-            } else {
-                const int p = parents[j];
-                const double* gp = G + p * 12 + row * 4;
-                double g = 0.0;
-                for (int k = 0; k < 3; ++k) g += gp[k] * (col < 3 ? R[j * 9 + k * 3 + col] : J[j * 3 + k] - J[p * 3 + k]);
-                G[j * 12 + t] = col < 3 ? g : g + gp[3];
-            }
-        }
-        __syncthreads();
-    }
+    poison += smpl_kinematics(pose, betas, jfold, parents, b, t, NJ, NB, R, J, G);
     // scale and offset, skinning transforms -> gG, gJ; blend shapes -> gR
     double gq[3] = {0.0, 0.0, 0.0};
     if (t < NJ) {
@@ -453,17 +387,11 @@ extern "C" int gator_smpl_backward_f32(gator_smpl* ctx, const float* pose, const
                                        float* grad_pose, float* grad_betas, float* grad_trans, void* stream) {
     using namespace gator;
     const char* who = "gator_smpl_backward_f32";
-    if (center_idx >= 0 && trans) return fail(GATOR_EINVAL, "%s: center_idx goes with trans = NULL (the layer centres only an untranslated batch)", who);
-    GATOR_TRY(check_handle(ctx, who, "ctx"));
-    if (batch < 0 || (batch > 0 && !pose)) return fail(GATOR_EINVAL, "%s: bad pose / batch", who);
-    if (center_idx >= ctx->NJ) return fail(GATOR_EINVAL, "%s: center_idx %d, the model has %d joints", who, center_idx, ctx->NJ);
-    if (!std::isfinite(out_scale)) return fail(GATOR_EINVAL, "%s: out_scale must be finite", who);
+    GATOR_TRY(smpl_check_layer_call(who, ctx, pose, trans, batch, center_idx, out_scale));
     if (!grad_verts && !grad_joints) return fail(GATOR_EINVAL, "%s: grad_verts and grad_joints are both NULL, there is nothing to propagate", who);
-    const int tiles = (batch + kTS - 1) / kTS;
-    if (tiles > 65535) return fail(GATOR_EINVAL, "%s: batch %d above %d", who, batch, 65535 * kTS);
     if (batch == 0 || (!grad_pose && !grad_betas && !grad_trans)) return GATOR_OK;
     if (!ctx->NB) grad_betas = nullptr;
-    const int NT = ctx->NVp / kTV, PW = bwd_pw(ctx->Kq, ctx->NJ), SW = bwd_sw(ctx->Kq, ctx->NJ);
+    const int tiles = (batch + kTS - 1) / kTS, NT = ctx->NVp / kTV, PW = bwd_pw(ctx->Kq, ctx->NJ), SW = bwd_sw(ctx->Kq, ctx->NJ);
     GATOR_TRY(smpl_reserve(ctx, batch));
     hipStream_t st = (hipStream_t)stream;
     if (grad_verts) {
@@ -471,20 +399,10 @@ extern "C" int gator_smpl_backward_f32(gator_smpl* ctx, const float* pose, const
         GATOR_TRY(ctx->grow(ctx->bpart, (size_t)tiles * NT * PW * kTS));
         GATOR_TRY(ctx->grow(ctx->btrans, (size_t)tiles * NT * 3 * kTS));
         GATOR_TRY(ctx->grow(ctx->bsum, (size_t)batch * SW));
-    }
-    if (grad_verts) {
         GATOR_TRY(smpl_pose_stage(ctx, pose, betas, nullptr, batch, -1, 1.0, nullptr, st));
-        const dim3 grid(NT, tiles);
-        const size_t lds = bwd_lds_bytes(ctx->NJ);
-        if (ctx->MI <= 4)
-            k_smpl_bwd_skin<4><<<grid, 256, lds, st>>>(ctx->basis, ctx->basisT, ctx->vtempl, ctx->widx, ctx->wval, ctx->MI, ctx->coef, ctx->xform,
-                                                       grad_verts, batch, ctx->NV, ctx->NVp, ctx->NJ, ctx->Kp, ctx->Kq, out_scale, ctx->bpart,
-                                                       ctx->btrans);
-        else
-            k_smpl_bwd_skin<0><<<grid, 256, lds, st>>>(ctx->basis, ctx->basisT, ctx->vtempl, ctx->widx, ctx->wval, ctx->MI, ctx->coef, ctx->xform,
-                                                       grad_verts, batch, ctx->NV, ctx->NVp, ctx->NJ, ctx->Kp, ctx->Kq, out_scale, ctx->bpart,
-                                                       ctx->btrans);
-        GATOR_HIP_CHECK(hipGetLastError());
+        GATOR_TRY(launch_by_influences(ctx, k_smpl_bwd_skin<4>, k_smpl_bwd_skin<0>, dim3(NT, tiles), bwd_lds_bytes(ctx->NJ), st, ctx->basis,
+                                       ctx->basisT, ctx->vtempl, ctx->widx, ctx->wval, ctx->MI, ctx->coef, ctx->xform, grad_verts, batch, ctx->NV,
+                                       ctx->NVp, ctx->NJ, ctx->Kp, ctx->Kq, out_scale, ctx->bpart, ctx->btrans));
         k_smpl_bwd_reduce<<<dim3((PW + 3 + 7) / 8, tiles), 256, 0, st>>>(ctx->bpart, ctx->btrans, batch, NT, PW, SW, ctx->bsum);
         GATOR_HIP_CHECK(hipGetLastError());
     }

@@ -1,5 +1,6 @@
 // The SMPL handle (gator_smpl_*): the packed model and the workspaces of its three users, the layer (smpl_lbs.hip), the fit
-// (smpl_fit.hip) and the layer's backward (smpl_backward.hip).
+// (smpl_fit.hip) and the layer's backward (smpl_backward.hip), with the host steps their entries share.  The device steps they share
+// are in smpl_steps.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,6 +57,22 @@ __device__ inline void smpl_rodrigues(double ax, double ay, double az, double* r
     r[0] = w2 + x2 - y2 - z2; r[1] = 2 * xy - 2 * wz;    r[2] = 2 * wy + 2 * xz;
     r[3] = 2 * wz + 2 * xy;   r[4] = w2 - x2 + y2 - z2;  r[5] = 2 * yz - 2 * wx;
     r[6] = 2 * xz - 2 * wy;   r[7] = 2 * wx + 2 * yz;    r[8] = w2 - x2 - y2 + z2;
+}
+
+// What every batched entry checks first: there is a ctx on the current device, and batch lies in 0 .. max_batch.
+int smpl_check_batch(const char* who, const gator_smpl* ctx, int batch, int max_batch);
+// The arguments the forward and the backward share: center_idx only without trans, smpl_check_batch up to 65535 sample tiles, a pose
+// for a batch that is not empty, center_idx below the joint count, a finite out_scale.
+int smpl_check_layer_call(const char* who, const gator_smpl* ctx, const float* pose, const float* trans, int batch, int center_idx,
+                          float out_scale);
+
+// One launch of a kernel pair by the model's influences per vertex: the MI_T = 4 form holds at most four in registers (SMPL, MANO),
+// the MI_T = 0 form reads any number from the lists.  256 threads.
+template <class... P, class... A>
+int launch_by_influences(const gator_smpl* c, void (*k4)(P...), void (*k0)(P...), dim3 grid, size_t lds, hipStream_t st, const A&... args) {
+    (c->MI <= 4 ? k4 : k0)<<<grid, 256, lds, st>>>(args...);
+    GATOR_HIP_CHECK(hipGetLastError());
+    return GATOR_OK;
 }
 
 int smpl_reserve(gator_smpl* c, int B);                                  // the forward's workspace for a batch of B

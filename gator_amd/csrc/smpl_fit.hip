@@ -5,7 +5,7 @@
 // The iteration.  Unknowns P = 3 NJ + NB + 3: a world-frame rotation increment delta_k per joint, the betas, the translation.  The state
 // is the float32 (pose, betas, trans) the layer takes, so the answer is what the caller feeds back to gator_smpl_forward_f32.
 //   forward      k_smpl_pose at the candidate (smpl_lbs.hip): the coefficient row, the skinning transforms A_j, the posed joints p_j;
-//                the kernels here recompute v_posed = v_template + basis . coef.
+//                the kernels here recompute v_posed = v_template + basis . coef and apply A_j with the layer's smpl_affine (smpl_steps.h).
 //   residual     r_v = verts_v + trans - target_v, verts_v = sum_j w_vj x_vj, x_vj = A_j [v_posed_v ; 1] (joint j's image of the vertex)
 //   rotation     d verts_v / d delta_k = -[c_vk]x,  c_vk = sum_{j in subtree(k)} w_vj (x_vj - p_k): the per-joint images, not the blended
 //                vertex (that simpler form stalls in local minima on small meshes).  The subtree test is a bit mask of ancestors per
@@ -45,6 +45,7 @@
 
 #include "internal.h"
 #include "smpl_ctx.h"
+#include "smpl_steps.h"
 #include "so3.h"
 
 namespace gator {
@@ -55,8 +56,6 @@ constexpr int kFC = 512;            // vertices per chunk: a multiple of the lay
 constexpr int kFRows = 3 * kFV;     // rows of [J | r] per tile, 48 per wave
 constexpr int kFitMaxBatch = 65535;
 constexpr double kLambda0 = 1e-2, kLambdaMin = 1e-9, kLambdaMax = 1e6, kRidge = 1e-12;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __host__ __device__ constexpr int fit_pairs(int nt) { return nt * (nt + 1) / 2; }
 
@@ -147,9 +146,7 @@ __global__ __launch_bounds__(256) void k_smpl_fit_normal(const float* __restrict
                 vp[c] = vtempl[(size_t)c * NVp + v] + (((vpart[vl * 3 + c] + vpart[(kFV + vl) * 3 + c]) + vpart[(2 * kFV + vl) * 3 + c]) + vpart[(3 * kFV + vl) * 3 + c]);
             const int m = wave;
             const float* A = xf + (m < MI ? widx[(size_t)m * NVp + v] : 0) * 12;
-            float* o = img + (vl * 4 + m) * 3;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) o[r] = fmaf(A[r * 4], vp[0], fmaf(A[r * 4 + 1], vp[1], fmaf(A[r * 4 + 2], vp[2], A[r * 4 + 3])));
+            smpl_affine(A, vp[0], vp[1], vp[2], img + (vl * 4 + m) * 3);
         }
         __syncthreads();
         for (int it = tid; it < items; it += 256) {         // 64 consecutive items share the column group c: uniform in a wave
@@ -234,8 +231,7 @@ __global__ __launch_bounds__(256) void k_smpl_fit_normal(const float* __restrict
     for (int p = 0; p < NP; ++p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int i = (r & 3) + 8 * (r >> 2) + 4 * hi;      // C/D map of the 32x32 MFMA: register r of lane (col, hi) is row i
-            Jt[wave * 1024 + i * 32 + col] = acc[p][r];
+            Jt[wave * 1024 + mfma32_row(r, hi) * 32 + col] = acc[p][r];
         }
         __syncthreads();
 #pragma unroll
@@ -470,8 +466,7 @@ int fit_normal(gator_smpl* c, const float* pose, const float* betas, const float
 }
 
 int fit_common_checks(const char* who, gator_smpl* ctx, int batch) {
-    GATOR_TRY(check_handle(ctx, who, "ctx"));
-    if (batch < 0 || batch > kFitMaxBatch) return fail(GATOR_EINVAL, "%s: batch %d outside 0..%d", who, batch, kFitMaxBatch);
+    GATOR_TRY(smpl_check_batch(who, ctx, batch, kFitMaxBatch));
     if (ctx->MI > 4)
         return fail(GATOR_EUNSUPPORTED, "%s: the model has up to %d influences per vertex, the fit supports at most 4", who, ctx->MI);
     return GATOR_OK;
@@ -493,8 +488,7 @@ int smpl_fit_build(gator_smpl* c, const gator_smpl_model* m) {
         for (int j = 0; j < NJ; ++j)
             if (m->weights[(size_t)v * NJ + j] != 0.f) am[(size_t)(n++) * NVp + v] = anc[j];      // the order of widx / wval
     }
-    GATOR_TRY(c->amask.alloc(sizeof(uint32_t) * am.size()));
-    GATOR_HIP_CHECK(hipMemcpy(c->amask.get(), am.data(), sizeof(uint32_t) * am.size(), hipMemcpyHostToDevice));
+    GATOR_TRY(upload(c->amask, am));
     int P, NT, S;
     fit_sizes(c, &P, &NT, &S);
     const int lds = (int)normal_lds_bytes(c, NT);

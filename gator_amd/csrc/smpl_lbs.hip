@@ -1,13 +1,15 @@
 // The SMPL body-model layer (smplpytorch/pytorch/smpl_layer.py:65-158, rodrigues_layer.py:13-52) on the device, batched:
 //   (pose [B,NJ*3], betas [B,NB], trans [B,3]) -> (verts [B,NV,3], joints [B,NJ,3])
 // in two launches and without the layer's per-vertex intermediates (th_T [B,4,4,NV], v_shaped, v_posed never exist in memory).
+// The steps that the backward and the fit run as well (kinematics, coefficient tile, blend product, affine apply) are in smpl_steps.h.
 //   k_smpl_pose : one wave per sample, fp64.  Rodrigues with the reference's `+ 1e-8` inside the norm and its normalised quaternion,
-//                 the pose map R[1:] - I, the shaped rest joints from the regressor folded at create, the kinematic chain; writes the
-//                 sample's coefficient row [betas ; pose map], its NJ skinning transforms (3x4, fp32), its offset and the joints.
+//                 the pose map R[1:] - I, the shaped rest joints from the regressor folded at create, the kinematic chain (all four:
+//                 smpl_kinematics); writes the sample's coefficient row [betas ; pose map], its NJ skinning transforms (3x4, fp32), its
+//                 offset and the joints.
 //   k_smpl_skin : the hot path.  Per (32-sample, 128-vertex) tile the blend offsets [32 x K] . [K x 3 x 128] on the fp32-input MFMA
-//                 (v_mfma_f32_32x32x2_f32: exact fp32 products, a fixed fmaf chain over k), the three coordinate planes of the basis as
-//                 three accumulators, so that a lane holds x, y, z of one vertex for 16 samples; then, in registers, T = sum w A over the
-//                 vertex's (index, weight) list with the tile's transforms in LDS, T . [v_posed ; 1], offset, scale, store.
+//                 (smpl_blend; v_mfma_f32_32x32x2_f32: exact fp32 products, a fixed fmaf chain over k), the three coordinate planes of the
+//                 basis as three accumulators, so that a lane holds x, y, z of one vertex for 16 samples; then, in registers, T = sum w A
+//                 over the vertex's (index, weight) list with the tile's transforms in LDS, T . [v_posed ; 1], offset, scale, store.
 // A sample is one MFMA row and one LDS row from end to end: its result depends on no other sample of the batch, and a non-finite
 // pose or beta makes every output of its own sample non-finite and touches no other.
 #include <hip/hip_runtime.h>
@@ -18,15 +20,10 @@
 
 #include "internal.h"
 #include "smpl_ctx.h"
+#include "smpl_steps.h"
 
 namespace gator {
 namespace {
-
-constexpr int kTS = 32;      // samples per tile: the M of one 32x32x2 MFMA
-constexpr int kKU = 4;      // k-pairs per pipeline stage of the blend GEMM: K is padded to two stages, 4 kKU
-constexpr int kCoefLd = 33;  // LDS leading dimension of the transposed coefficient tile (conflict-free both ways)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(64) void k_smpl_pose(const float* __restrict__ pose, const float* __restrict__ betas, const float* __restrict__ trans,
                                                   const double* __restrict__ jfold, const int32_t* __restrict__ parents, int NJ, int NB, int K,
@@ -41,39 +38,7 @@ __global__ __launch_bounds__(64) void k_smpl_pose(const float* __restrict__ pose
         poison += (double)cf[k] * 0.0;
     }
     for (int k = K + t; k < Kp; k += 64) cf[k] = 0.f;
-    if (t < NJ) {
-        const float* a = pose + ((size_t)b * NJ + t) * 3;
-        const double ax = a[0], ay = a[1], az = a[2];
-        poison += (ax + ay + az) * 0.0;
-        double* r = R + t * 9;
-        smpl_rodrigues(ax, ay, az, r);
-        if (t >= 1)
-            for (int e = 0; e < 9; ++e) cf[NB + (t - 1) * 9 + e] = (float)(r[e] - ((e & 3) == 0 ? 1.0 : 0.0));      // subtract_flat_id
-        for (int c = 0; c < 3; ++c) {
-            const double* f = jfold + (size_t)(t * 3 + c) * (1 + NB);
-            double acc = f[0];
-            if (betas)
-                for (int k = 0; k < NB; ++k) acc += f[1 + k] * (double)betas[(size_t)b * NB + k];
-            J[t * 3 + c] = acc;
-        }
-    }
-    __syncthreads();
-    // the chain, joint by joint (parents[j] < j); lane e < 12 owns entry (row, col) of the 3x4 global transform
-    const int row = (t & 15) >> 2, col = t & 3;
-    for (int j = 0; j < NJ; ++j) {
-        if (t < 12) {
-            if (j == 0) {
-                G[t] = col < 3 ? R[row * 3 + col] : J[row];
-            } else {
-                const int p = parents[j];
-                const double* gp = G + p * 12 + row * 4;
-                double g = 0.0;
-                for (int k = 0; k < 3; ++k) g += gp[k] * (col < 3 ? R[j * 9 + k * 3 + col] : J[j * 3 + k] - J[p * 3 + k]);
-                G[j * 12 + t] = col < 3 ? g : g + gp[3];
-            }
-        }
-        __syncthreads();
-    }
+    poison += smpl_kinematics(pose, betas, jfold, parents, b, t, NJ, NB, R, J, G, cf + NB);
     // A non-finite root rotation leaves the root joint finite and a non-finite elbow its ancestors (the reference's behaviour); here the
     // whole sample is marked instead: the flag, summed over the wave, rides on the offset that every joint and vertex receives.
     for (int d = 32; d > 0; d >>= 1) poison += __shfl_xor(poison, d);
@@ -102,46 +67,11 @@ __global__ __launch_bounds__(256) void k_smpl_skin(const float* __restrict__ bas
     const int s0 = blockIdx.y * kTS, v0 = blockIdx.x * kTV;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 31, hi = lane >> 5;
     const int ns = min(kTS, B - s0);
-    for (int e = threadIdx.x; e < kTS * Kp; e += 256) {                 // the tile's coefficient rows, transposed: lds[k][sample]
-        const int s = e / Kp, k = e - s * Kp;
-        lds[k * kCoefLd + s] = s < ns ? coef[(size_t)(s0 + s) * Kp + k] : 0.f;
-    }
+    smpl_coef_tile(coef, s0, ns, Kp, lds);
     __syncthreads();
     const int v = v0 + wave * 32 + col;                                 // < NVp: the planes are padded to whole tiles
-    const size_t plane = (size_t)Kp * NVp;
-    const float* bp = basis + v;
     f32x16 ax = {0}, ay = {0}, az = {0};
-    // A[i = sample][k], B[k][j = vertex]: lane (col, hi) feeds k + hi.  A stage is kKU k-pairs = twelve MFMAs; two register sets
-    // take turns, each loaded a whole stage (768 cycles of matrix work) before it is used.
-    float pa[kKU], px_[kKU], py_[kKU], pz_[kKU], qa[kKU], qx[kKU], qy[kKU], qz[kKU];
-    auto fetch = [&](int k, float (&a)[kKU], float (&x)[kKU], float (&y)[kKU], float (&z)[kKU]) {
-#pragma unroll
-        for (int u = 0; u < kKU; ++u) {
-            const int kk = k + 2 * u + hi;
-            const size_t o = (size_t)kk * NVp;
-            a[u] = lds[kk * kCoefLd + col];
-            x[u] = bp[o]; y[u] = bp[o + plane]; z[u] = bp[o + 2 * plane];
-        }
-    };
-    auto mma = [&](const float (&a)[kKU], const float (&x)[kKU], const float (&y)[kKU], const float (&z)[kKU]) {
-#pragma unroll
-        for (int u = 0; u < kKU; ++u) {
-            ax = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], x[u], ax, 0, 0, 0);
-            ay = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], y[u], ay, 0, 0, 0);
-            az = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], z[u], az, 0, 0, 0);
-        }
-    };
-    fetch(0, pa, px_, py_, pz_);
-    for (int k = 0; k < Kp; k += 4 * kKU) {                              // Kp is a multiple of two stages
-        fetch(k + 2 * kKU, qa, qx, qy, qz);
-        __builtin_amdgcn_sched_barrier(0);                              // keep the loads ahead of the stage they overlap
-        mma(pa, px_, py_, pz_);
-        __builtin_amdgcn_sched_barrier(0);
-        fetch(min(k + 4 * kKU, Kp - 2 * kKU), pa, px_, py_, pz_);       // after the last stage: an in-bounds fetch nobody uses
-        __builtin_amdgcn_sched_barrier(0);
-        mma(qa, qx, qy, qz);
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    smpl_blend(lds, basis + v, NVp, Kp, col, hi, ax, ay, az);
     __syncthreads();                                                    // the coefficient tile is done with: the transforms take its place
     const int nxf = ns * NJ * 12;
     const float* xs = xform + (size_t)s0 * NJ * 12;
@@ -162,7 +92,7 @@ __global__ __launch_bounds__(256) void k_smpl_skin(const float* __restrict__ bas
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int i = (r & 3) + 8 * (r >> 2) + 4 * hi;                  // C/D map of the 32x32 MFMA: register r of lane (col, hi) is row i
+        const int i = mfma32_row(r, hi);
         if (i >= ns) continue;
         const float* xi = lds + i * NJ * 12;
         float T[12];
@@ -187,26 +117,17 @@ __global__ __launch_bounds__(256) void k_smpl_skin(const float* __restrict__ bas
                 for (int e = 0; e < 12; ++e) T[e] = fmaf(w, qq[e], T[e]);
             }
         }
-        const float px = tx + ax[r], py = ty + ay[r], pz = tz + az[r];   // v_posed = v_template + blend offsets
-        const float x = fmaf(T[0], px, fmaf(T[1], py, fmaf(T[2], pz, T[3])));
-        const float y = fmaf(T[4], px, fmaf(T[5], py, fmaf(T[6], pz, T[7])));
-        const float z = fmaf(T[8], px, fmaf(T[9], py, fmaf(T[10], pz, T[11])));
+        float x[3];
+        smpl_affine(T, tx + ax[r], ty + ay[r], tz + az[r], x);          // v_posed = v_template + blend offsets
         float* o = verts + ((size_t)(s0 + i) * NV + v) * 3;             // 32 lanes x 12 bytes: 384 contiguous bytes per sample
-        o[0] = (x + lo[i * 4]) * out_scale;
-        o[1] = (y + lo[i * 4 + 1]) * out_scale;
-        o[2] = (z + lo[i * 4 + 2]) * out_scale;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = (x[c] + lo[i * 4 + c]) * out_scale;
     }
 }
 
 size_t skin_lds_bytes(const gator_smpl* c) {
-    const size_t a = (size_t)c->Kp * kCoefLd, b = (size_t)kTS * c->NJ * 12 + kTS * 4;
+    const size_t a = (size_t)c->Kp * kLd, b = (size_t)kTS * c->NJ * 12 + kTS * 4;
     return sizeof(float) * (a > b ? a : b);
-}
-
-template <class T> int upload(DevBuf<T>& d, const std::vector<T>& h) {
-    GATOR_TRY(d.alloc(sizeof(T) * (h.empty() ? 1 : h.size())));
-    if (!h.empty()) GATOR_HIP_CHECK(hipMemcpy(d.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-    return GATOR_OK;
 }
 
 int smpl_build(gator_smpl* c, const gator_smpl_model* m) {
@@ -259,6 +180,22 @@ int smpl_build(gator_smpl* c, const gator_smpl_model* m) {
 }
 
 }  // namespace
+
+int smpl_check_batch(const char* who, const gator_smpl* ctx, int batch, int max_batch) {
+    GATOR_TRY(check_handle(ctx, who, "ctx"));
+    if (batch < 0 || batch > max_batch) return fail(GATOR_EINVAL, "%s: batch %d outside 0..%d", who, batch, max_batch);
+    return GATOR_OK;
+}
+
+int smpl_check_layer_call(const char* who, const gator_smpl* ctx, const float* pose, const float* trans, int batch, int center_idx,
+                          float out_scale) {
+    if (center_idx >= 0 && trans) return fail(GATOR_EINVAL, "%s: center_idx goes with trans = NULL (the layer centres only an untranslated batch)", who);
+    GATOR_TRY(smpl_check_batch(who, ctx, batch, 65535 * kTS));          // the sample tiles are the grid's y
+    if (batch > 0 && !pose) return fail(GATOR_EINVAL, "%s: pose is NULL", who);
+    if (center_idx >= ctx->NJ) return fail(GATOR_EINVAL, "%s: center_idx %d, the model has %d joints", who, center_idx, ctx->NJ);
+    if (!std::isfinite(out_scale)) return fail(GATOR_EINVAL, "%s: out_scale must be finite", who);
+    return GATOR_OK;
+}
 
 int smpl_reserve(gator_smpl* c, int B) {
     if (B <= c->cap) return GATOR_OK;
@@ -316,27 +253,14 @@ extern "C" int gator_smpl_workspace(const gator_smpl* ctx, const void** base, in
 extern "C" int gator_smpl_forward_f32(gator_smpl* ctx, const float* pose, const float* betas, const float* trans, int32_t batch,
                                       int32_t center_idx, float out_scale, float* verts, float* joints, void* stream) {
     using namespace gator;
-    if (center_idx >= 0 && trans) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: center_idx goes with trans = NULL (the layer centres only an untranslated batch)");
-    GATOR_TRY(check_handle(ctx, "gator_smpl_forward_f32", "ctx"));
-    if (batch < 0 || (batch > 0 && !pose)) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: bad pose / batch");
-    if (center_idx >= ctx->NJ) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: center_idx %d, the model has %d joints", center_idx, ctx->NJ);
-    if (!std::isfinite(out_scale)) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: out_scale must be finite");
-    const int tiles = (batch + kTS - 1) / kTS;
-    if (tiles > 65535) return fail(GATOR_EINVAL, "gator_smpl_forward_f32: batch %d above %d", batch, 65535 * kTS);
+    GATOR_TRY(smpl_check_layer_call("gator_smpl_forward_f32", ctx, pose, trans, batch, center_idx, out_scale));
     if (batch == 0) return GATOR_OK;
     GATOR_TRY(smpl_reserve(ctx, batch));
     hipStream_t st = (hipStream_t)stream;
     GATOR_TRY(smpl_pose_stage(ctx, pose, betas, trans, batch, center_idx, (double)out_scale, joints, st));
-    if (verts) {
-        const dim3 grid(ctx->NVp / kTV, tiles);
-        const size_t lds = skin_lds_bytes(ctx);
-        if (ctx->MI <= 4)
-            k_smpl_skin<4><<<grid, 256, lds, st>>>(ctx->basis, ctx->vtempl, ctx->widx, ctx->wval, ctx->MI, ctx->coef, ctx->xform, ctx->offs,
-                                                   batch, ctx->NV, ctx->NVp, ctx->NJ, ctx->Kp, out_scale, verts);
-        else
-            k_smpl_skin<0><<<grid, 256, lds, st>>>(ctx->basis, ctx->vtempl, ctx->widx, ctx->wval, ctx->MI, ctx->coef, ctx->xform, ctx->offs,
-                                                   batch, ctx->NV, ctx->NVp, ctx->NJ, ctx->Kp, out_scale, verts);
-        GATOR_HIP_CHECK(hipGetLastError());
-    }
+    if (verts)
+        GATOR_TRY(launch_by_influences(ctx, k_smpl_skin<4>, k_smpl_skin<0>, dim3(ctx->NVp / kTV, (batch + kTS - 1) / kTS), skin_lds_bytes(ctx), st,
+                                       ctx->basis, ctx->vtempl, ctx->widx, ctx->wval, ctx->MI, ctx->coef, ctx->xform, ctx->offs, batch, ctx->NV,
+                                       ctx->NVp, ctx->NJ, ctx->Kp, out_scale, verts));
     return GATOR_OK;
 }

@@ -89,10 +89,8 @@ class _LayerFunction(torch.autograd.Function):
             gv = None if gv is None else gv.contiguous().float()
             gj = None if gj is None else gj.contiguous().float()
             ptr = _lib.ptr
-            with torch.cuda.device(layer.device):
-                _lib.check(_lib.load().gator_smpl_backward_f32(layer._ctx, ptr(pose), ptr(betas), ptr(trans), B, ctx.center, ctx.out_scale,
-                                                               ptr(gv), ptr(gj), ptr(g_pose), ptr(g_betas), ptr(g_trans),
-                                                               _lib.stream_ptr(layer.device)), 'gator_smpl_backward_f32')
+            layer._call('gator_smpl_backward_f32', ptr(pose), ptr(betas), ptr(trans), B, ctx.center, ctx.out_scale, ptr(gv), ptr(gj), ptr(g_pose),
+                        ptr(g_betas), ptr(g_trans), _lib.stream_ptr(layer.device))
         return None, None, None, None, None, g_pose, g_betas, g_trans
 
 
@@ -146,16 +144,21 @@ class SMPLLayer(_lib.DeviceHandle):
     def from_pkl(cls, path, **kw):
         return cls(**read_pkl(path), **kw)
 
+    def _call(self, name, *args):
+        """The C entry `name` on this layer's ctx, with the layer's device current; a failure raises with the library's message."""
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(_lib.load(), name)(self._ctx, *args), name)
+
     def workspace(self):
         """(device address, batch capacity) of the ctx's workspace: a test hook."""
         base, cap = ctypes.c_void_p(), ctypes.c_int64()
-        _lib.check(_lib.load().gator_smpl_workspace(self._ctx, ctypes.byref(base), ctypes.byref(cap)), 'gator_smpl_workspace')
+        self._call('gator_smpl_workspace', ctypes.byref(base), ctypes.byref(cap))
         return base.value or 0, cap.value
 
     def workspace_bytes(self):
         """(bytes held by the ctx's grown blocks, growths since create): a test hook; a repeated call at a known batch moves neither."""
         b, n = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(_lib.load().gator_smpl_workspace_bytes(self._ctx, ctypes.byref(b), ctypes.byref(n)), 'gator_smpl_workspace_bytes')
+        self._call('gator_smpl_workspace_bytes', ctypes.byref(b), ctypes.byref(n))
         return b.value, n.value
 
     def _arg(self, x, width, name, B):
@@ -186,9 +189,8 @@ class SMPLLayer(_lib.DeviceHandle):
         verts = torch.empty((B, self.num_verts, 3), device=self.device, dtype=torch.float32) if want_verts else None
         joints = torch.empty((B, self.num_joints, 3), device=self.device, dtype=torch.float32) if want_joints else None
         ptr = _lib.ptr
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().gator_smpl_forward_f32(self._ctx, ptr(pose), ptr(betas), ptr(trans), B, center, out_scale, ptr(verts),
-                                                          ptr(joints), _lib.stream_ptr(self.device)), 'gator_smpl_forward_f32')
+        self._call('gator_smpl_forward_f32', ptr(pose), ptr(betas), ptr(trans), B, center, out_scale, ptr(verts), ptr(joints),
+                   _lib.stream_ptr(self.device))
         return verts, joints
 
     __call__ = forward
@@ -196,7 +198,7 @@ class SMPLLayer(_lib.DeviceHandle):
     def fit_width(self):
         """(P, N): the fit's unknowns, 3 NJ + NB + 3, and the padded width of its normal matrix."""
         P, N = ctypes.c_int32(), ctypes.c_int32()
-        _lib.check(_lib.load().gator_smpl_fit_width(self._ctx, ctypes.byref(P), ctypes.byref(N)), 'gator_smpl_fit_width')
+        self._call('gator_smpl_fit_width', ctypes.byref(P), ctypes.byref(N))
         return P.value, N.value
 
     def _verts_arg(self, verts):
@@ -229,9 +231,8 @@ class SMPLLayer(_lib.DeviceHandle):
         pose, betas, trans, rms = (torch.empty(shape, device=self.device, dtype=torch.float32)
                                    for shape in ((B, self.num_joints * 3), (B, self.num_betas), (B, 3), (B,)))
         ptr = _lib.ptr
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().gator_smpl_fit_f32(self._ctx, ptr(verts), ptr(ip), ptr(ib), ptr(it), B, int(iters), ptr(pose), ptr(betas),
-                                                      ptr(trans), ptr(rms), _lib.stream_ptr(self.device)), 'gator_smpl_fit_f32')
+        self._call('gator_smpl_fit_f32', ptr(verts), ptr(ip), ptr(ib), ptr(it), B, int(iters), ptr(pose), ptr(betas), ptr(trans), ptr(rms),
+                   _lib.stream_ptr(self.device))
         return pose, betas, trans, rms
 
     def fit_normal(self, pose, betas, trans, verts):
@@ -245,9 +246,7 @@ class SMPLLayer(_lib.DeviceHandle):
         N = self.fit_width()[1]
         M = torch.zeros((B, N, N), device=self.device, dtype=torch.float32)
         ptr = _lib.ptr
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().gator_smpl_fit_normal_f32(self._ctx, ptr(pose), ptr(betas), ptr(trans), ptr(verts), B, ptr(M),
-                                                             _lib.stream_ptr(self.device)), 'gator_smpl_fit_normal_f32')
+        self._call('gator_smpl_fit_normal_f32', ptr(pose), ptr(betas), ptr(trans), ptr(verts), B, ptr(M), _lib.stream_ptr(self.device))
         return M
 
 

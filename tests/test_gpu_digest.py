@@ -83,12 +83,15 @@ def test_caller_side_digests_match_the_recorded_build():
 HANDLES_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'handle_digests.json')
 
 
-@pytest.mark.parametrize('lib', ['renderer', 'draw2d', 'smpl', 'fit'])
+@pytest.mark.parametrize('lib', ['renderer', 'draw2d', 'smpl', 'fit', 'backward'])
 def test_handle_digests_match_the_recorded_build(lib):
     """The auxiliary libraries behind a handle bit for bit against the build recorded before their host scaffolding (growth rule, staged
     table, handle checks) was stated once in csrc/handle.h: small seeded calls of every entry point, and per handle a small call, the
     largest and the small one again, whose digests must not depend on the handle's history and whose workspace() tuples (bytes and
-    allocation counts, the SMPL capacity) are the recorded ones (tools/ab_digest.py: handle_digests)."""
+    allocation counts, the SMPL capacity) are the recorded ones (tools/ab_digest.py: handle_digests).  Every 'backward' key was
+    recorded before the SMPL kernels' shared device steps moved into csrc/smpl_steps.h: gator_smpl_backward_f32 at B = 1 and 33 on three
+    vertex tiles, every upstream subset, centring, an output subset, and 24 influences per vertex (the looped MI_T = 0 kernels) in
+    both directions; the layer's dense forward is in this group so that the earlier groups keep their key sets."""
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from tools.ab_digest import HANDLE_LIBS, handle_digests

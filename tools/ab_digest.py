@@ -11,7 +11,7 @@
   * `--encoder --write tests/golden/encoder_form_digests.json` does the same for encoder_digests(): every form of the GAT encoder kernels
     (k_gat8, k_gat, k_gat_tiled, the tail launches, the stand-alone encoder entry, the block taps) at batches the fp32 digests never reach.
   * `--handles --write tests/golden/handle_digests.json` does the same for handle_digests(): the auxiliary libraries behind a handle (mesh
-    renderer, 2D overlay, SMPL layer and fit) on small seeded shapes, with each handle's workspace() after a small, the largest and the small
+    renderer, 2D overlay, SMPL layer, fit and backward) on small seeded shapes, with each handle's workspace() after a small, the largest and the small
     call again.
 python tools/ab_digest.py [tag] [--forms | --caller | --encoder | --handles] [--write path [--commit hash-of-the-recorded-build]]"""
 import contextlib, hashlib, json, os, sys
@@ -318,7 +318,7 @@ def caller_digests():
 # The auxiliary libraries' handles (render.hip, draw2d.hip, smpl_lbs.hip, smpl_fit.hip): small seeded calls, and per handle the sequence
 # small call / largest call / small call again with the workspace() tuple after each, so that the host side of a handle (growth rule,
 # staged tables, accounting) is pinned against the build that recorded the file.
-HANDLE_LIBS = ('renderer', 'draw2d', 'smpl', 'fit')
+HANDLE_LIBS = ('renderer', 'draw2d', 'smpl', 'fit', 'backward')
 HANDLE_SMPL_CASE = 'nv257'
 
 
@@ -443,11 +443,60 @@ def _fit_digests(out):
     out['fit sequence small'], out['fit sequence workspace'] = seq[0], ws
 
 
+def _grad_case(name):
+    """A golden case as tests/test_gpu_smpl_backward.py takes it: (make a layer, device inputs with None for the absent ones,
+    device upstream gradients (grad_verts, grad_joints))."""
+    from gator_amd import smpl
+    from tests import smpl_grad_refs as gr, smpl_refs
+    m = smpl_refs.synthetic_model(*smpl_refs.CASES[name][0])
+    make = lambda: smpl.SMPLLayer.from_arrays(m['v_template'], m['shapedirs'], m['posedirs'], m['weights'], m['J_regressor'], m['parents'])  # noqa: E731
+    ins = tuple(None if a is None else torch.from_numpy(a).cuda() for a in gr.case_arguments(name))
+    return make, ins, tuple(torch.from_numpy(a).cuda() for a in gr.upstream(name))
+
+
+def _backward(layer, ins, ups, B, which='full', center=-1, needs=(True, True, True)):
+    """gator_smpl_backward_f32 itself on the first B samples -> the digest of the gradients that were asked for."""
+    from gator_amd import _lib
+    from tests import smpl_grad_refs as gr
+    ins = [None if a is None else a[:B].contiguous() for a in ins]
+    gV, gJ = gr.select_upstream(which, *(g[:B].contiguous() for g in ups))
+    outs = [torch.full_like(a, 7.0) if (a is not None and n) else None for a, n in zip(ins, needs)]
+    ptr = _lib.ptr
+    _lib.check(_lib.load().gator_smpl_backward_f32(layer._ctx, ptr(ins[0]), ptr(ins[1]), ptr(ins[2]), B, center, 1.0, ptr(gV), ptr(gJ),
+                                                   ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), _lib.stream_ptr(layer.device)),
+               'gator_smpl_backward_f32')
+    return _sha_canon(*(o for o in outs if o is not None))
+
+
+def _backward_digests(out):
+    """B = 1 and 33 (one lane of a sample tile; a full tile and a one-sample tile), nv257 (three vertex tiles, the last nearly all padding)
+    and dense (24 influences: the looped MI_T = 0 kernels), every upstream subset, centring, an output subset, the workspace's growth."""
+    make, ins, ups = _grad_case(HANDLE_SMPL_CASE)
+    layer = make()
+    seq, ws = [], []
+    for B in (1, 33, 1):
+        seq.append(_backward(layer, ins, ups, B))
+        ws.append(list(layer.workspace_bytes()))
+    for B in (1, 33):
+        out['backward %s B=%d full' % (HANDLE_SMPL_CASE, B)] = seq[0] if B == 1 else seq[1]
+        for which in ('verts', 'joints'):
+            out['backward %s B=%d %s' % (HANDLE_SMPL_CASE, B, which)] = _backward(layer, ins, ups, B, which)
+    out['backward %s B=33 full center_idx=3' % HANDLE_SMPL_CASE] = _backward(layer, (ins[0], ins[1], None), ups, 33, center=3)
+    out['backward %s B=33 full grad_pose only' % HANDLE_SMPL_CASE] = _backward(layer, ins, ups, 33, needs=(True, False, False))
+    dmake, dins, dups = _grad_case('dense')
+    out['backward dense B=33 full'] = _backward(dmake(), dins, dups, 33)
+    # the layer's own looped kernel (k_smpl_skin<0>), verts + joints; kept in this group: the 'smpl' group's keys are the set recorded before
+    out['backward dense B=33 forward'] = _sha_canon(*dmake()(*(a[:33] for a in dins)))
+    fresh = _backward(make(), ins, ups, 1)
+    assert seq[0] == seq[2] == fresh, 'the SMPL backward depends on its workspace history'
+    out['backward sequence small'], out['backward sequence workspace'] = seq[0], ws
+
+
 def handle_digests(libs=None):
     """{'<library> <case>': digest, '<library> sequence workspace': the workspace() tuple after each of the three calls}."""
     out = {}
     for lib in (libs or HANDLE_LIBS):
-        {'renderer': _renderer_digests, 'draw2d': _draw2d_digests, 'smpl': _smpl_digests, 'fit': _fit_digests}[lib](out)
+        {'renderer': _renderer_digests, 'draw2d': _draw2d_digests, 'smpl': _smpl_digests, 'fit': _fit_digests, 'backward': _backward_digests}[lib](out)
     torch.cuda.synchronize()
     return out
 
@@ -459,9 +508,9 @@ def main_handles():
         print('%-56s %s' % (k, h), flush=True)
     if write:
         commit = sys.argv[sys.argv.index('--commit') + 1] if '--commit' in sys.argv else 'unknown'
-        what = ('sha256[:32] of the raw output bytes of the auxiliary libraries (tools/ab_digest.py: handle_digests: renderer, draw2d, SMPL layer '
-                'and fit), gfx950, NaNs canonicalised, seeded inputs; "sequence workspace": workspace() after a small, the largest and the small '
-                'call again on one handle (SMPL: [capacity, block replaced]).  Recorded with the library of commit %s' % commit)
+        what = ('sha256[:32] of the raw output bytes of the auxiliary libraries (tools/ab_digest.py: handle_digests: renderer, draw2d, SMPL layer, '
+                'fit and backward), gfx950, NaNs canonicalised, seeded inputs; "sequence workspace": workspace() after a small, the largest and '
+                'the small call again on one handle (SMPL: [capacity, block replaced]; backward: [bytes, allocations]).  Recorded with the library of commit %s' % commit)
         with open(write, 'w') as f:
             json.dump({'what': what, 'digests': d}, f, indent=1)
 
