@@ -383,12 +383,12 @@ int fused_create(gator_ctx* c, void* stream) {
     float* up = take(n_up);
     if (f->opt.up_x3 == 2) {
         GATOR_TRY(f->up_w2.alloc(upsample_x2_weight_elems() * 2));
-        int rc = pack_upsample_x2(w.up_w, f->up_w2, &f->up_w2_unscale, stream);
+        int rc = pack_upsample_any(Regressor::X2, w.up_w, f->up_w2, &f->up_w2_unscale, stream);
         if (rc == GATOR_OK) rc = upsample_x2_prepare_device();
         if (rc) return rc;
     } else if (f->opt.up_x3 == 1) {
         GATOR_TRY(f->up_w3.alloc(upsample_x3_weight_elems() * 2));
-        int rc = pack_upsample_x3(w.up_w, f->up_w3, stream);
+        int rc = pack_upsample_any(Regressor::X3, w.up_w, f->up_w3, nullptr, stream);
         if (rc) return rc;
     } else {
         for (int tap = 0; tap < 3; ++tap) {
@@ -530,10 +530,6 @@ void fused_destroy(gator_ctx* c) {
     c->fused = nullptr;
 }
 
-int launch_upsample_any(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const RegressorPlan& r, int B, float* verts, void* stream) {
-    return r.form == Regressor::FP32 ? launch_upsample(f, c, ws, B, verts, stream) : r.form == Regressor::X2 ? launch_upsample_x2(f, c, ws, B, verts, stream, r.with_joints, r.w1) : launch_upsample_x3(f, c, ws, B, verts, stream, r.with_joints);
-}
-
 // The plan of one call on this ctx (forward_plan.h), or GATOR_EUNSUPPORTED with the planner's reason: before anything is queued
 static int fused_plan(const gator_ctx* c, int B, PlanEntry entry, bool bf16, bool with_joints, ForwardPlan* p) {
     const FusedState* f = c->fused;
@@ -553,9 +549,7 @@ int fused_upsample(gator_ctx* c, const float* vert431, int B, float* verts, void
     FusedWs& ws = f->sets[0];
     GATOR_TRY(fused_ensure_ws(c, ws, B));
     const RegressorPlan r = plan_regressor(f->opt, false, false);
-    int rc = r.form == Regressor::FP32 ? launch_pack_vc(vert431, B, ws.vcp, stream)
-         : r.form == Regressor::X2 ? launch_pack_vc_x2(vert431, B, ws.vcp3, stream) : launch_pack_vc_x3(vert431, B, ws.cap, ws.vcp3, stream);
-    if (rc) return rc;
+    GATOR_TRY(launch_pack_vc_any(r, vert431, B, ws, stream));
     StageTimer tm(c, "upsample", stream);
     return launch_upsample_any(f, c, ws, r, B, verts, stream);
 }
@@ -565,7 +559,7 @@ static int fused_upsample_bf16_in(gator_ctx* c, FusedWs& ws, const float* vert43
     FusedState* f = c->fused;
     if (!f->up_w16) {      // first bf16 call: pack the regressor weights once
         GATOR_TRY(f->up_w16.alloc(upsample_bf16_weight_elems() * 2));
-        GATOR_TRY(pack_upsample_bf16(c->w.up_w, f->up_w16, stream));
+        GATOR_TRY(pack_upsample_any(Regressor::BF16, c->w.up_w, f->up_w16, nullptr, stream));
         // One-time: the pack must be COMPLETE before any other stream may read up_w16.  In sub-batch mode the second half
         // runs on a different (non-blocking) stream whose fork event was recorded before this pack was queued.
         GATOR_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
@@ -576,7 +570,9 @@ static int fused_upsample_bf16_in(gator_ctx* c, FusedWs& ws, const float* vert43
         ws.vcp16_cap = B;
     }
     StageTimer tm(c, "upsample_bf16", stream);
-    return launch_upsample_bf16(f, c, ws, vert431, B, verts, stream);
+    const RegressorPlan r{Regressor::BF16, false, false};
+    GATOR_TRY(launch_pack_vc_any(r, vert431, B, ws, stream));
+    return launch_upsample_any(f, c, ws, r, B, verts, stream);
 }
 
 int fused_upsample_bf16(gator_ctx* c, const float* vert431, int B, float* verts, void* stream) {

@@ -379,6 +379,15 @@ __device__ __forceinline__ void glds(const float* gsrc, const float* lds_dst) {
                      : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
 }
 
+// The same copy for one whole 1 KiB fragment (16 bytes per lane) with a wave-uniform base in SGPRs and one per-lane byte offset
+// (k_upsample_x2), and the wait of whoever reads what such copies wrote: at most N of this wave's VMEM operations still in flight.
+__device__ __forceinline__ void dma_frag(const void* base, unsigned lane_off, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(lane_off), "s"(base), "s"(lds_dst) : "memory");
+}
+template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
 // XCD-aware bijective remap of a 1-D grid: blocks that share an XCD (equal blockIdx % 8) get CONTIGUOUS logical ids,
 // so the workgroups of one sample hit one L2.  Speed only -- never correctness (cdna_hip_programming.md T1).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

@@ -26,14 +26,11 @@ __global__ void k_repack_x3(const float* __restrict__ src, __bf16* __restrict__ 
     if (e >= total) return;
     const int jj = e & 7, lane = (e >> 3) & 63, s = (e >> 9) & 1;
     const int64_t tile = e >> 10;
-    const float x = src[tile * kTile + ((2 * s + (jj >> 2)) * 64 + lane) * 4 + (jj & 3)];
-    const __bf16 h = (__bf16)x;
-    const float r = x - (float)h;
-    const __bf16 m = (__bf16)r;
+    const Split3<__bf16> q = split3<__bf16>(src[tile * kTile + ((2 * s + (jj >> 2)) * 64 + lane) * 4 + (jj & 3)]);
     __bf16* d = dst + tile * (2 * kTileX3) + (s * 64 + lane) * 8 + jj;
-    d[0] = h;
-    d[1024] = m;
-    d[2048] = (__bf16)(r - (float)m);
+    d[0] = q.h;
+    d[1024] = q.m;
+    d[2048] = q.l();
 }
 // H3 tile [plane][s][lane][jj] <- three fp16 planes of scale * (fp32 tile element)
 __global__ void k_repack_h3(const float* __restrict__ src, _Float16* __restrict__ dst, int64_t total, float scale) {
@@ -41,14 +38,11 @@ __global__ void k_repack_h3(const float* __restrict__ src, _Float16* __restrict_
     if (e >= total) return;
     const int jj = e & 7, lane = (e >> 3) & 63, s = (e >> 9) & 1;
     const int64_t tile = e >> 10;
-    const float x = src[tile * kTile + ((2 * s + (jj >> 2)) * 64 + lane) * 4 + (jj & 3)] * scale;
-    const _Float16 h = (_Float16)x;
-    const float r = x - (float)h;
-    const _Float16 m = (_Float16)r;
+    const Split3<_Float16> q = split3<_Float16>(src[tile * kTile + ((2 * s + (jj >> 2)) * 64 + lane) * 4 + (jj & 3)] * scale);
     _Float16* d = dst + tile * (2 * kTileX3) + (s * 64 + lane) * 8 + jj;
-    d[0] = h;
-    d[1024] = m;
-    d[2048] = (_Float16)(r - (float)m);
+    d[0] = q.h;
+    d[1024] = q.m;
+    d[2048] = q.l();
 }
 // out[tile] = max |w| of that tile; one 256-thread block per tile
 __global__ void k_absmax_per_tile(const float* __restrict__ w, float* __restrict__ out) {
@@ -80,14 +74,7 @@ int fused_repack_h3(const float* src_tiles, float* dst_tiles, int64_t ntiles, in
         if (m > wmax) wmax = m;
         if (m > 0.f && (wmin == 0.f || m < wmin)) wmin = m;
     }
-    int sh = 0;
-    if (wmax > 0.f && std::isfinite(wmax)) {
-        int e;
-        (void)std::frexp(wmax, &e);              // wmax 2^(14 - e) in [2^13, 2^14)
-        sh = 14 - e;
-        if (sh > 24) sh = 24;
-        if (sh < -16) sh = -16;
-    }
+    const int sh = pow2_shift_below_2_14(wmax, -16, 24);
     *shift = sh;
     *tile_ratio = wmax > 0.f ? wmin / wmax : 1.f;
     if (!h3_set_holds(*tile_ratio)) return GATOR_OK;      // the caller takes the form without a shared scale

@@ -2,12 +2,11 @@
 #pragma once
 #include "internal.h"
 #include "forward_plan.h"
+#include "regressor_slots.h"            // kOB, kCB, kS16, the vertex regressor's operand layouts and their sizes
 #include <vector>
 
 namespace gator {
 
-constexpr int kOB = 216;                // 32-vertex output blocks of the upsample GEMM (6890 -> 6912)
-constexpr int kCB = 14;                 // 32-wide k blocks over the 431 coarse vertices
 constexpr int kTile = 32 * 32;          // floats in one packed 32x32 tile ([4 g][64 lanes][4])
 // words of k_mdr_persist's counters for a forward of B samples: per launch a 32-word header (tickets, error flag) + 4 counts per sample
 __host__ __device__ inline size_t mdr_ctr_words(int B) { return (size_t)32 * kMdrCtrChunks + (size_t)4 * B; }
@@ -136,9 +135,6 @@ inline void h3_demote(FusedState* f, int set) {
 int fused_pack_linear(const float* W, int64_t wsn, int64_t wsk, int N, int K, float* dst, void* stream);   // -> [NB][KB] tiles
 inline int nblk32(int n) { return (n + 31) / 32; }
 // The launchers execute their part of a ForwardPlan (forward_plan.h) on the workspace set they are handed; none reads a switch to choose a kernel.
-// upsample_fused.hip
-int launch_pack_vc(const float* vc, int B, float* vcp, void* stream);
-int launch_upsample(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream);
 // gat_fused.hip
 int gat_prepare_device();
 int gat_ensure_blk_tap(gator_ctx* c, FusedState* f, int B);
@@ -154,26 +150,12 @@ int launch_gat_tiled(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan
 // gat_tail.hip
 size_t gat_tail_part_floats(int B, int J);
 int launch_gat_tail(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pose2d, float* x_out, void* stream);  // lifter + MDR joint tokens of samples 0 .. p.n_tail
-// upsample_bf16.hip
-size_t upsample_bf16_weight_elems();
-size_t upsample_bf16_vcp_elems(int B);
-int pack_upsample_bf16(const float* up_w, void* dst, void* stream);
-int launch_upsample_bf16(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const float* vc, int B, float* verts, void* stream);
-// upsample_x3.hip
-size_t upsample_x3_weight_elems();
-size_t upsample_x3_vcp_elems(int B);
-int pack_upsample_x3(const float* up_w, void* dst, void* stream);
-int launch_pack_vc_x3(const float* vc, int B, int cap, void* vcp3, void* stream);
-int launch_upsample_x3(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream, bool with_joints);
-int launch_jreg_reduce(const FusedState* f, int B, float* joints, void* stream);
-// upsample_x2.hip
-size_t upsample_x2_weight_elems();
-size_t upsample_x2_vcp_elems(int B);
+// The vertex regressor (upsample_common.h states the row; the entries are in upsample_fused.hip): every form through one pack and one launch entry
+int pack_upsample_any(Regressor form, const float* up_w, void* dst, float* unscale, void* stream);      // the packed weights of X3 | X2 | BF16 (FP32: fused_pack_linear)
 int upsample_x2_prepare_device();
-int pack_upsample_x2(const float* up_w, void* dst, float* unscale, void* stream);
-int launch_pack_vc_x2(const float* vc, int B, void* vcp2, void* stream);
-int launch_upsample_x2(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream, bool with_joints, bool w1);
-int launch_upsample_any(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const RegressorPlan& r, int B, float* verts, void* stream);      // fp32-input MFMA | bf16 x 3 | fp16 x 2 (the bf16 kernel: fused_api.hip)
+int launch_pack_vc_any(const RegressorPlan& r, const float* vc, int B, const FusedWs& ws, void* stream);      // vc -> ws.vcp | ws.vcp3 | ws.vcp16
+int launch_upsample_any(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const RegressorPlan& r, int B, float* verts, void* stream);
+int launch_jreg_reduce(const FusedState* f, int B, float* joints, void* stream);
 // mdr_fused.hip: the joint tokens (pc, the MDR entry point; else x_out and pose2d of the whole forward), the layers and the head, as p says; the first
 // and the last through mdr_head.hip's launchers below
 int launch_mdr(gator_ctx* c, FusedState* f, FusedWs& ws, const ForwardPlan& p, const float* pc, int B, void* stream, const float* x_out, const float* pose2d);

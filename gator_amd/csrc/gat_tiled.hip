@@ -254,8 +254,8 @@ __global__ __launch_bounds__(256, 1) void k_gat_tiled(const TiledArgs a) {
     };
     auto begin_group = [&]() -> const float* {      // -> ring slot holding the group that begins now
         // vmcnt retires in order: all but this wave's 6 youngest copies (group gk+1) done  =>  its pieces of group gk have landed
-        if (gk + 1 < kDepth * kGroupsPerBlock) { if constexpr (NP == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (gk + 1 < kDepth * kGroupsPerBlock) wait_vm<NP == 6 ? 6 : 4>();
+        else wait_vm<0>();
         __syncthreads();                            // ... and so have everybody's; slot (gk+2) % 3 (group gk-1) is free
         issue(gk + 2);
         const float* slot = RING + (gk % kRing) * kRingSlot;

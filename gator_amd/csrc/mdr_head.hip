@@ -37,7 +37,9 @@ __device__ __forceinline__ void head_report(const HeadArgs& a, int b, bool bad, 
                            __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// where a coarse vertex coordinate goes: the reference layout (tap / stage API) and the packed A operand of whichever vertex GEMM the ctx runs
+// where a coarse vertex coordinate goes: the reference layout (tap / stage API) and the packed A operand of whichever vertex GEMM the ctx runs.
+// The three layouts are regressor_slots.h's act_slot_x2 / act_slot_b16 / act_slot_f32 and the splits x3_common.h's split2 / split3, restated:
+// written with those functions k_mdr_head_finish and both k_mdr_head<512, .> compile to other listings (profiles/refactor_regressor.txt)
 __device__ __forceinline__ void head_store(const HeadArgs& a, int b, int v, int c, float val) {
     const int mt = b >> 5, sl = b & 31;
     a.vc[((size_t)b * kV + v) * 3 + c] = val;
@@ -318,7 +320,8 @@ __global__ __launch_bounds__(NT, HOIST ? 2 : 4) void k_mdr_head(const HeadArgs a
     if (tok) {
         if (!HOIST) load_rows();
         // (the softmax-mix and the store below are head_finish's, and stay written out here: as functions shared with head_finish they change
-        // k_mdr_head_finish's instructions -- head_store's second caller alone does, profiles/refactor_mdr_forms.txt)
+        // k_mdr_head_finish's instructions -- head_store's second caller alone does, profiles/refactor_mdr_forms.txt.  The layouts below are
+        // regressor_slots.h's, restated as in head_store.)
         float av[20];
 #pragma unroll
         for (int g = 0; g < 5; ++g) { av[4 * g] = row[g][0]; av[4 * g + 1] = row[g][1]; av[4 * g + 2] = row[g][2]; av[4 * g + 3] = row[g][3]; }

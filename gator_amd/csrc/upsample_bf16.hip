@@ -11,32 +11,6 @@
 namespace gator {
 namespace {
 
-// dst[tap][ob][s][lane][j] = bf16( w[32ob + (lane&31)][16s + 8(lane>>5) + j][tap] )
-__global__ void k_pack_up_bf16(const float* __restrict__ w, __bf16* __restrict__ dst, int64_t total) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    const int j = e & 7, lane = (e >> 3) & 63;
-    int64_t r = e >> 9;
-    const int s = r % kS16; r /= kS16;
-    const int ob = r % kOB;
-    const int tap = (int)(r / kOB);
-    const int o = 32 * ob + (lane & 31), c = 16 * s + 8 * (lane >> 5) + j;
-    dst[e] = (o < kNV && c < kV) ? (__bf16)w[((int64_t)o * kV + c) * 3 + tap] : (__bf16)0.f;
-}
-
-// vcp[mt][l'][s][lane][j] = bf16( vc[32mt + (lane&31)][16s + 8(lane>>5) + j][l'] )
-__global__ void k_pack_vc_bf16(const float* __restrict__ vc, int B, __bf16* __restrict__ vcp, int64_t total) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    const int j = e & 7, lane = (e >> 3) & 63;
-    int64_t r = e >> 9;
-    const int s = r % kS16; r /= kS16;
-    const int lp = r % 3;
-    const int mt = (int)(r / 3);
-    const int smp = 32 * mt + (lane & 31), c = 16 * s + 8 * (lane >> 5) + j;
-    vcp[e] = (smp < B && c < kV) ? (__bf16)vc[((int64_t)smp * kV + c) * 3 + lp] : (__bf16)0.f;
-}
-
 __global__ __launch_bounds__(256) void k_upsample_bf16(const __bf16* __restrict__ vcp, const __bf16* __restrict__ wp,
                                                        const float* __restrict__ bias, const float* __restrict__ tpl,
                                                        float* __restrict__ out, int B, int MT, int nwg) {
@@ -61,7 +35,7 @@ __global__ __launch_bounds__(256) void k_upsample_bf16(const __bf16* __restrict_
         const bf16x8 w0 = wq[o], w1 = wq[w_tap + o], w2 = wq[2 * w_tap + o];
         const bf16x8 x0 = a0p[o], x1 = a0p[a_lp + o], x2 = a0p[2 * a_lp + o];
         const bf16x8 y0 = a1p[o], y1 = a1p[a_lp + o], y2 = a1p[2 * a_lp + o];
-        // out l gets input l' = l + k - 1 ; A = samples (rows), B = vertices (cols)
+        // the tap list (regressor_slots.h: kRegTaps) written out, two sample tiles interleaved; A = samples (rows), B = vertices (cols)
         acc[0][0] = GATOR_MFMA_BF16(x0, w1, acc[0][0]);
         acc[1][0] = GATOR_MFMA_BF16(y0, w1, acc[1][0]);
         acc[0][1] = GATOR_MFMA_BF16(x0, w0, acc[0][1]);
@@ -77,44 +51,14 @@ __global__ __launch_bounds__(256) void k_upsample_bf16(const __bf16* __restrict_
         acc[0][1] = GATOR_MFMA_BF16(x2, w2, acc[0][1]);
         acc[1][1] = GATOR_MFMA_BF16(y2, w2, acc[1][1]);
     }
-    const int ov = 32 * ob + (lane & 31), h = lane >> 5;
-    if (ov >= kNV) return;
-    const float bo = bias[ov];
-    const float t0 = tpl[ov * 3], t1 = tpl[ov * 3 + 1], t2 = tpl[ov * 3 + 2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        if (m == 1 && mt1 == mt0) break;
-        const int mt = m ? mt1 : mt0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int smp = 32 * mt + kap(r) + 4 * h;
-            if (smp < B) {
-                F3 v;
-                v.x = (acc[m][0][r] + bo) + t0;
-                v.y = (acc[m][1][r] + bo) + t1;
-                v.z = (acc[m][2][r] + bo) + t2;
-                *reinterpret_cast<F3*>(out + ((int64_t)smp * kNV + ov) * 3) = v;
-            }
-        }
-    }
+    const int mts[2] = {mt0, mt1};
+    regress_finish<false>(ob, mts, mt1 == mt0 ? 1 : 2, true, lane, B, bias, tpl, out, JregEpi{}, [&](int m, int l, int r) { return acc[m][l][r]; });
 }
 
 }  // namespace
 
-size_t upsample_bf16_weight_elems() { return (size_t)3 * kOB * kS16 * 512; }
-size_t upsample_bf16_vcp_elems(int B) { return (size_t)((B + 31) / 32) * 3 * kS16 * 512; }
-
-int pack_upsample_bf16(const float* up_w, void* dst, void* stream) {
-    const int64_t total = (int64_t)upsample_bf16_weight_elems();
-    k_pack_up_bf16<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(up_w, (__bf16*)dst, total);
-    GATOR_HIP_CHECK(hipGetLastError());
-    return GATOR_OK;
-}
-
-int launch_upsample_bf16(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const float* vc, int B, float* verts, void* stream) {
+int launch_upsample_bf16(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream) {
     const int MT = (B + 31) / 32;
-    const int64_t total = (int64_t)upsample_bf16_vcp_elems(B);
-    k_pack_vc_bf16<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(vc, B, (__bf16*)ws.vcp16.get(), total);
     const int MP = (MT + 1) / 2;
     const int nwg = kOB * ((MP + 3) / 4);
     k_upsample_bf16<<<nwg, 256, 0, (hipStream_t)stream>>>((const __bf16*)ws.vcp16.get(), (const __bf16*)f->up_w16.get(), c->w.up_b, c->w.v6890,

@@ -12,19 +12,6 @@
 namespace gator {
 namespace {
 
-// vcp[mt][l'][cb][g][lane][j] = vc[32mt + (lane&31)][32cb + 8g + 4(lane>>5) + j][l']   (zero padded)
-__global__ void k_pack_vc(const float* __restrict__ vc, int B, float* __restrict__ vcp, int64_t total) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    const int j = e & 3, lane = (e >> 2) & 63, g = (e >> 8) & 3;
-    int64_t r = e >> 10;
-    const int cb = r % kCB; r /= kCB;
-    const int lp = r % 3;
-    const int mt = (int)(r / 3);
-    const int s = 32 * mt + (lane & 31), c = 32 * cb + 8 * g + 4 * (lane >> 5) + j;
-    vcp[e] = (s < B && c < kV) ? vc[((int64_t)s * kV + c) * 3 + lp] : 0.f;
-}
-
 // NT = 32-sample tiles per wave that share each weight fragment.  NT = 2 (64 samples x 32 vertices x 3 coords) halves the
 // weight traffic and, at B=256, gives 864 waves - at most one per SIMD, so no co-resident partner competes for the MFMA pipe
 // (142 -> 107 us); NT = 1 keeps small batches spread over the chip.
@@ -37,10 +24,11 @@ __global__ __launch_bounds__(256, 1) void k_upsample(const float* __restrict__ v
     const int MP = (MT + NT - 1) / NT, mgroups = (MP + 3) >> 2;
     const int ob = wg / mgroups, mp = (wg % mgroups) * 4 + wave;
     if (mp >= MP) return;
-    int mt[NT];
+    int mt[NT], nt = 0;
     const f32x4* a_base[NT];
 #pragma unroll
     for (int m = 0; m < NT; ++m) {
+        if (NT * mp + m < MT) nt = m + 1;
         mt[m] = NT * mp + m < MT ? NT * mp + m : NT * mp;        // ragged tail: repeat the first tile (its result is not stored)
         a_base[m] = reinterpret_cast<const f32x4*>(vcp) + ((size_t)mt[m] * 3 * kCB * 4) * 64 + lane;
     }
@@ -77,8 +65,8 @@ __global__ __launch_bounds__(256, 1) void k_upsample(const float* __restrict__ v
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                // out l gets input l' = l + k - 1 (the zero-padding taps are never multiplied); ordered so that consecutive
-                // MFMAs never write the same accumulator
+                // the tap list (regressor_slots.h: kRegTaps) written out in another issue order: consecutive MFMAs never write
+                // the same accumulator
 #pragma unroll
                 for (int m = 0; m < NT; ++m) acc[m][0] = GATOR_MFMA(x[m][0][j], w[1][j], acc[m][0]);
 #pragma unroll
@@ -107,38 +95,12 @@ __global__ __launch_bounds__(256, 1) void k_upsample(const float* __restrict__ v
 #pragma unroll
             for (int l = 0; l < 3; ++l) { tot[m][l] += acc[m][l]; acc[m][l] = zero16(); }
     }
-    const int o = 32 * ob + (lane & 31), h = lane >> 5;
-    if (o >= kNV) return;
-    const float bo = bias[o];
-    const float t0 = tpl[o * 3] , t1 = tpl[o * 3 + 1], t2 = tpl[o * 3 + 2];
-#pragma unroll
-    for (int m = 0; m < NT; ++m) {
-        if (m > 0 && NT * mp + m >= MT) break;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int s = 32 * mt[m] + kap(r) + 4 * h;
-            if (s < B) {
-                F3 v;
-                v.x = (tot[m][0][r] + bo) + t0;     // conv output (+bias) first, then the template add: MDR.py:167-168
-                v.y = (tot[m][1][r] + bo) + t1;
-                v.z = (tot[m][2][r] + bo) + t2;
-                *reinterpret_cast<F3*>(out + ((int64_t)s * kNV + o) * 3) = v;
-            }
-        }
-    }
+    regress_finish<false>(ob, mt, nt, true, lane, B, bias, tpl, out, JregEpi{}, [&](int m, int l, int r) { return tot[m][l][r]; });
 }
 
 }  // namespace
 
-int launch_pack_vc(const float* vc, int B, float* vcp, void* stream) {
-    const int MT = (B + 31) / 32;
-    const int64_t total = (int64_t)MT * 3 * kCB * kTile;
-    k_pack_vc<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(vc, B, vcp, total);
-    GATOR_HIP_CHECK(hipGetLastError());
-    return GATOR_OK;
-}
-
-int launch_upsample(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream) {
+int launch_upsample_f32(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream) {
     const int MT = (B + 31) / 32;
     if (MT >= 8) {          // >= 225 samples: two tiles per wave
         const int MP = (MT + 1) / 2, nwg = kOB * ((MP + 3) / 4);
@@ -150,6 +112,39 @@ int launch_upsample(const FusedState* f, const gator_ctx* c, const FusedWs& ws, 
     k_upsample<1><<<nwg, 256, 0, (hipStream_t)stream>>>(ws.vcp, f->up_w, c->w.up_b, c->w.v6890, verts, B, MT, nwg);
     GATOR_HIP_CHECK(hipGetLastError());
     return GATOR_OK;
+}
+
+// ---- the row's entries: every form of the packed operands and of the launch, chosen by the plan (forward_plan.h) -------------------------
+// upsample_conv.weight [6890][431][3] -> the form's packed weights; *unscale: what undoes the two-plane form's operand scalings.  (The
+// fp32 form's weights are fused_pack_linear's tile grids, one per tap.)
+int pack_upsample_any(Regressor form, const float* up_w, void* dst, float* unscale, void* stream) {
+    if (form == Regressor::X2) return pack_upsample_x2(up_w, dst, unscale, stream);
+    if (form == Regressor::X3) return pack_operand<__bf16, 3, false, w_slot_b16>(up_w, kNV, 32 * kOB, dst, upsample_x3_weight_elems() / 3, 1.f, stream);
+    if (form == Regressor::BF16) return pack_operand<__bf16, 1, false, w_slot_b16>(up_w, kNV, 32 * kOB, dst, 0, 1.f, stream);
+    return fail(GATOR_EINVAL, "pack_upsample_any: no packed weight form");
+}
+
+// vc [B][431][3] -> the A operand of the plan's kernel in ws.  The three-plane form's planes are strided by the workspace capacity, so
+// padding written once stays valid for every smaller batch
+int launch_pack_vc_any(const RegressorPlan& r, const float* vc, int B, const FusedWs& ws, void* stream) {
+    const int pad32 = (B + 31) / 32 * 32;
+    switch (r.form) {
+    case Regressor::FP32: return pack_operand<float, 1, false, act_slot_f32>(vc, B, pad32, ws.vcp, 0, 1.f, stream);
+    case Regressor::X3: return pack_operand<__bf16, 3, false, act_slot_b16>(vc, B, pad32, ws.vcp3, upsample_x3_vcp_elems(ws.cap) / 3, 1.f, stream);
+    case Regressor::X2: return pack_operand<_Float16, 2, true, act_slot_x2>(vc, B, (B + 127) / 128 * 128, ws.vcp3, kX2Plane, (float)(1 << kActShift), stream);
+    case Regressor::BF16: return pack_operand<__bf16, 1, false, act_slot_b16>(vc, B, pad32, ws.vcp16.get(), 0, 1.f, stream);
+    default: return fail(GATOR_EINVAL, "launch_pack_vc_any: no regressor planned");
+    }
+}
+
+int launch_upsample_any(const FusedState* f, const gator_ctx* c, const FusedWs& ws, const RegressorPlan& r, int B, float* verts, void* stream) {
+    switch (r.form) {
+    case Regressor::FP32: return launch_upsample_f32(f, c, ws, B, verts, stream);
+    case Regressor::X3: return launch_upsample_x3(f, c, ws, B, verts, stream, r.with_joints);
+    case Regressor::X2: return launch_upsample_x2(f, c, ws, B, verts, stream, r.with_joints, r.w1);
+    case Regressor::BF16: return launch_upsample_bf16(f, c, ws, B, verts, stream);
+    default: return fail(GATOR_EINVAL, "launch_upsample_any: no regressor planned");
+    }
 }
 
 }  // namespace gator

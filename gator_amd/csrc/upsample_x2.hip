@@ -25,49 +25,6 @@ namespace gator {
 namespace {
 
 constexpr int kNBuf = 4, kStageFrags = 36;          // 1 KiB fragments per stage: [mt 4][lp 3][plane 2] then [ob 2][tap 3][plane 2]
-constexpr int kActShift = 4;                        // activations x 2^4
-
-__device__ __forceinline__ void split2(float x, _Float16& h, _Float16& l) {
-    h = (_Float16)x;
-    l = (_Float16)(x - (float)h);
-}
-
-// wp[ob pair][s][ob 2][tap 3][plane 2][lane][8] <- split2( scale * w[32 ob + (lane&31)][16 s + 8 (lane>>5) + j][tap] )
-__global__ void k_pack_up_x2(const float* __restrict__ w, _Float16* __restrict__ dst, int64_t n_frag_pairs, float scale) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;      // one element of one (hi, lo) fragment pair
-    if (e >= n_frag_pairs * 512) return;
-    const int j = e & 7, lane = (e >> 3) & 63;
-    int64_t r = e >> 9;
-    const int tap = r % 3; r /= 3;
-    const int o2 = r & 1; r >>= 1;
-    const int s = r % kS16;
-    const int op = (int)(r / kS16);
-    const int o = 32 * (2 * op + o2) + (lane & 31), c = 16 * s + 8 * (lane >> 5) + j;
-    const float x = (o < kNV && c < kV) ? w[((int64_t)o * kV + c) * 3 + tap] * scale : 0.f;
-    _Float16 h, l;
-    split2(x, h, l);
-    const int64_t pair = (((int64_t)op * kS16 + s) * 2 + o2) * 3 + tap;
-    dst[(pair * 2 + 0) * 512 + lane * 8 + j] = h;
-    dst[(pair * 2 + 1) * 512 + lane * 8 + j] = l;
-}
-// ap[mt / 4][s][mt % 4][lp 3][plane 2][lane][8] <- split2( 2^4 * vc[32 mt + (lane&31)][16 s + 8 (lane>>5) + j][lp] )
-__global__ void k_pack_vc_x2(const float* __restrict__ vc, int B, _Float16* __restrict__ ap, int64_t n_frag_pairs) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n_frag_pairs * 512) return;
-    const int j = e & 7, lane = (e >> 3) & 63;
-    int64_t r = e >> 9;
-    const int lp = r % 3; r /= 3;
-    const int mi = r & 3; r >>= 2;
-    const int s = r % kS16;
-    const int mg = (int)(r / kS16);
-    const int smp = 32 * (4 * mg + mi) + (lane & 31), c = 16 * s + 8 * (lane >> 5) + j;
-    const float x = (smp < B && c < kV) ? vc[((int64_t)smp * kV + c) * 3 + lp] * (float)(1 << kActShift) : 0.f;
-    _Float16 h, l;
-    split2(x, h, l);
-    const int64_t pair = (((int64_t)mg * kS16 + s) * 4 + mi) * 3 + lp;
-    ap[(pair * 2 + 0) * 512 + lane * 8 + j] = h;
-    ap[(pair * 2 + 1) * 512 + lane * 8 + j] = l;
-}
 
 __global__ void k_absmax(const float* __restrict__ w, int64_t n, unsigned* __restrict__ out) {
     float m = 0.f;
@@ -82,16 +39,7 @@ __global__ void k_absmax(const float* __restrict__ w, int64_t n, unsigned* __res
     if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));      // non-negative floats (and NaN above inf) order as unsigned
 }
 
-// one 1 KiB fragment global -> LDS without registers: wave-uniform base in SGPRs, one per-lane byte offset.  Inline asm on
-// purpose: hipcc counts the builtin form in its vmcnt bookkeeping and drains it before the next LDS access (gat_tiled.hip).
-__device__ __forceinline__ void dma_frag(const void* base, unsigned lane_off, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(lane_off), "s"(base), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// Joint-regression epilogue: upsample_common.h (JregEpi; the same order of operations on the finished vertex as upsample_x3.hip).
+// The copies: fused_common.h (dma_frag, wait_vm).  The joint-regression tables: upsample_common.h (JregEpi).
 // WLO = false (BASELINE config 3, the 16-bit operand mode): the weights' lo plane is not used -- weights on ONE fp16 plane, coarse vertices on two:
 // two MFMAs per product instead of three (0.35 mm max / 0.06 mm rms by the emulation: profiles/r05_emulate_16bit.txt)
 template <bool WLO = true>
@@ -165,14 +113,13 @@ __global__ __launch_bounds__(512, 1) void k_upsample_x2(const _Float16* __restri
         if (s + 3 < kS16) issue(s + 3);
         load_rest(s);
         if (live) {
-            // out[l] += x[lp] * w[k] with l = lp + 1 - k (MDR.py:167, padding 1): grouped by input position, taps descending, so
-            // every accumulator sees tap order 0, 1, 2 within a k-step -- the order of upsample_x3.hip
+            // out[l] += x[lp] * w[k] over the tap list (regressor_slots.h: kRegTaps)
 #pragma unroll
             for (int lp = 0; lp < 3; ++lp)
 #pragma unroll
-                for (int k = 2; k >= 0; --k) {
-                    const int l = lp + 1 - k;
-                    if (l < 0 || l > 2) continue;
+                for (int t = 0; t < 7; ++t) {
+                    if (kRegTaps[t].lp != lp) continue;
+                    const int k = kRegTaps[t].k, l = kRegTaps[t].l;
                     big[l] = GATOR_MFMA_F16(a[lp][0], w[k][0], big[l]);      // hi*hi
                     if constexpr (WLO) sm[l] = GATOR_MFMA_F16(a[lp][0], w[k][1], sm[l]);        // hi*lo
                     sm[l] = GATOR_MFMA_F16(a[lp][1], w[k][0], sm[l]);        // lo*hi
@@ -186,6 +133,9 @@ __global__ __launch_bounds__(512, 1) void k_upsample_x2(const _Float16* __restri
         }
         if (s + 1 < kS16) load_first(s + 1);
     }
+    // regress_finish<true> (upsample_common.h) written out, with (tot + sm) * unscale as its sum: called as the function this kernel's
+    // epilogue compiles to the same instruction count with two scalar address chains in the other order, and the `upsample` stage timer of
+    // the B = 256 forward read 42.5 .. 44.8 us against the parent's 41.9 .. 42.0 (profiles/refactor_regressor.txt, section 5)
     const int ov = 32 * ob + (lane & 31), h = lane >> 5;
     if (ov >= kNV || !live) return;
     const float bo = bias[ov];
@@ -217,9 +167,6 @@ constexpr size_t kX2Lds = (size_t)kNBuf * kStageFrags * 1024;      // 144 KiB
 
 }  // namespace
 
-size_t upsample_x2_weight_elems() { return (size_t)(kOB / 2) * kS16 * 12 * 512; }                    // fp16 elements
-size_t upsample_x2_vcp_elems(int B) { return (size_t)((B + 127) / 128) * kS16 * 24 * 512; }           // fp16 elements
-
 int upsample_x2_prepare_device() {
     GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_upsample_x2<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kX2Lds));
     GATOR_HIP_CHECK(hipFuncSetAttribute((const void*)k_upsample_x2<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kX2Lds));
@@ -241,31 +188,13 @@ int pack_upsample_x2(const float* up_w, void* dst, float* unscale, void* stream)
     float wmax;
     static_assert(sizeof(wmax) == sizeof(bits), "float bits");
     memcpy(&wmax, &bits, sizeof(wmax));
-    int shift = 0;
-    if (wmax > 0.f && std::isfinite(wmax)) {
-        int e;
-        (void)std::frexp(wmax, &e);                  // wmax = m * 2^e, m in [0.5, 1)  ->  wmax * 2^(14 - e) in [2^13, 2^14)
-        shift = 14 - e;
-        // the clamps only keep 2^shift and the epilogue's 2^-(shift + 4) normal floats; every fp32 weight image with max|w| >= 2^-104
-        // gets its full scale (a tighter clamp leaves small weights fp16-subnormal: finite results with a few bits of the weights)
-        if (shift > 118) shift = 118;
-        if (shift < -118) shift = -118;
-    }
-    const int64_t pairs = (int64_t)upsample_x2_weight_elems() / 1024;
-    k_pack_up_x2<<<(unsigned)((pairs * 512 + 255) / 256), 256, 0, st>>>(up_w, (_Float16*)dst, pairs, std::ldexp(1.0f, shift));
-    GATOR_HIP_CHECK(hipGetLastError());
+    // the clamps only keep 2^shift and the epilogue's 2^-(shift + 4) normal floats; every fp32 weight image with max|w| >= 2^-104
+    // gets its full scale (a tighter clamp leaves small weights fp16-subnormal: finite results with a few bits of the weights)
+    const int shift = pow2_shift_below_2_14(wmax, -118, 118);
     *unscale = std::ldexp(1.0f, -(shift + kActShift));
-    return GATOR_OK;
+    return pack_operand<_Float16, 2, true, w_slot_x2>(up_w, kNV, 32 * kOB, dst, kX2Plane, std::ldexp(1.0f, shift), stream);
 }
 
-int launch_pack_vc_x2(const float* vc, int B, void* vcp2, void* stream) {
-    const int64_t pairs = (int64_t)upsample_x2_vcp_elems(B) / 1024;
-    k_pack_vc_x2<<<(unsigned)((pairs * 512 + 255) / 256), 256, 0, (hipStream_t)stream>>>(vc, B, (_Float16*)vcp2, pairs);
-    GATOR_HIP_CHECK(hipGetLastError());
-    return GATOR_OK;
-}
-
-// verts == nullptr: vertices are not stored (joint regression only); with_joints: also fill f->jr_P for launch_jreg_reduce
 int launch_upsample_x2(const FusedState* f, const gator_ctx* c, const FusedWs& ws, int B, float* verts, void* stream, bool with_joints, bool w1) {
     const int MT = (B + 31) / 32, MG = (MT + 3) / 4;
     const JregEpi jr = jreg_epi(f, with_joints);

@@ -10,50 +10,12 @@
 namespace gator {
 namespace {
 
-__device__ __forceinline__ void split3(float x, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)x;
-    const float r = x - (float)h;
-    m = (__bf16)r;
-    l = (__bf16)(r - (float)m);
-}
-
-// dst[plane][tap][ob][s][lane][j] <- split3( w[32ob + (lane&31)][16s + 8(lane>>5) + j][tap] )
-__global__ void k_pack_up_x3(const float* __restrict__ w, __bf16* __restrict__ dst, int64_t plane_elems) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= plane_elems) return;
-    const int j = e & 7, lane = (e >> 3) & 63;
-    int64_t r = e >> 9;
-    const int s = r % kS16; r /= kS16;
-    const int ob = r % kOB;
-    const int tap = (int)(r / kOB);
-    const int o = 32 * ob + (lane & 31), c = 16 * s + 8 * (lane >> 5) + j;
-    const float x = (o < kNV && c < kV) ? w[((int64_t)o * kV + c) * 3 + tap] : 0.f;
-    __bf16 h, m, l;
-    split3(x, h, m, l);
-    dst[e] = h; dst[plane_elems + e] = m; dst[2 * plane_elems + e] = l;
-}
-// vcp[plane][mt][l'][s][lane][j]
-__global__ void k_pack_vc_x3(const float* __restrict__ vc, int B, __bf16* __restrict__ vcp, int64_t n, int64_t plane_elems) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int j = e & 7, lane = (e >> 3) & 63;
-    int64_t r = e >> 9;
-    const int s = r % kS16; r /= kS16;
-    const int lp = r % 3;
-    const int mt = (int)(r / 3);
-    const int smp = 32 * mt + (lane & 31), c = 16 * s + 8 * (lane >> 5) + j;
-    const float x = (smp < B && c < kV) ? vc[((int64_t)smp * kV + c) * 3 + lp] : 0.f;
-    __bf16 h, m, l;
-    split3(x, h, m, l);
-    vcp[e] = h; vcp[plane_elems + e] = m; vcp[2 * plane_elems + e] = l;
-}
-
 // One workgroup = one 32-vertex output tile x up to 8 sample tiles (one per compute wave) + ONE LOADER WAVE.
 // The 9 weight fragments of a k-step (3 taps x 3 planes, 9 KiB; the 54 MB weight stream comes from HBM) are fetched by
 // the loader wave four k-steps ahead into a register ring and handed to the compute waves through a double-buffered LDS
 // stage: its vmcnt queue is its own, so the compute waves' (L2-resident) activation prefetch never queues behind an
 // HBM miss (vmcnt retires in order).  Each compute wave register-prefetches its 9 activation fragments one step ahead.
-// Joint-regression epilogue: upsample_common.h (JregEpi).
+// The finished vertex and the joint-regression epilogue: upsample_common.h (regress_finish).
 constexpr int kX3Waves = 8, kX3Ring = 4;
 __global__ __launch_bounds__(64 * (kX3Waves + 1), 1) void k_upsample_x3(const __bf16* __restrict__ vcp, const __bf16* __restrict__ wp,
                                                                        const float* __restrict__ bias, const float* __restrict__ tpl,
@@ -124,9 +86,9 @@ __global__ __launch_bounds__(64 * (kX3Waves + 1), 1) void k_upsample_x3(const __
 #pragma unroll
         for (int lp = 0; lp < 3; ++lp) {
 #pragma unroll
-            for (int k = 2; k >= 0; --k) {             // l = lp + 1 - k ascending <=> k descending; accumulators are independent
-                const int l = lp + 1 - k;
-                if (l < 0 || l > 2) continue;
+            for (int t = 0; t < 7; ++t) {              // this input position's taps of the list (regressor_slots.h: kRegTaps); accumulators are independent
+                if (kRegTaps[t].lp != lp) continue;
+                const int k = kRegTaps[t].k, l = kRegTaps[t].l;
                 const bf16x8 w0 = wl[cur][3 * k + 0][lane], w1 = wl[cur][3 * k + 1][lane], w2 = wl[cur][3 * k + 2][lane];
                 big[l] = GATOR_MFMA_BF16(x[lp][0], w0, big[l]);      // hi*hi
                 sm[l] = GATOR_MFMA_BF16(x[lp][0], w1, sm[l]);        // hi*mid
@@ -166,31 +128,8 @@ __global__ __launch_bounds__(64 * (kX3Waves + 1), 1) void k_upsample_x3(const __
 #pragma unroll
             for (int j = 0; j < 4; ++j) big[l][4 * g + j] += v4[j];
         }
-    const int ov = 32 * ob + (lane & 31), h = lane >> 5;
-    if (ov >= kNV || !live) return;
-    const float bo = bias[ov];
-    const float t0 = tpl[ov * 3], t1 = tpl[ov * 3 + 1], t2 = tpl[ov * 3 + 2];
-    const int2 jb = jr.P ? jr.blk[ob] : int2{0, 0};           // regressor entries of this vertex block (most blocks have none)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int smp = 32 * mt + kap(r) + 4 * h;
-        if (smp < B) {
-            F3 v;
-            v.x = ((big[0][r] + sm[0][r]) + bo) + t0;
-            v.y = ((big[1][r] + sm[1][r]) + bo) + t1;
-            v.z = ((big[2][r] + sm[2][r]) + bo) + t2;
-            if (out) *reinterpret_cast<F3*>(out + ((int64_t)smp * kNV + ov) * 3) = v;
-            for (int e = jb.x; e < jb.x + jb.y; ++e) {
-                const int2 en = jr.ent[e];
-                if (en.x == ov) {
-                    const float we = jr.w[e];
-                    F3 q;
-                    q.x = we * v.x; q.y = we * v.y; q.z = we * v.z;
-                    *reinterpret_cast<F3*>(jr.P + ((int64_t)smp * jr.nnz + en.y) * 3) = q;
-                }
-            }
-        }
-    }
+    const int mts[1] = {mt};
+    regress_finish<true>(ob, mts, 1, live, lane, B, bias, tpl, out, jr, [&](int, int l, int r) { return big[l][r] + sm[l][r]; });
 }
 
 // joints[b][j][c] = sum of joint j's entries of P[b], ascending vertex order, accumulated in fp64
@@ -205,24 +144,6 @@ __global__ void k_jreg_reduce(const float* __restrict__ P, const int* __restrict
 }
 
 }  // namespace
-
-size_t upsample_x3_weight_elems() { return (size_t)3 * 3 * kOB * kS16 * 512; }                 // bf16 elements, 3 planes
-size_t upsample_x3_vcp_elems(int B) { return (size_t)3 * ((B + 31) / 32) * 3 * kS16 * 512; }      // bf16 elements, 3 planes
-
-int pack_upsample_x3(const float* up_w, void* dst, void* stream) {
-    const int64_t w_plane = (int64_t)upsample_x3_weight_elems() / 3;
-    k_pack_up_x3<<<(unsigned)((w_plane + 255) / 256), 256, 0, (hipStream_t)stream>>>(up_w, (__bf16*)dst, w_plane);
-    GATOR_HIP_CHECK(hipGetLastError());
-    return GATOR_OK;
-}
-
-// planes are `cap`-strided (the workspace capacity), so padding written once stays valid for every smaller batch
-int launch_pack_vc_x3(const float* vc, int B, int cap, void* vcp3, void* stream) {
-    const int64_t a_plane = (int64_t)upsample_x3_vcp_elems(cap) / 3, n = (int64_t)upsample_x3_vcp_elems(B) / 3;
-    k_pack_vc_x3<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(vc, B, (__bf16*)vcp3, n, a_plane);
-    GATOR_HIP_CHECK(hipGetLastError());
-    return GATOR_OK;
-}
 
 int launch_jreg_reduce(const FusedState* f, int B, float* joints, void* stream) {
     const int64_t n = (int64_t)B * f->jr_nj * 3;

@@ -14,6 +14,8 @@
 #pragma once
 #include "fused_common.h"
 
+#include <cmath>
+
 namespace gator {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -23,19 +25,34 @@ constexpr int kTileX3 = 1536;       // floats-equivalent of one X3 operand tile
 
 struct X3 { bf16x8 p[3][2]; };      // [plane hi/mid/lo][k-step]: 24 VGPRs
 
+// The plane splits of one value, the only statement of them: x = h + l (two planes of T, rounded) and x = h + m + l (three planes; exact
+// for T = __bf16).  Every packer, x2_split / x3_split below, the MDR head and fused_pack.hip split with these.
+// (l() forms the last plane where it is stored, as the kernels' listings were recorded: the MDR kernels move on the order of these lines.)
+template <class T> struct Split2 {
+    float x; T h;
+    __device__ __forceinline__ T l() const { return (T)(x - (float)h); }
+};
+template <class T> struct Split3 {
+    float r; T h, m;
+    __device__ __forceinline__ T l() const { return (T)(r - (float)m); }
+};
+template <class T = _Float16> __device__ __forceinline__ Split2<T> split2(float x) { return {x, (T)x}; }
+template <class T> __device__ __forceinline__ Split3<T> split3(float x) {
+    const T h = (T)x;
+    const float r = x - (float)h;
+    return {r, h, (T)r};
+}
+
 __device__ __forceinline__ X3 x3_split(const f32x16& v) {
     X3 o;
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float x = v[8 * s + j];
-            const __bf16 h = (__bf16)x;
-            const float r = x - (float)h;
-            const __bf16 m = (__bf16)r;
-            o.p[0][s][j] = h;
-            o.p[1][s][j] = m;
-            o.p[2][s][j] = (__bf16)(r - (float)m);
+            const Split3<__bf16> q = split3<__bf16>(v[8 * s + j]);
+            o.p[0][s][j] = q.h;
+            o.p[1][s][j] = q.m;
+            o.p[2][s][j] = q.l();
         }
     return o;
 }
@@ -91,10 +108,9 @@ __device__ __forceinline__ X2 x2_split(const f32x16& v) {
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float x = v[8 * s + j];
-            const _Float16 h = (_Float16)x;
-            o.p[0][s][j] = h;
-            o.p[1][s][j] = (_Float16)(x - (float)h);
+            const Split2<_Float16> q = split2(v[8 * s + j]);
+            o.p[0][s][j] = q.h;
+            o.p[1][s][j] = q.l();
         }
     return o;
 }
@@ -251,6 +267,16 @@ int fused_repack_x3(const float* src_tiles, float* dst_tiles, int64_t ntiles, vo
 // 2^-36 / r <= 2^-24 gives r >= 2^-12.  The weight dynamic range the default arithmetic supports is therefore 2^12 between the
 // 32 x 32 tiles of one weight set; beyond it the ctx takes the exact forms (tests/test_host_rescale_refs.py restates split and ratio).
 constexpr float kH3MinTileRatio = 0x1p-12f;
+// The pack-time power-of-two scale of a weight set (fused_repack_h3, pack_upsample_x2): the shift with 2^13 <= max|2^shift w| < 2^14,
+// clamped to [lo, hi] -- the caller's bounds keep 2^shift and whatever undoes it normal floats.  A set whose maximum is zero, NaN or
+// infinite keeps scale 1.
+inline int pow2_shift_below_2_14(float wmax, int lo, int hi) {
+    if (!(wmax > 0.f) || !std::isfinite(wmax)) return 0;
+    int e;
+    (void)std::frexp(wmax, &e);              // wmax = m 2^e, m in [0.5, 1)  ->  wmax 2^(14 - e) in [2^13, 2^14)
+    const int sh = 14 - e;
+    return sh > hi ? hi : sh < lo ? lo : sh;
+}
 inline bool h3_set_holds(float tile_ratio) { return tile_ratio >= kH3MinTileRatio; }      // (false for NaN)
 int fused_repack_h3(const float* src_tiles, float* dst_tiles, int64_t ntiles, int* shift, float* tile_ratio, void* stream,
                     int64_t period = 0, int64_t live = 0);

@@ -5,7 +5,8 @@ A change that is meant to move bits re-records the file (and re-runs the error b
 tests/golden/mdr_form_digests.json does the same for the MDR kernels' other forms (tools/ab_digest.py: form_digests): exact split, fp32-input
 MFMA, config 3 and the whole-head kernels, four-launch and persistent, at B = 11.
 tests/golden/caller_side_digests.json does it for the kernels around the forward (tools/ab_digest.py: caller_digests).
-tests/golden/encoder_form_digests.json does it for every form of the GAT encoder kernels (tools/ab_digest.py: encoder_digests)."""
+tests/golden/encoder_form_digests.json does it for every form of the GAT encoder kernels (tools/ab_digest.py: encoder_digests).
+tests/golden/regressor_form_digests.json does it for every form of the vertex regressor (tools/ab_digest.py: regressor_digests)."""
 import json
 import os
 
@@ -101,6 +102,28 @@ def test_handle_digests_match_the_recorded_build(lib):
     assert len(want) >= 5 and set(got) == set(want)
     bad = {k: (got.get(k), h) for k, h in want.items() if got.get(k) != h}
     assert not bad, 'outputs or workspaces moved against tests/golden/handle_digests.json: %s' % bad
+
+
+REGRESSOR_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'regressor_form_digests.json')
+REGRESSOR_FORMS = ['fp32', 'x3', 'x2', 'bf16', 'c3_default', 'c3_w1_0', 'c3_bf16']
+
+
+@pytest.mark.parametrize('form', REGRESSOR_FORMS)
+def test_regressor_form_digests_match_the_recorded_build(form):
+    """Every form of the vertex regressor bit for bit against the build recorded before its operand slots, packers and epilogue were
+    stated once in csrc/upsample_common.h: the stage entry with its pack kernels (fp32-input, three bf16 planes, two fp16 planes at
+    B = 1, 33, 129, 257, fp32 also at its one-tile -> two-tile switch 224 / 225, bf16 at 1, 33, 65), the head-written operand in a whole
+    forward, the joint epilogue with and without the vertex store, config 3's three regressors, weights times 2^12 (another pack-time
+    shift), and one context through B = 33, 257, 1 (tools/ab_digest.py: regressor_digests)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tools.ab_digest import REGRESSOR_FORMS as forms, regressor_digests
+    assert sorted(forms) == sorted(REGRESSOR_FORMS)
+    want = {k: h for k, h in json.load(open(REGRESSOR_PATH))['digests'].items() if k.startswith(form + ' ')}
+    got = regressor_digests([form])
+    assert len(want) >= 1 and set(got) == set(want)
+    bad = {k: (got.get(k), h) for k, h in want.items() if got.get(k) != h}
+    assert not bad, 'outputs moved bits against tests/golden/regressor_form_digests.json: %s' % bad
 
 
 def test_byte_lo_weight_stream_equals_the_three_plane_stream_bit_for_bit(monkeypatch):

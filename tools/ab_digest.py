@@ -13,7 +13,10 @@
   * `--handles --write tests/golden/handle_digests.json` does the same for handle_digests(): the auxiliary libraries behind a handle (mesh
     renderer, 2D overlay, SMPL layer, fit and backward) on small seeded shapes, with each handle's workspace() after a small, the largest and the small
     call again.
-python tools/ab_digest.py [tag] [--forms | --caller | --encoder | --handles] [--write path [--commit hash-of-the-recorded-build]]"""
+  * `--regressor --write tests/golden/regressor_form_digests.json` does the same for regressor_digests(): every form of the vertex regressor
+    (fp32-input, three bf16 planes, two fp16 planes, bf16, config 3's three) through the stage entry and its packers, the head-written
+    operand, the joint epilogue and a rescaled weight, at the batches where a tile, a workgroup or a kernel choice changes.
+python tools/ab_digest.py [tag] [--forms | --caller | --encoder | --handles | --regressor] [--write path [--commit hash-of-the-recorded-build]]"""
 import contextlib, hashlib, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -501,6 +504,101 @@ def handle_digests(libs=None):
     return out
 
 
+# The vertex regressor's forms (upsample_*.hip behind upsample_common.h).  name: (environment, stage precision or None, stage batches, extras)
+#   stage: pose2mesh.upsample on randn(B, 431, 3) * 0.3 seeded with B -- the stage packers and the regressor kernel.  33: a second tile and a
+#       ragged one; 129: x2's second 128-sample workgroup with three dead waves; 257: x3's ninth tile (second workgroup, seven shadow waves)
+#       and fp32's ragged pair; 224 / 225: fp32's one-tile -> two-tile switch; 65 (bf16): an odd tile count, the last pair repeats its tile.
+#   extras: 'forward' the whole forward at B = 33 (the head-written operand); 'joints' forward_joints at B = 33 with and without the vertex
+#       store, a seeded sparse regressor with an entry at vertex 0 and at 6889; 'scaled' the stage entry with the regressor's weights
+#       times 2^12 (another pack-time shift than the golden one); 'c3' gator_forward_bf16 at B = 33; 'sequence' one context through B = 33,
+#       257, 1 (the x3 plane stride follows the capacity; the row-subset digests of the first and third call must not depend on history).
+REGRESSOR_FORMS = {
+    'fp32': ({'GATOR_UPSAMPLE_X3': '0'}, 'f32', (1, 33, 129, 257, 224, 225), ('forward', 'sequence')),
+    'x3': ({'GATOR_UPSAMPLE_X3': '1'}, 'f32', (1, 33, 129, 257), ('forward', 'joints', 'scaled', 'sequence')),
+    'x2': ({'GATOR_UPSAMPLE_X3': '2'}, 'f32', (1, 33, 129, 257), ('joints', 'scaled', 'sequence')),
+    'bf16': ({}, 'bf16', (1, 33, 65), ('sequence',)),
+    'c3_default': ({}, None, (), ('c3',)),
+    'c3_w1_0': ({'GATOR_C3_UPSAMPLE_W1': '0'}, None, (), ('c3',)),
+    'c3_bf16': ({'GATOR_C3_UPSAMPLE_BF16': '1'}, None, (), ('c3',)),
+}
+REGRESSOR_SWITCHES = ('GATOR_UPSAMPLE_X3', 'GATOR_C3_UPSAMPLE_W1', 'GATOR_C3_UPSAMPLE_BF16')
+REGRESSOR_B = 33
+REGRESSOR_SEQUENCE = (33, 257, 1)
+REGRESSOR_VARIANT = ('h36m17_bn', 17)
+
+
+def _coarse(B, seed=None):
+    return (torch.randn((B, 431, 3), generator=torch.Generator().manual_seed(B if seed is None else seed)) * 0.3).float().cuda()
+
+
+def regressor_digests(forms=None):
+    """{'<form> <case>': digest}.  The switches are read when a context is created, so every form drops the model's contexts first."""
+    import numpy as np
+    out = {}
+    name, J = REGRESSOR_VARIANT
+    for form in (forms or REGRESSOR_FORMS):
+        env, precision, batches, extras = REGRESSOR_FORMS[form]
+        m = build_model(name, 'fused')[1]
+
+        def renew():
+            torch.cuda.synchronize()
+            m.invalidate()
+            m.pose2mesh.invalidate()
+
+        def note(case, *tensors):
+            torch.cuda.synchronize()
+            assert all(bool(torch.isfinite(t).all()) for t in tensors), (form, case)
+            out['%s %s' % (form, case)] = _sha(*tensors)
+
+        with _switches(env, REGRESSOR_SWITCHES):
+            renew()
+            for B in batches:
+                note('stage B=%d' % B, m.pose2mesh.upsample(_coarse(B), precision=precision))
+            x = torch.from_numpy(synthetic.synthetic_pose2d(REGRESSOR_B, J, seed=REGRESSOR_B)).cuda()
+            if 'forward' in extras:
+                note('forward B=%d' % REGRESSOR_B, *m(x))
+            if 'c3' in extras:
+                m.precision = 'bf16'
+                note('forward_bf16 B=%d' % REGRESSOR_B, *m(x))
+                m.precision = 'f32'
+            if 'joints' in extras:
+                rs = np.random.RandomState(13000)
+                dense = _sparse_regressor(rs, 17, 6890)
+                dense[0, 0], dense[16, 6889] = 0.25, -0.5
+                m.set_joint_regressor(dense)
+                for with_verts in (True, False):
+                    note('joints B=%d with_verts=%d' % (REGRESSOR_B, with_verts), *m.forward_joints(x, with_verts=with_verts))
+            if 'sequence' in extras:
+                renew()
+                vc = _coarse(max(REGRESSOR_SEQUENCE), seed=14000)
+                seq = [_sha(m.pose2mesh.upsample(vc[:B].contiguous(), precision=precision)[:1]) for B in REGRESSOR_SEQUENCE]
+                assert seq[0] == seq[2], 'the regressor depends on its workspace history'
+                for B, h in zip(REGRESSOR_SEQUENCE[:2], seq):
+                    out['%s sequence B=%d row 0' % (form, B)] = h
+            if 'scaled' in extras:
+                with torch.no_grad():
+                    m.pose2mesh.upsample_conv.weight.mul_(2.0 ** 12)
+                renew()
+                note('stage B=%d weights * 2^12' % REGRESSOR_B, m.pose2mesh.upsample(_coarse(REGRESSOR_B), precision=precision))
+            renew()
+    return out
+
+
+def main_regressor():
+    write = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
+    d = regressor_digests()
+    for k, h in d.items():
+        print('%-56s %s' % (k, h), flush=True)
+    if write:
+        commit = sys.argv[sys.argv.index('--commit') + 1] if '--commit' in sys.argv else 'unknown'
+        what = ('sha256[:32] per vertex-regressor form (tools/ab_digest.py: regressor_digests), gfx950, golden weights of h36m17_bn: the stage '
+                'entry on randn(B, 431, 3) * 0.3 seeded with B, the whole forward and forward_joints on synthetic_pose2d(33, 17, seed=33), '
+                'gator_forward_bf16 under its three regressor switches, weights times 2^12, and row 0 of one context run through B = 33, 257, 1.  '
+                'Recorded with the library of commit %s' % commit)
+        with open(write, 'w') as f:
+            json.dump({'what': what, 'digests': d}, f, indent=1)
+
+
 def main_handles():
     write = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
     d = handle_digests()
@@ -537,6 +635,8 @@ def main():
         return main_encoder()
     if '--handles' in sys.argv:
         return main_handles()
+    if '--regressor' in sys.argv:
+        return main_regressor()
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
     write = sys.argv[sys.argv.index('--write') + 1] if '--write' in sys.argv else None
     if write in args:
